@@ -11,11 +11,15 @@ textures, coarse phase at epoch 0: sigma=1e-4, opacity noise, decimated textures
 tensors, [RCCL all-reduce of the flat gradient buffer when N > 1], fused Adam on both lr groups.  LPIPS is excluded
 (SURVEY.md 8a A10).  Inputs are resident in HBM before the timed region.  Weak scaling (default): every rank renders V views per
 step; value = N * V * steps / max-over-ranks time.  `--scaling strong` is BASELINE config 3 as written: the SAME 49 views split over
-the ranks (7,6,...,6), value = V * steps / time.  The line also carries, measured in the same run after the timed region: the two
-other training phases of the config (`phases`), the per-step all-reduce time (`allreduce_ms`, N > 1), and at N = 1 the CPU baselines.
+the ranks (7,6,...,6), value = V * steps / time.  A plain run does only that: set-up, warm-up, the timed steps, one JSON line from
+rank 0 (the measurements below are null in it).  `--dump-outputs DIR` then writes what one more call of the timed path, from the seeded
+state the warm-up started from, hands its caller (loss values, parameters after Adam, their gradient, Adam's moments) as DIR/<name>.npy, to
+compare two builds output for output.
 
-Rank 0 prints ONE JSON line, with `roofline` for the dominant kernel (HIP-event timed on the launch stream) and, at N=1,
-`cpu_baseline` (the CPU oracle -- a port, the reference's PyTorch3D path cannot run here -- on a bounded sample)."""
+`--full` adds, measured in the same run after the timed region: the two other training phases of the config (`phases`), the per-step
+all-reduce time (`allreduce_ms`) and the other scaling form (N > 1), `roofline` for the dominant kernel (HIP-event timed on the launch
+stream), and at N = 1 the extra legs and `cpu_baseline` (the CPU oracle -- a port: the reference's own path needs PyTorch3D -- on a
+bounded sample)."""
 import argparse
 import json
 import os
@@ -127,6 +131,46 @@ def build_workload(args, dev):
     del target
     model.train()
     return model, inp
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def write_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: tensor} -> d/<name>.npy, float64 kept, everything else as float32, `limit` bytes in all.  Smallest first, an array is
+    written whole when it fits an equal share of the bytes still free, else as a sample of that many elements drawn with seed 0, in
+    flat-index order: the same elements on every run with the same arguments, so that two runs compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: v.double() if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    free = limit - 256 * len(arrays)                    # (256 B: room for each file's header)
+    order = sorted(arrays, key=lambda k: arrays[k].numel() * arrays[k].element_size())
+    for i, k in enumerate(order):
+        v = arrays[k]
+        m = min(v.numel(), int(free / (len(order) - i)) // v.element_size())
+        if m < v.numel():
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:m].sort().values
+            v = v.reshape(-1)[idx]
+        free -= v.numel() * v.element_size()
+        np.save(os.path.join(d, f'{k}.npy'), v.numpy())
+
+
+def dump_outputs(d, model, step, losses):
+    """What one call of the timed path handed its caller: the loss values `losses`, the parameters Adam moved, the gradient it moved them
+    by and Adam's two moments (the flat buffers of parallel.FlatParams and ShardedTrainStep, in the parameters' shapes).  main() makes that
+    call the first step from the seeded state, where the bias-corrected moments are g and g^2 whatever the betas: the moments themselves,
+    (1 - beta1) g and (1 - beta2) g^2, are what show the betas.  What the optimiser does past its first step (the bias correction at
+    n_steps > 1, moments carried from step to step) is not in the dump."""
+    torch.cuda.synchronize()
+    shapes = {n: p.shape for n, p in model.named_parameters()}
+    arrays = {f'loss_{k}': v for k, v in losses.items() if v is not None}
+    for name, off, k in step.params.names:
+        arrays[f'param_{name}'] = step.params.flat[off:off + k].view(shapes[name])
+        arrays[f'grad_{name}'] = step.params.grad[off:off + k].view(shapes[name])
+        arrays[f'exp_avg_{name}'] = step.exp_avg[off:off + k].view(shapes[name])
+        arrays[f'exp_avg_sq_{name}'] = step.exp_avg_sq[off:off + k].view(shapes[name])
+    write_outputs(d, arrays)
 
 
 BIN_STATS = {}
@@ -389,6 +433,94 @@ def cpu_baseline(args):
     return out
 
 
+def roofline_report(args, step, model, inp, global_count, restore, world, views_per_s, bytes_per_view):
+    """`roofline` of the result line (--full): the dominant kernel of the step, HIP-event timed, against the HBM roofline."""
+    P = args.H * args.W
+    # the kernels of an iteration in exactly the form the step launches them (the fg forward WITH the env layer folded into it, the
+    # composite + MSE epilogue, tiled images): the step's own HIP events around its four big kernels, once with everything in order on ONE
+    # stream (every kernel alone on the GPU: `frac`), once as the step really runs (side streams next to them: `frac_in_step`)
+    K_ = args.fpp
+    B_ = inp['R'].shape[0]
+    fg_bytes, env_bytes = (20 * P * K_ + 16 * P) * B_, (20 * P + 16 * P) * B_
+    if step.cstep is not None and world == 1:
+        restore()
+        alone = step.cstep.kernel_times(inp, global_count, alone=True)
+        folded = alone['env_fwd'] < 0.03 and (step.cstep.fuse & 18) == 18          # no env pass of its own between its two events (an empty pair reads ~5 us)
+        name_of = {'env_fwd': 'render_fwd_fused K=1 (env pass)',
+                   'fg_fwd': f'render_fwd_fused K={K_} (fg pass' + (' + folded env layer)' if folded else ')'),
+                   'fg_bwd': f'render_bwd_fused K={K_} (fg pass)', 'env_bwd': 'render_bwd_fused K=1 (env pass)'}
+        # algorithmic bytes per launch (SURVEY.md 8d, zbuf not materialised): a pass writes 20 P K of fragments + 16 P of image and its
+        # backward reads them back; the folded forward does the env pass's writes (K = 1) too
+        nbytes_of = {'env_fwd': env_bytes, 'fg_fwd': fg_bytes + (env_bytes if folded else 0), 'fg_bwd': fg_bytes, 'env_bwd': env_bytes}
+        kb = {name_of[k]: (v, nbytes_of[k]) for k, v in alone.items() if not (k == 'env_fwd' and folded)}
+        restore()
+        kt = step.cstep.kernel_times(inp, global_count)
+        in_step = {name_of[k]: round(v, 4) for k, v in kt.items() if not (k == 'env_fwd' and folded)}
+        restore()
+    else:
+        kb, in_step = kernel_breakdown(model, inp), None
+    order = sorted(kb, key=lambda k: -kb[k][0])
+    dom = order[0]
+    ms, nbytes = kb[dom]
+    achieved = nbytes / (ms * 1e-3) / 1e9
+
+    def kernel_line(k):
+        t, nb_ = kb[k]
+        return {'kernel': k, 'avg_ms_per_launch': t, 'algorithmic_bytes_per_launch': nb_, 'achieved': nb_ / (t * 1e-3) / 1e9,
+                'frac': nb_ / (t * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                'avg_ms_in_step': None if not in_step else in_step.get(k),
+                'frac_in_step': None if not in_step or not in_step.get(k) else nb_ / (in_step[k] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+    # counter evidence for the dominant kernel from the rocprofv3 PMC passes of this same workload (profiles/, see its _how):
+    # HBM bytes per launch (FETCH_SIZE / WRITE_SIZE with the gfx950 correction) and the SQ issue counters
+    traffic, counters, counters_note = None, None, None
+    sha = csrc_sha16()
+    try:
+        pmc = json.load(open(os.path.join(ROOT, 'profiles', PMC_FILE)))
+        pmc_key = next((k for k in pmc if not k.startswith('_') and k.split(' (')[0] == dom.split(' (')[0] and ('fg' in k) == ('fg' in dom)), None)
+        if inp['R'].shape[0] == 49 and (args.H, args.W, args.fpp, args.blocks, args.txt, args.epoch) == (300, 400, 10, 10, 256, 0) and pmc_key:
+            if pmc.get('_csrc_sha16') == sha:
+                traffic, counters = pmc[pmc_key].get('hbm_bytes'), {k: v for k, v in pmc[pmc_key].items() if k != 'hbm_bytes'}
+            else:       # counters of another build of the kernels say nothing about this one
+                counters_note = f'profiles/{PMC_FILE} was collected on csrc {pmc.get("_csrc_sha16")}, this library is built from {sha}: not reported'
+    except (OSError, ValueError, KeyError):
+        pmc = {}
+    # ... and the HBM bytes measured live, in child processes of this run (N = 1, headline workload; --no-live-counters: the committed value only)
+    traffic_source = None if traffic is None else f'profiles/{PMC_FILE} (committed; keyed on csrc_sha16)'
+    default_workload = inp['R'].shape[0] == 49 and (args.H, args.W, args.fpp, args.blocks, args.txt, args.epoch) == (300, 400, 10, 10, 256, 0)
+    profiled = 'rocprof' in os.environ.get('LD_PRELOAD', '') or any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)       # (no profiler inside a profiler)
+    if world == 1 and default_workload and not (args.no_live_counters or args.no_extras or profiled) and step.cstep is not None:
+        cal = pmc.get('_calibration') if isinstance(pmc, dict) else None
+        cal = {'fetch': float(cal['fetch']), 'write': float(cal['write'])} if cal and 'fetch' in cal and 'write' in cal else {'fetch': 2.0, 'write': 1.0}
+        torch.cuda.synchronize()
+        live, note = live_traffic(dom, cal)
+        if live is not None:
+            committed = traffic
+            traffic, traffic_source = live, note + ('' if committed is None else f'; the committed passes (profiles/{PMC_FILE}) read {committed} B')
+        else:
+            traffic_source = (traffic_source or 'none') + f' (live collection: {note})'
+    return {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+            'traffic': traffic, 'traffic_frac': None if traffic is None else traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            'traffic_source': traffic_source,
+            'avg_ms_per_launch': ms, 'algorithmic_bytes_per_launch': nbytes,
+            # frac: the kernel alone on the GPU, launched by the step itself in order on one stream (HIP events recorded by the
+            # step); frac_in_step: the same launch where it really runs, sharing the GPU with the env backward chain and the
+            # regularisers on their side streams
+            'frac_in_step': None if not in_step or not in_step.get(dom) else nbytes / (in_step[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            'top_kernels': [kernel_line(k) for k in order[:2]],
+            'measured_as': 'dbw_train_step_profile: the kernels the training step launches, in the form it launches them' if in_step is not None
+                           else 'operator-level launches from Python (tools form: fg forward without the folded env layer)',
+            'all_kernels_ms_in_step': in_step,
+            'all_kernels_ms': {k: round(v[0], 4) for k, v in kb.items()}, 'texbins': BIN_STATS or None,
+            'whole_path_frac': views_per_s / world * bytes_per_view / 1e9 / HBM_PEAK_GBS,
+            'counters': counters, 'csrc_sha16': sha,
+            'counters_source': counters_note if counters is None else f'profiles/{PMC_FILE}: separate rocprofv3 --pmc passes of this '
+                               'workload on this build (tools/pmc_sq.sh), committed -- NOT measured in this run (a counter pass '
+                               'serialises the kernels); avg_ms_per_launch, achieved and frac ARE measured in this run (HIP events)',
+            'limiter': 'instruction issue and latency, not HBM: see `counters` (share of the SIMD time the VALU is busy, lane '
+                       f'utilisation, HBM traffic per launch; profiles/{PMC_FILE}) and DESIGN.md section 4; frac is the '
+                       'share of the HBM roofline the ALGORITHMIC bytes reach, traffic_frac the share the measured bytes reach'}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -408,12 +540,16 @@ def main():
     ap.add_argument('--scaling', choices=['auto', 'weak', 'strong'], default='auto', help='strong (default when --gpus > 1): --views in total, sharded '
                     'over the ranks = BASELINE config 3 as written (49 views -> 7,6,...,6), the weak form measured next to it in the same run; '
                     'weak: --views per GPU')
-    ap.add_argument('--no-phases', action='store_true', help='skip the measurement of the two other training phases')
-    ap.add_argument('--no-extras', action='store_true', help='skip the measurements reported next to the headline at N = 1: the reference\'s own '
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what one more step from the seeded starting state '
+                    'computes (loss values, parameters, gradient, Adam\'s moments) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, measure everything reported next to the headline: the other '
+                    'training phases, roofline, the all-reduce and the other scaling form (N > 1), the extra legs and the CPU baselines (N = 1)')
+    ap.add_argument('--no-phases', action='store_true', help='with --full: skip the measurement of the two other training phases')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the measurements reported next to the headline at N = 1: the reference\'s own '
                     'operating point (batch 4, loss values read every step), BASELINE configs 4 and 5 (per-GPU share) and the sustained run')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-live-counters', action='store_true', help='do not collect roofline.traffic in this run (two rocprofv3 --pmc child processes, '
-                    '~1 min at N = 1 on the headline workload): report the committed counters only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-live-counters', action='store_true', help='with --full: do not collect roofline.traffic in this run (two rocprofv3 --pmc '
+                    'child processes, ~1 min at N = 1 on the headline workload): report the committed counters only')
     ap.add_argument('--backward-order', choices=['auto', 'sequential', 'concurrent'], default='auto', help='debug: the two backward kernels')
     ap.add_argument('--no-side-priority', action='store_true', help='debug: the side stream of the native step at normal priority')
     ap.add_argument('--no-overlap', action='store_true', help='everything in order on ONE stream: every kernel alone on the GPU (per-kernel averages of a '
@@ -504,12 +640,26 @@ def main():
     dt, losses = timed(args.steps)
     total_loss = losses['total'].item()
     assert total_loss == total_loss, 'loss is NaN'
+    if args.dump_outputs:
+        # the dumped step is one more call of the timed path, from the seeded state the warm-up started from: the state the last timed step
+        # started from is not the same from run to run (every step sums with unordered fp32 atomics, and the chained optimiser steps grow the
+        # last-bit differences: tools/diag/dump_drift.py, profiles/dump_drift.txt), the state before the first one is.  The state after the
+        # timed steps is put back for --full.
+        after = (step.params.flat.clone(), step.exp_avg.clone(), step.exp_avg_sq.clone(), step.n_steps)
+        restore()
+        replay = step(inp, global_count=global_count)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, step, replay)
+        sync()
+        step.params.flat.copy_(after[0]); step.exp_avg.copy_(after[1]); step.exp_avg_sq.copy_(after[2])
+        step.n_steps = after[3]
+        del replay, after
 
-    # ---- outside the timed region: the other two training phases of the same config, the all-reduce alone ----
+    # ---- outside the timed region (--full): the other two training phases of the same config, the all-reduce alone ----
     PHASES = (('epoch0', 0, 'coarse, decimated textures', 750), ('epoch800', 800, 'coarse, full-resolution textures', 750),
               ('epoch1600', 1600, 'fine', 300))          # default.yml:15-16,39: decimation until 750, coarse until 1500, 1800 epochs
     phases = None
-    if not args.no_phases:
+    if args.full and not args.no_phases:
         phases = {}
         for name, epoch, what, n_ep in PHASES:
             if epoch == args.epoch:
@@ -530,9 +680,10 @@ def main():
     allreduce_ms, allreduce_bytes = None, None
     deferred = step.cstep is not None and step.defer_textures       # the ranks sum the prepared maps' gradient + the small gradients (parallel.py)
     if world > 1:
-        sync()
         bufs = [step.cstep.map_grads(), step.params.grad[:step.params.bounds[0][1]]] if deferred else None
         allreduce_bytes = sum(t.numel() * 4 for t in bufs) if deferred else step.params.flat.numel() * 4
+    if args.full and world > 1:
+        sync()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(5):
@@ -549,7 +700,7 @@ def main():
 
     # ---- N > 1: the other scaling form in the same run, and what the early slice of the all-reduce buys ----
     other_scaling, overlap_off_ms, flat_ms = None, None, None
-    if world > 1:
+    if args.full and world > 1:
         restore()
         model.set_cur_epoch(args.epoch)
         if args.scaling == 'strong':
@@ -591,68 +742,9 @@ def main():
         views_per_s = views_total * args.steps / dt
         P = args.H * args.W
         bytes_per_view = 64 * P * args.fpp + 140 * P                      # whole-path algorithmic bytes
-        # the kernels of an iteration in exactly the form the step launches them (the fg forward WITH the env layer folded into it, the
-        # composite + MSE epilogue, tiled images): the step's own HIP events around its four big kernels, once with everything in order on ONE
-        # stream (every kernel alone on the GPU: `frac`), once as the step really runs (side streams next to them: `frac_in_step`)
-        K_ = args.fpp
-        B_ = inp['R'].shape[0]
-        fg_bytes, env_bytes = (20 * P * K_ + 16 * P) * B_, (20 * P + 16 * P) * B_
-        if step.cstep is not None and world == 1:
-            restore()
-            alone = step.cstep.kernel_times(inp, global_count, alone=True)
-            folded = alone['env_fwd'] < 0.03 and (step.cstep.fuse & 18) == 18          # no env pass of its own between its two events (an empty pair reads ~5 us)
-            name_of = {'env_fwd': 'render_fwd_fused K=1 (env pass)',
-                       'fg_fwd': f'render_fwd_fused K={K_} (fg pass' + (' + folded env layer)' if folded else ')'),
-                       'fg_bwd': f'render_bwd_fused K={K_} (fg pass)', 'env_bwd': 'render_bwd_fused K=1 (env pass)'}
-            # algorithmic bytes per launch (zbuf not materialised): a pass writes 20 P K of fragments + 16 P of image and its
-            # backward reads them back; the folded forward does the env pass's writes (K = 1) too
-            nbytes_of = {'env_fwd': env_bytes, 'fg_fwd': fg_bytes + (env_bytes if folded else 0), 'fg_bwd': fg_bytes, 'env_bwd': env_bytes}
-            kb = {name_of[k]: (v, nbytes_of[k]) for k, v in alone.items() if not (k == 'env_fwd' and folded)}
-            restore()
-            kt = step.cstep.kernel_times(inp, global_count)
-            in_step = {name_of[k]: round(v, 4) for k, v in kt.items() if not (k == 'env_fwd' and folded)}
-            restore()
-        else:
-            kb, in_step = kernel_breakdown(model, inp), None
-        order = sorted(kb, key=lambda k: -kb[k][0])
-        dom = order[0]
-        ms, nbytes = kb[dom]
-        achieved = nbytes / (ms * 1e-3) / 1e9
-
-        def kernel_line(k):
-            t, nb_ = kb[k]
-            return {'kernel': k, 'avg_ms_per_launch': t, 'algorithmic_bytes_per_launch': nb_, 'achieved': nb_ / (t * 1e-3) / 1e9,
-                    'frac': nb_ / (t * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    'avg_ms_in_step': None if not in_step else in_step.get(k),
-                    'frac_in_step': None if not in_step or not in_step.get(k) else nb_ / (in_step[k] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        # counter evidence for the dominant kernel from the rocprofv3 PMC passes of this same workload (profiles/, see its _how):
-        # HBM bytes per launch (FETCH_SIZE / WRITE_SIZE with the gfx950 correction) and the SQ issue counters
-        traffic, counters, counters_note = None, None, None
-        sha = csrc_sha16()
-        try:
-            pmc = json.load(open(os.path.join(ROOT, 'profiles', PMC_FILE)))
-            pmc_key = next((k for k in pmc if not k.startswith('_') and k.split(' (')[0] == dom.split(' (')[0] and ('fg' in k) == ('fg' in dom)), None)
-            if inp['R'].shape[0] == 49 and (args.H, args.W, args.fpp, args.blocks, args.txt, args.epoch) == (300, 400, 10, 10, 256, 0) and pmc_key:
-                if pmc.get('_csrc_sha16') == sha:
-                    traffic, counters = pmc[pmc_key].get('hbm_bytes'), {k: v for k, v in pmc[pmc_key].items() if k != 'hbm_bytes'}
-                else:       # counters of another build of the kernels say nothing about this one
-                    counters_note = f'profiles/{PMC_FILE} was collected on csrc {pmc.get("_csrc_sha16")}, this library is built from {sha}: not reported'
-        except (OSError, ValueError, KeyError):
-            pmc = {}
-        # ... and the HBM bytes measured live, in child processes of this run (N = 1, headline workload; --no-live-counters: the committed value only)
-        traffic_source = None if traffic is None else f'profiles/{PMC_FILE} (committed; keyed on csrc_sha16)'
-        default_workload = inp['R'].shape[0] == 49 and (args.H, args.W, args.fpp, args.blocks, args.txt, args.epoch) == (300, 400, 10, 10, 256, 0)
-        profiled = 'rocprof' in os.environ.get('LD_PRELOAD', '') or any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)       # (no profiler inside a profiler)
-        if world == 1 and default_workload and not (args.no_live_counters or args.no_extras or profiled) and step.cstep is not None:
-            cal = pmc.get('_calibration') if isinstance(pmc, dict) else None
-            cal = {'fetch': float(cal['fetch']), 'write': float(cal['write'])} if cal and 'fetch' in cal and 'write' in cal else {'fetch': 2.0, 'write': 1.0}
-            torch.cuda.synchronize()
-            live, note = live_traffic(dom, cal)
-            if live is not None:
-                committed = traffic
-                traffic, traffic_source = live, note + ('' if committed is None else f'; the committed passes (profiles/{PMC_FILE}) read {committed} B')
-            else:
-                traffic_source = (traffic_source or 'none') + f' (live collection: {note})'
+        roofline = None
+        if args.full:
+            roofline = roofline_report(args, step, model, inp, global_count, restore, world, views_per_s, bytes_per_view)
         local_views = inp['R'].shape[0]
         out = {
             'metric': 'rendered views/sec (fwd+bwd) per node, DTU 400x300 K=10 blocks', 'value': views_per_s, 'unit': 'views/s',
@@ -677,33 +769,13 @@ def main():
                            f'{step.params.flat.numel() * 4 / 1e6:.1f} MB of gradients all-reduced per step over RCCL'
                            + (' (blocks\' textures overlapped with the env backward, the rest after it)' if step.overlap_allreduce else '')),
                        'nranks': dist.get_world_size() if world > 1 else 1},
-            'roofline': {'bound': 'hbm', 'kernel': dom, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic, 'traffic_frac': None if traffic is None else traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         'traffic_source': traffic_source,
-                         'avg_ms_per_launch': ms, 'algorithmic_bytes_per_launch': nbytes,
-                         # frac: the kernel alone on the GPU, launched by the step itself in order on one stream (HIP events recorded by the
-                         # step); frac_in_step: the same launch where it really runs, sharing the GPU with the env backward chain and the
-                         # regularisers on their side streams
-                         'frac_in_step': None if not in_step or not in_step.get(dom) else nbytes / (in_step[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         'top_kernels': [kernel_line(k) for k in order[:2]],
-                         'measured_as': 'dbw_train_step_profile: the kernels the training step launches, in the form it launches them' if in_step is not None
-                                        else 'operator-level launches from Python (tools form: fg forward without the folded env layer)',
-                         'all_kernels_ms_in_step': in_step,
-                         'all_kernels_ms': {k: round(v[0], 4) for k, v in kb.items()}, 'texbins': BIN_STATS or None,
-                         'whole_path_frac': views_per_s / world * bytes_per_view / 1e9 / HBM_PEAK_GBS,
-                         'counters': counters, 'csrc_sha16': sha,
-                         'counters_source': counters_note if counters is None else f'profiles/{PMC_FILE}: separate rocprofv3 --pmc passes of this '
-                                            'workload on this build (tools/pmc_sq.sh), committed -- NOT measured in this run (a counter pass '
-                                            'serialises the kernels); avg_ms_per_launch, achieved and frac ARE measured in this run (HIP events)',
-                         'limiter': 'instruction issue and latency, not HBM: see `counters` (share of the SIMD time the VALU is busy, lane '
-                                    f'utilisation, HBM traffic per launch; profiles/{PMC_FILE}) and DESIGN.md section 4; frac is the '
-                                    'share of the HBM roofline the ALGORITHMIC bytes reach, traffic_frac the share the measured bytes reach'},
+            'roofline': roofline,
             'phases': phases, 'allreduce_ms': allreduce_ms, 'allreduce_path': getattr(step, 'allreduce_path', None), 'other_scaling': other_scaling, 'ms_per_step_overlap_allreduce_off': overlap_off_ms, 'ms_per_step_flat_allreduce': flat_ms, 'allreduce_bytes': allreduce_bytes,
             'final_loss': total_loss,
             # polls between the step's streams that gave up (dbw_train_step_sync_timeouts): anything but 0 voids the run
             'sync_timeouts': step.cstep.sync_timeouts() if step.cstep is not None and step.cstep._cur is not None else None,
         }
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             default = (args.views, args.H, args.W, args.blocks, args.fpp, args.txt, args.epoch) == (49, 300, 400, 10, 10, 256, 0)
             if default:
                 del step, model, inp
@@ -741,7 +813,7 @@ def main():
                 for name, cfg_, st_ in (('c4', (8, 576, 768, 20, 16, 256), 20), ('c5', (25, 1080, 1920, 50, 16, 512), 5)):
                     r = measure_other(*cfg_, dev, steps=st_, warmup=3, epoch=800)
                     out['configs'][name]['full_resolution_phase'] = {k: r[k] for k in ('ms_per_step', 'views_per_s', 'whole_path_frac', 'steps')}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args)
         print(json.dumps(out))
     if world > 1:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the whole bench.py line (driver protocol + every extra leg), with a readable digest.  usage: r06_bench.sh <tag> [bench args]
 O=gpurun_out/r06/$1; shift; mkdir -p $O
-timeout 1800 python bench.py "$@" > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+timeout 1800 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
 python - $O/bench.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

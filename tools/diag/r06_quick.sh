@@ -7,7 +7,7 @@ if [ "$tests" != "-" ]; then timeout 1500 python -m pytest $tests -x -q > $O/tes
 for round in 1 2; do
   for v in "$@"; do
     if [ $v = tree ]; then unset DBW_HIP_LIB; else export DBW_HIP_LIB=tools/variants/$v.so; fi
-    timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $epoch > $O/bench_${v}_$round.json 2> $O/bench_${v}_$round.err
+    timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $epoch > $O/bench_${v}_$round.json 2> $O/bench_${v}_$round.err
     python - $O/bench_${v}_$round.json $v <<'PY'
 import json, sys
 try:

@@ -5,9 +5,9 @@ O=gpurun_out/r03; mkdir -p $O; export TMPDIR=/tmp
 # (the cycle-accounting build must be of the same sources as the library: rebuild it when it is older)
 [ tools/variants/fprof.so -nt differentiable-blocksworld_amd/dbw_amd/libdbw_hip.so ] || tools/variants.sh fprof "-DDBW_PROFILE_FWD" > /dev/null 2>&1
 for e in 0 800 1600; do
-  rocprofv3 --kernel-trace -d $O/t$e -o p --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $e > $O/t$e.log 2>&1
+  rocprofv3 --kernel-trace -d $O/t$e -o p --output-format csv -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $e > $O/t$e.log 2>&1
   csv=$(find $O/t$e -name "*kernel_trace.csv" | head -1)
-  python tools/rocprof_csv_summary.py $csv $O/r03_kernel_stats_epoch$e.txt "python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $e (rocprofv3 --kernel-trace)" > /dev/null
+  python tools/rocprof_csv_summary.py $csv $O/r03_kernel_stats_epoch$e.txt "python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-phases --no-extras --epoch $e (rocprofv3 --kernel-trace)" > /dev/null
   python tools/step_sequence.py $csv > $O/r03_step_sequence_epoch$e.txt 2>&1
   rm -rf $O/t$e
 done
@@ -23,7 +23,7 @@ cp $O/pmc/bench_counters.json $O/r03_pmc_counters.json
 rm -rf $O/pmc/g1 $O/pmc/g2 $O/pmc/g3 $O/pmc/g4
 DBW_HIP_LIB=tools/variants/fprof.so python tools/fwd_cycles.py 0 > $O/r03_fwd_cycle_accounting.txt 2>&1
 DBW_HIP_LIB=tools/variants/fprof.so python tools/fwd_timeline.py 0 > $O/r03_fwd_timeline.txt 2>&1
-python bench.py > $O/r03_bench.json 2> $O/r03_bench.err
+python bench.py --full > $O/r03_bench.json 2> $O/r03_bench.err
 tail -2 $O/r03_bench.err
 head -12 $O/r03_kernel_stats_epoch0.txt
 python -c "
