@@ -23,19 +23,7 @@
 
 using namespace dbw;
 
-// Fragments, gradient images and texel-gradient records are produced once and consumed once, a gigabyte of traffic later: they are
-// loaded / stored non-temporally so that they stream past the L2 instead of evicting the tables the kernels keep coming back to
-#ifndef DBW_NT_LOADS
-#define DBW_NT_LOADS 1
-#endif
-template <class T>
-__device__ __forceinline__ T ld_stream(const T *p) {
-#if DBW_NT_LOADS
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+// (fragments, gradient images and texel-gradient records stream: ld_stream / DBW_NT_LOADS, shade_common.h)
 __device__ __forceinline__ void st_stream4(int4 *p, int4 v) {
 #if DBW_NT_LOADS
     int *q = (int *)p;
@@ -1291,59 +1279,15 @@ int dbw_fill_shade_args(ShadeArgs &A, const int32_t *pix_to_face, const float *b
 
 // ---- the hard single-layer pass (sky + ground), specialised: hard uv-fragments (layout 3) ---------------------------------------------
 // K = 1, sigma = 0, no learned opacity, texel gradients through the LDS hash (magnified / decimated maps).  The forward leaves (clipped
-// face, u, v, face | map) per pixel; this kernel loads them with the pixel's image gradient -- four coalesced loads -- and runs the
-// per-pixel backward of env_bwd.h (the same function the training step's fused forward runs in its epilogue).
+// face, u, v, face | map) per pixel; this kernel loads them with the pixel's image gradient, P tiles of 8x8 pixels per wave, and runs
+// the backward of env_bwd.h.
+constexpr int HARD_P = DBW_HARD_P;
 __global__ __launch_bounds__(NT) void render_bwd_hard_kernel(ShadeArgs A, long long total_blocks, const float *__restrict__ gimg,
                                                             float *__restrict__ gmaps, const float *__restrict__ fv,
                                                             float *__restrict__ gfv, int want_bary, int persp) {
     extern __shared__ __attribute__((aligned(16))) float s_hard[];
-    HardTexAgg tex_agg;
-    HardFaceAgg face_agg;
-    tex_agg.bind(s_hard);
-    tex_agg.clear(threadIdx.x, NT);
-    face_agg.bind((char *)s_hard + HardTexAgg::BYTES);
-    face_agg.clear(threadIdx.x, NT);
-    int n, xi, yi;
-    if (!pixel_of_block(A, total_blocks, n, xi, yi)) return;
-    __syncthreads();
-    const bool in_img = xi < A.W && yi < A.H;
-    int fc = -1, jm = 0;
-    float u = 0.f, v = 0.f, gr = 0.f, gg = 0.f, gbl = 0.f;
-    const float gs = A.gscale ? *A.gscale : 1.f;
-    if (A.tiled && A.img_tiled) {
-        // 8x8-tile planar fragments and images (the training step): a wave's quadrant is ONE tile -- scalar base + lane, immediate plane offsets
-        const int tiles_x = (A.W + 7) >> 3, tiles_y = (A.H + 7) >> 3;
-        const int lane = threadIdx.x & 63;
-        const bool real = (yi >> 3) < tiles_y && (xi >> 3) < tiles_x;       // (a 16x16 workgroup at the border can hold quadrants outside the tile grid)
-        const int tile = __builtin_amdgcn_readfirstlane(real ? (n * tiles_y + (yi >> 3)) * tiles_x + (xi >> 3) : n * tiles_y * tiles_x);
-        if (in_img && real) {
-            fc = ld_stream(A.p2f + ((long long)tile << 6) + lane);
-            if (fc >= 0) {
-                const float *b = A.bary + ((long long)tile * 3 << 6) + lane, *gi = gimg + ((long long)tile * 4 << 6) + lane;
-                u = ld_stream(b); v = ld_stream(b + 64); jm = __float_as_int(ld_stream(b + 128));
-                gr = ld_stream(gi) * gs; gg = ld_stream(gi + 64) * gs; gbl = ld_stream(gi + 128) * gs;
-            }
-        }
-    } else {
-        const FragAddr o = frag_addr(A, n, yi, xi, 0);
-        fc = in_img ? ld_stream(A.p2f + o.s) : -1;
-        if (fc >= 0) {
-            u = ld_stream(A.bary + o.b); v = ld_stream(A.bary + o.b + o.bstride); jm = __float_as_int(ld_stream(A.bary + o.b + 2 * o.bstride));
-            const ImgAddr ia = img_addr(A, n, yi, xi, 4);
-            const float *gi = gimg + ia.base;
-            gr = ld_stream(gi) * gs; gg = ld_stream(gi + ia.cstride) * gs; gbl = ld_stream(gi + 2 * ia.cstride) * gs;
-        }
-    }
-    const bool valid = fc >= 0;
-    const float gc[3] = {gr, gg, gbl};               // blend weight of a hard fragment = 1
-    EnvBwdArgs E;
-    E.map_desc = A.map_desc; E.maps = A.maps; E.face_uvs = A.face_uvs; E.code = A.c2o ? A.code : nullptr; E.cw = A.cw; E.fv = fv; E.gmaps = gmaps; E.gfv = gfv;
-    E.H = A.H; E.W = A.W; E.geom_begin = A.geom_begin; E.want_bary = want_bary; E.persp = persp;
-    for (int i = 0; i < 4; ++i) E.ndc[i] = A.ndc[i];
-    env_bwd_pixel(E, tex_agg, face_agg, valid, fc, u, v, jm, gc, xi, yi);
-    __syncthreads();
-    tex_agg.flush(gmaps, threadIdx.x, NT);
-    face_agg.flush(gfv, threadIdx.x, NT);
+    __shared__ __attribute__((aligned(16))) int s_md[MD_CACHE_MAPS * 8];
+    env_bwd_region<HARD_P>(A, total_blocks, gimg, gmaps, fv, gfv, want_bary, persp, s_hard, s_md);
 }
 
 __global__ void flag_store_kernel(unsigned *flag, unsigned v) { __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1402,7 +1346,8 @@ static int launch_bwd(ShadeArgs &A, int N, int H, int W, int K, const float *gra
         return dbw_check_launch("render_bwd_uv_kernel");
     }
     if (A.tiled == 3) {       // hard uv-fragments: validated by the caller (K == 1, sigma == 0, no opacities, LDS aggregation)
-        hipLaunchKernelGGL(render_bwd_hard_kernel, dim3(dbw_xcd_grid(total)), dim3(NT), HardTexAgg::BYTES + HardFaceAgg::BYTES, s, A, total, grad_image,
+        const long long regions = HardRegion<HARD_P>::blocks(N, H, W);
+        hipLaunchKernelGGL(render_bwd_hard_kernel, dim3(dbw_xcd_grid(regions)), dim3(NT), HardTexAgg::BYTES + HardFaceAgg::BYTES, s, A, regions, grad_image,
                            grad_maps, fv, gfv, want_bary, persp);
         return dbw_check_launch("render_bwd_hard_kernel");
     }

@@ -7,6 +7,20 @@
 
 namespace dbw {
 
+// Fragments, gradient images and texel-gradient records are produced once and consumed once, a gigabyte of traffic later: they are
+// loaded / stored non-temporally so that they stream past the L2 instead of evicting the tables the kernels keep coming back to
+#ifndef DBW_NT_LOADS
+#define DBW_NT_LOADS 1
+#endif
+template <class T>
+__device__ __forceinline__ T ld_stream(const T *p) {
+#if DBW_NT_LOADS
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
 #ifndef DBW_TEX_LOG2
 #define DBW_TEX_LOG2 8       // 128 / 256 / 512 / 1024 slots: uv backward 0.49 / 0.323 / 0.353 / 0.54 ms at config 2 (round 3, after the lane merge:
 #endif                       // 19 instead of 26 KB of LDS per workgroup = 8 instead of 5-6 waves per SIMD; 128 slots overflow into memory atomics)
@@ -64,8 +78,9 @@ struct ShadeArgs {
 // The map descriptors of a pass in LDS.  A fragment's footprint starts with its map's six descriptor ints; read from memory that is
 // a dependent round trip per fragment (face | map comes out of the fragment itself) in front of every table update of the backward.
 // Row 0 of map_desc carries the number of rows in its 7th int (include/dbw_hip.h; 0 = not given): tables of up to MD_CACHE_MAPS rows are
-// copied to LDS once per workgroup, larger or uncounted ones are read from memory as before.  Used by the binned uv backward only: the
-// instantiation for decimated maps is bound by the LDS atomic unit, and the extra LDS reads cost it 0.39 -> 0.41 ms.
+// copied to LDS once per workgroup, larger or uncounted ones are read from memory as before.  Used by the binned uv backward and by the
+// hard pass's backward (env_bwd.h); not by the uv backward on decimated maps, which is bound by the LDS atomic unit, and the extra LDS
+// reads cost it 0.39 -> 0.41 ms.
 #ifndef DBW_MD_LDS
 #define DBW_MD_LDS 1
 #endif
