@@ -133,6 +133,25 @@ OTHER_SIGNATURES = {
     'dbw_lpips_head_blocks': (c_i, [c_i, c_i]),
 }
 
+# the 3D evaluation entry points: name -> argtypes, exactly the prototypes of include/dbw_eval.h (checked by tests/test_eval3d_host.py).
+# A table of their own: SIGNATURES / OTHER_SIGNATURES stay the prototypes of include/dbw_hip.h.
+EVAL_SIGNATURES = {
+    'dbw_nn_points': [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    'dbw_dtu_lattice_counts': [c_p, c_i64, c_p, c_p],
+    'dbw_dtu_lattice_points': [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p],
+    'dbw_radius_downsample_round': [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_d, c_p, c_p, c_p],
+}
+
+
+def _header_eval_abi_version():
+    """DBW_EVAL_ABI_VERSION of include/dbw_eval.h (dbw_eval_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_eval.h')) as f:
+        return int(re.search(r'#define DBW_EVAL_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+EVAL_ABI_VERSION = _header_eval_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -175,6 +194,12 @@ def load():
         if hasattr(lib, name):                  # (absent from tuning builds of older sources)
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
+    if hasattr(lib, 'dbw_eval_abi_version'):    # (absent from tuning builds of older sources: eval3d refuses to run on them)
+        lib.dbw_eval_abi_version.restype = c_i
+        for name, argtypes in EVAL_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
     _lib = lib
     return lib
 

@@ -354,6 +354,18 @@ class DifferentiableBlocksWorld(nn.Module):
         return PackedScene(verts.reshape(-1, 3), self._block_faces_all[:F_], self._block_face_uvs_all[:F_],
                            self._block_face_map_all[:F_], desc, maps.reshape(-1), texbins)
 
+    def blocks_mesh(self, filter_transparent=True):
+        """-> (verts (V,3) fp32, faces (F,3) int64): the posed blocks in world coordinates, live ones only, joined into one mesh in block
+        order -- what the reference's build_blocks(filter_transparent, as_scene=True).get_mesh_verts_faces(0) returns (dbw.py:297-346), the
+        mesh the DTU evaluation scores (eval3d.evaluate_dtu).  An evaluation-time call: under sync_free the kept blocks are packed on the
+        host all the same, and the per-step state of the last forward is left as it was."""
+        with torch.no_grad(), self._host_packed_rebuild():
+            scene = self.build_blocks_scene(filter_transparent=filter_transparent)
+        dev = self.alpha_logit.device
+        if scene is None:
+            return torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev)
+        return scene.verts.detach().clone(), scene.faces.to(torch.int64)
+
     def build_scene(self, filter_transparent=False):
         """Background + ground + blocks as ONE scene (dbw.py:250-266), for the non-decoupled hard / SSAA evaluation render."""
         env = self.build_env_scene()

@@ -1,0 +1,520 @@
+"""3D evaluation of a reconstruction: Chamfer distance and the official DTU protocol, on the GPU (include/dbw_eval.h).
+
+The reference computes these at the end of a DTU run through PyTorch3D's CUDA `knn_points` / `sample_points_from_meshes`
+(utils/chamfer.py) and through open3d plus an sklearn KD-tree (utils/dtu_eval.py); neither has a ROCm build.  Here the hot path -- exact
+nearest neighbours, the DTU dense lattice and its radius downsample -- is HIP (csrc/nn_search.hip) and torch / numpy do the plumbing.
+
+    nn_points(x, y)                       exact 1-nearest neighbour (knn_points with K = 1)            -> (dist2, idx)
+    chamfer_distance(x, y, ...)           utils/chamfer.py:7-160 (L1 / L2, direction reductions)      -> (cham_dist, cham_normals)
+    sample_points_from_meshes(v, f, n)    PyTorch3D 0.7.1 ops/sample_points_from_meshes.py             -> (1, n, 3) points [, normals]
+    chamfer_l1_scores(v, f, gt, scale)    the custom Chamfer-L1 of mbf_eval.py:54-60 / ems_eval.py:55-61 -> (acc, comp)
+    dtu_scores(v, f, obs_mask, ...)       dtu_eval.py:47-160 on arrays                                 -> dict(acc, comp, avg, counts)
+    evaluate_mesh(v, f, scan_id, ...)     dtu_eval.py:47-164 on a DTU directory, writes dtu_scores{suffix}.tsv
+    evaluate_dtu(model, scale_mat, ...)   trainer.py:255-264: the live blocks of a model, scaled by scale_mat, evaluated
+"""
+import ctypes
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+MAX_DIST = 20                  # dtu_eval.py:16-18
+PATCH = 60
+DOWNSAMPLE_DENSITY = 0.2
+CHAMFER_FACTOR = 10            # mbf_eval.py / ems_eval.py: the custom Chamfer-L1 is reported x10
+
+
+def _p(t):
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _call(name, *args):
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_eval_abi_version'):
+        raise RuntimeError(f'{_lib.LIB_PATH} has no 3D evaluation entry points (include/dbw_eval.h): rebuild it')
+    if lib.dbw_eval_abi_version() != _lib.EVAL_ABI_VERSION:
+        raise RuntimeError(f'the library was built for eval ABI {lib.dbw_eval_abi_version()}, include/dbw_eval.h declares '
+                           f'{_lib.EVAL_ABI_VERSION}: rebuild it')
+    _lib.call(name, *args)
+
+
+# ------------------------------------------------------------------------------------------------ nearest neighbours
+def _lengths(lengths, N, P, dev):
+    if lengths is None:
+        return torch.full((N,), P, dtype=torch.int64, device=dev)
+    return torch.as_tensor(lengths, device=dev).to(torch.int64).clamp(0, P).contiguous()
+
+
+def nn_points_torch(x, y, x_lengths=None, y_lengths=None, chunk_elems=1 << 22):
+    """nn_points by chunked brute force in torch, on any device: same distance expression ((dx*dx + dy*dy) + dz*dz, one rounding per
+    elementwise op), same tie rule (lowest index).  The CPU path of nn_points and the yardstick of the GPU tests."""
+    N, P1, _ = x.shape
+    P2 = y.shape[1]
+    xl = _lengths(x_lengths, N, P1, 'cpu').tolist()
+    yl = _lengths(y_lengths, N, P2, 'cpu').tolist()
+    dist2 = torch.zeros(N, P1, dtype=torch.float32, device=x.device)
+    idx = torch.full((N, P1), -1, dtype=torch.int64, device=x.device)
+    for n in range(N):
+        lx, ly = xl[n], yl[n]
+        if ly == 0:
+            dist2[n, :lx] = math.inf
+            continue
+        yn = y[n, :ly].float()
+        ar = torch.arange(ly, device=x.device)
+        step = max(1, chunk_elems // ly)
+        for a in range(0, lx, step):
+            b = min(lx, a + step)
+            d = x[n, a:b, None, :].float() - yn[None]
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            m = d2.min(1).values
+            dist2[n, a:b] = m
+            idx[n, a:b] = torch.where(d2 == m[:, None], ar, ly).min(1).values
+    return dist2, idx
+
+
+def nn_points(x, y, x_lengths=None, y_lengths=None, splits=0):
+    """Exact 1-nearest neighbour of every x[n, i] among y[n, :y_lengths[n]] -> (dist2 (N,P1) fp32, idx (N,P1) int64).
+
+    dist2 = ((dx*dx + dy*dy) + dz*dz), d = x - y in fp32; ties go to the lowest index; a query at or past x_lengths gets (0, -1), a batch
+    with y_lengths == 0 gets (+inf, -1).  Device tensors use the HIP kernel (dbw_nn_points; `splits` forces the number of y ranges merged
+    by the 64-bit atomic min, 0 = from the sizes: the result does not depend on it), CPU tensors the chunked torch brute force.  No
+    gradient (chamfer_distance recomputes the distances of the chosen pairs in torch)."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != 3 or y.shape[2] != 3 or x.shape[0] != y.shape[0]:
+        raise ValueError(f'nn_points: x (N,P1,3) and y (N,P2,3) expected, got {tuple(x.shape)} and {tuple(y.shape)}')
+    if x.device.type == 'cpu' and y.device.type == 'cpu':
+        return nn_points_torch(x.detach(), y.detach(), x_lengths, y_lengths)
+    if x.device != y.device or x.device.type != 'cuda':
+        raise ValueError('nn_points: x and y must be on the same device')
+    N, P1, _ = x.shape
+    P2 = y.shape[1]
+    dev = x.device
+    xs = x.detach().to(torch.float32).contiguous()
+    ys = y.detach().to(torch.float32).contiguous()
+    dist2 = torch.empty(N, P1, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, P1, dtype=torch.int64, device=dev)
+    if P1 == 0:
+        return dist2, idx
+    if P2 == 0:
+        return dist2.fill_(math.inf), idx.fill_(-1)
+    xl = None if x_lengths is None else _lengths(x_lengths, N, P1, dev)
+    yl = None if y_lengths is None else _lengths(y_lengths, N, P2, dev)
+    keys = torch.empty(N * P1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _call('dbw_nn_points', _p(xs), _p(ys), _p(xl), _p(yl), N, P1, P2, int(splits), _p(keys), _p(dist2), _p(idx), _stream(dev))
+    return dist2, idx
+
+
+# ------------------------------------------------------------------------------------------------ Chamfer distance
+def _validate_chamfer_reduction_inputs(batch_reduction, point_reduction):      # pytorch3d/loss/chamfer.py
+    if batch_reduction is not None and batch_reduction not in ['mean', 'sum']:
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction not in ['mean', 'sum']:
+        raise ValueError('point_reduction must be one of ["mean", "sum"]')
+
+
+def _handle_pointcloud_input(points, lengths, normals):                          # pytorch3d/loss/chamfer.py (tensors only)
+    if points.ndim != 3:
+        raise ValueError('Expected points to be of shape (N, P, D)')
+    X = points
+    if lengths is not None and (lengths.ndim != 1 or lengths.shape[0] != X.shape[0]):
+        raise ValueError('Expected lengths to be of shape (N,)')
+    if lengths is None:
+        lengths = torch.full((X.shape[0],), X.shape[1], dtype=torch.int64, device=points.device)
+    if normals is not None and normals.ndim != 3:
+        raise ValueError('Expected normals to be of shape (N, P, 3')
+    return X, lengths, normals
+
+
+def _nn_dist2(x, y, idx, mask):
+    """differentiable squared distance of x to its neighbour y[idx] (the kernel's expression); masked queries see distance 1"""
+    g = y.gather(1, idx.clamp(min=0)[..., None].expand(-1, -1, 3))
+    d = x - g
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return d2 if mask is None else torch.where(mask, torch.ones_like(d2), d2)
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None, batch_reduction='mean',
+                     point_reduction='mean', direction_reduction='sum', return_L1=False):
+    """utils/chamfer.py:7-160 (PyTorch3D's chamfer_distance with the Chamfer-L1 and the direction reductions of the reference):
+    same arguments, defaults and return values -> (cham_dist, cham_normals); direction_reduction 'none' / None returns the pairs
+    (cham_x, cham_y) and (cham_norm_x, cham_norm_y).
+
+    The neighbours come from nn_points (the HIP kernel for device tensors); the distances of the chosen pairs are recomputed in torch from
+    x and y[idx], so autograd gives what PyTorch3D's knn backward gives, in x, y and the normals.  Masking, weighting and the return_L1
+    square root are written out of place (the reference's in-place `cham_x[x_mask] = 0.0` after the square root cannot be
+    differentiated); the values are the same, and the square root keeps torch's behaviour at a zero distance."""
+    _validate_chamfer_reduction_inputs(batch_reduction, point_reduction)
+    x, x_lengths, x_normals = _handle_pointcloud_input(x, x_lengths, x_normals)
+    y, y_lengths, y_normals = _handle_pointcloud_input(y, y_lengths, y_normals)
+    return_normals = x_normals is not None and y_normals is not None
+    N, P1, D = x.shape
+    P2 = y.shape[1]
+    if y.shape[0] != N or y.shape[2] != D:
+        raise ValueError('y does not have the correct shape.')
+    is_x_heterogeneous = bool((x_lengths != P1).any())
+    is_y_heterogeneous = bool((y_lengths != P2).any())
+    x_mask = torch.arange(P1, device=x.device)[None] >= x_lengths[:, None]
+    y_mask = torch.arange(P2, device=y.device)[None] >= y_lengths[:, None]
+    if weights is not None:
+        if weights.size(0) != N:
+            raise ValueError('weights must be of shape (N,).')
+        if not (weights >= 0).all():
+            raise ValueError('weights cannot be negative.')
+        if weights.sum() == 0.0:
+            weights = weights.view(N, 1)
+            if batch_reduction in ['mean', 'sum']:
+                return (x.sum((1, 2)) * weights).sum() * 0.0, (x.sum((1, 2)) * weights).sum() * 0.0
+            return (x.sum((1, 2)) * weights) * 0.0, (x.sum((1, 2)) * weights) * 0.0
+
+    cham_norm_x = x.new_zeros(())
+    cham_norm_y = x.new_zeros(())
+    _, x_idx = nn_points(x, y, x_lengths, y_lengths)
+    _, y_idx = nn_points(y, x, y_lengths, x_lengths)
+    xm = x_mask if is_x_heterogeneous else None
+    ym = y_mask if is_y_heterogeneous else None
+    cham_x = _nn_dist2(x, y, x_idx, xm)
+    cham_y = _nn_dist2(y, x, y_idx, ym)
+    if return_L1:
+        cham_x, cham_y = cham_x.sqrt(), cham_y.sqrt()
+    if is_x_heterogeneous:
+        cham_x = torch.where(x_mask, torch.zeros_like(cham_x), cham_x)
+    if is_y_heterogeneous:
+        cham_y = torch.where(y_mask, torch.zeros_like(cham_y), cham_y)
+    if weights is not None:
+        cham_x = cham_x * weights.view(N, 1)
+        cham_y = cham_y * weights.view(N, 1)
+
+    if return_normals:
+        x_normals_near = y_normals.gather(1, x_idx.clamp(min=0)[..., None].expand(-1, -1, y_normals.shape[2]))
+        y_normals_near = x_normals.gather(1, y_idx.clamp(min=0)[..., None].expand(-1, -1, x_normals.shape[2]))
+        cham_norm_x = 1 - torch.abs(F.cosine_similarity(x_normals, x_normals_near, dim=2, eps=1e-6))
+        cham_norm_y = 1 - torch.abs(F.cosine_similarity(y_normals, y_normals_near, dim=2, eps=1e-6))
+        if is_x_heterogeneous:
+            cham_norm_x = torch.where(x_mask, torch.zeros_like(cham_norm_x), cham_norm_x)
+        if is_y_heterogeneous:
+            cham_norm_y = torch.where(y_mask, torch.zeros_like(cham_norm_y), cham_norm_y)
+        if weights is not None:
+            cham_norm_x = cham_norm_x * weights.view(N, 1)
+            cham_norm_y = cham_norm_y * weights.view(N, 1)
+
+    cham_x = cham_x.sum(1)
+    cham_y = cham_y.sum(1)
+    if return_normals:
+        cham_norm_x = cham_norm_x.sum(1)
+        cham_norm_y = cham_norm_y.sum(1)
+    if point_reduction == 'mean':
+        cham_x = cham_x / x_lengths
+        cham_y = cham_y / y_lengths
+        if return_normals:
+            cham_norm_x = cham_norm_x / x_lengths
+            cham_norm_y = cham_norm_y / y_lengths
+    if batch_reduction is not None:
+        cham_x = cham_x.sum()
+        cham_y = cham_y.sum()
+        if return_normals:
+            cham_norm_x = cham_norm_x.sum()
+            cham_norm_y = cham_norm_y.sum()
+        if batch_reduction == 'mean':
+            div = weights.sum() if weights is not None else N
+            cham_x = cham_x / div
+            cham_y = cham_y / div
+            if return_normals:
+                cham_norm_x = cham_norm_x / div
+                cham_norm_y = cham_norm_y / div
+
+    if direction_reduction is None or direction_reduction == 'none':
+        cham_dist = (cham_x, cham_y)
+        cham_normals = (cham_norm_x, cham_norm_y) if return_normals else None
+    else:
+        cham_dist = cham_x + cham_y
+        cham_normals = cham_norm_x + cham_norm_y if return_normals else None
+        if direction_reduction == 'mean':
+            cham_dist, cham_normals = 0.5 * cham_dist, 0.5 * cham_normals if return_normals else None
+    return cham_dist, cham_normals
+
+
+# ------------------------------------------------------------------------------------------------ mesh sampling
+def sample_points_from_meshes(verts, faces, num_samples, return_normals=False, generator=None, return_face_idx=False):
+    """PyTorch3D 0.7.1 `sample_points_from_meshes` for ONE mesh (verts (V,3), faces (F,3)) -> points (1, num_samples, 3)
+    [, normals (1, num_samples, 3)] [, face index (num_samples,)].
+
+    Restated from memory of PyTorch3D 0.7.1 (the package is not available here), like SURVEY.md Appendix A: faces are drawn with
+    replacement by `multinomial` over the face areas 0.5 * |(v1 - v0) x (v2 - v0)|, then `torch.rand(2, 1, num_samples)` gives u, v and
+    w = (1 - sqrt(u), sqrt(u) * (1 - v), sqrt(u) * v); point = (w0 * v0 + w1 * v1) + w2 * v2 of the sampled face.  Normals are the
+    normalised (v1 - v0) x (v2 - v1) of the sampled face (norm clamped at the fp64 epsilon).  Differentiable in verts."""
+    faces = faces.to(device=verts.device, dtype=torch.int64)
+    fv = verts[faces]
+    v0, v1, v2 = fv[:, 0], fv[:, 1], fv[:, 2]
+    with torch.no_grad():
+        areas = 0.5 * torch.linalg.cross(v1 - v0, v2 - v0, dim=1).norm(dim=1)
+        fidx = areas[None].multinomial(num_samples, replacement=True, generator=generator)[0]
+    uv = torch.rand(2, 1, num_samples, dtype=verts.dtype, device=verts.device, generator=generator)
+    u_sqrt = uv[0].sqrt()
+    w0, w1, w2 = 1.0 - u_sqrt, u_sqrt * (1.0 - uv[1]), u_sqrt * uv[1]
+    pts = w0[:, :, None] * v0[fidx][None] + w1[:, :, None] * v1[fidx][None] + w2[:, :, None] * v2[fidx][None]
+    out = [pts]
+    if return_normals:
+        n = torch.linalg.cross(v1 - v0, v2 - v1, dim=1)
+        n = n / n.norm(dim=1, p=2, keepdim=True).clamp(min=np.finfo(np.float64).eps)
+        out.append(n[fidx][None])
+    if return_face_idx:
+        out.append(fidx)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def chamfer_l1_scores(verts, faces, gt_points, scale_mat, n_points=500_000, generator=None):
+    """The custom Chamfer-L1 of the reference's baseline scripts (mbf_eval.py:54-60, ems_eval.py:55-61): n_points samples of the mesh
+    (sample_points_from_meshes), brought into the normalised frame with the inverse of the VolSDF `scale_mat` (points @ inv[:3,:3] +
+    inv[:3,3]), Chamfer-L1 against gt_points (P,3) with direction_reduction='none', times 10 -> (acc, comp) floats."""
+    dev = verts.device
+    pts = sample_points_from_meshes(verts, faces, n_points, generator=generator)
+    scale_inv = torch.as_tensor(scale_mat).to(dev).inverse()
+    pts = pts @ scale_inv[:3, :3] + scale_inv[:3, 3]
+    gt = torch.as_tensor(gt_points).to(device=dev, dtype=pts.dtype)[None]
+    acc, comp = chamfer_distance(pts, gt, return_L1=True, direction_reduction='none')[0]
+    return CHAMFER_FACTOR * acc.item(), CHAMFER_FACTOR * comp.item()
+
+
+# ------------------------------------------------------------------------------------------------ DTU protocol
+def _device(dev):
+    dev = torch.device('cuda' if dev is None else dev)
+    if dev.type != 'cuda':
+        raise ValueError('the DTU evaluation runs its lattice, downsample and search kernels on the GPU: pass a cuda device')
+    return dev
+
+
+def compact_mesh(verts, faces):
+    """open3d's remove_unreferenced_vertices: the referenced vertices in their order, faces renumbered"""
+    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+    used[faces.reshape(-1)] = True
+    new_id = torch.cumsum(used.to(torch.int64), 0) - 1
+    return verts[used], new_id[faces]
+
+
+def dense_lattice(verts, faces):
+    """The dense point cloud of dtu_eval.py:56-78 (HIP kernels, fp64): the vertices (all referenced ones, in order) followed by the lattice
+    of every face of non-zero area in face order, each in np.mgrid row-major order -> (points (n,3) fp64, per-face counts (F,) int64).
+    verts (V,3) fp32 or fp64 and faces (F,3) on a cuda device; unreferenced vertices are dropped first."""
+    dev = verts.device
+    v64, faces = compact_mesh(verts.to(torch.float64), faces.to(device=dev, dtype=torch.int64))
+    F_ = faces.shape[0]
+    counts = torch.zeros(F_, dtype=torch.int64, device=dev)
+    if F_ == 0:
+        return v64.contiguous(), counts
+    tri = v64[faces].contiguous()                                            # (F,3,3)
+    with torch.cuda.device(dev):
+        _call('dbw_dtu_lattice_counts', _p(tri), F_, _p(counts), _stream(dev))
+        offsets = torch.cumsum(counts, 0) - counts
+        total = int(counts.sum())
+        pts = torch.empty(v64.shape[0] + total, 3, dtype=torch.float64, device=dev)
+        pts[:v64.shape[0]] = v64
+        if total:
+            _call('dbw_dtu_lattice_points', _p(tri), F_, _p(counts), _p(offsets), total, _p(pts[v64.shape[0]:]), _stream(dev))
+    return pts, counts
+
+
+def radius_downsample(points, radius=DOWNSAMPLE_DENSITY):
+    """The greedy downsample of dtu_eval.py:82-96 in the given order: point i is kept iff no earlier KEPT point lies within `radius`
+    (distance <= radius, fp64).  Computed exactly as a parallel maximal independent set over a uniform grid (cell size >= radius, torch
+    sorts the points by cell): each round (dbw_radius_downsample_round) keeps the undecided points without an earlier undecided or kept
+    neighbour and removes those with an earlier kept one.  O(log n) rounds for a random order (Blelloch, Fineman and Shun, SPAA 2012).
+    points (n,3) fp64 on a cuda device -> (keep mask (n,) bool, number of rounds)."""
+    dev = points.device
+    n = points.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=dev), 0
+    p = points.to(torch.float64)
+    lo = p.min(0).values
+    cell = torch.floor((p - lo) / (radius * (1 + 1e-6))).to(torch.int64) + 1      # a border of empty cells: no neighbour key aliases
+    dims = (cell.max(0).values + 2).tolist()
+    if dims[0] * dims[1] * dims[2] >= 1 << 62:
+        raise ValueError('radius_downsample: the grid is too large for 64-bit cell keys')
+    keys = (cell[:, 0] * dims[1] + cell[:, 1]) * dims[2] + cell[:, 2]
+    keys_s, rank = torch.sort(keys, stable=True)                # within a cell: the processing order
+    pts_s = p[rank].contiguous()
+    st = [torch.zeros(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)]
+    rounds, open_ = 0, n
+    with torch.cuda.device(dev):
+        while open_:
+            _call('dbw_radius_downsample_round', _p(pts_s), _p(keys_s), _p(rank), n, dims[1], dims[2], float(radius), _p(st[0]), _p(st[1]),
+                  _stream(dev))
+            st.reverse()
+            rounds += 1
+            left = int((st[0] == 0).sum())
+            if left >= open_:                                   # (the earliest undecided point is always decided: cannot happen)
+                raise RuntimeError('radius_downsample: a round decided nothing')
+            open_ = left
+    keep = torch.empty(n, dtype=torch.bool, device=dev)
+    keep[rank] = st[0] == 1
+    return keep, rounds
+
+
+def _nn_fp64(q, ref, center):
+    """nearest neighbour of every q among ref: searched in fp32 on coordinates centred on `center`, the chosen pair's distance recomputed in
+    fp64 -> distances (len(q),) float64 numpy"""
+    if len(q) == 0:
+        return np.zeros(0)
+    if len(ref) == 0:
+        return np.full(len(q), np.inf)
+    dev = q.device
+    c = torch.as_tensor(center, dtype=torch.float64, device=dev)
+    _, idx = nn_points((q - c).float()[None], (ref - c).float()[None])
+    d = q - ref[idx[0]]
+    return torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).cpu().numpy()
+
+
+def dtu_scores(verts, faces, obs_mask, bb, res, plane, stl, order=None, seed=None, device=None):
+    """The official DTU protocol (dtu_eval.py:47-160) on arrays -> dict(acc, comp, avg, n_vertices, n_lattice, n_points, n_down,
+    n_in_obs, n_stl_above, n_d2s, n_s2d, rounds).
+
+    verts (V,3) / faces (F,3) in the DTU frame (mm), obs_mask / bb / res: the ObsMask, BB, Res of ObsMask{id}_10.mat, plane: P of
+    Plane{id}.mat, stl (M,3): the ground-truth points.  The dense cloud (dense_lattice) is shuffled with `order` (a permutation of its
+    n_points rows: shuffled[k] = cloud[order[k]]) or, when order is None, with np.random.default_rng(seed).permutation.  The reference
+    shuffles with an UNSEEDED default_rng(), so its scores are not reproducible from run to run; a fixed seed here is.  Then the greedy
+    radius downsample (radius_downsample), the masks of the reference with its exact semantics (BB - PATCH <= p < BB + 2 PATCH, np.around
+    half to even, ObsMask lookup, plane test), and the two searches: data in ObsMask -> stl (acc) and stl above the plane -> data inside
+    the box (comp, fitted on data_in, not on the ObsMask-filtered set).  Means over the distances < MAX_DIST (20 mm), in fp64.
+    n_d2s / n_s2d count the distances below MAX_DIST."""
+    dev = _device(device)
+    v = torch.as_tensor(verts).to(dev)
+    if v.dtype != torch.float64:
+        v = v.to(torch.float32)
+    f = torch.as_tensor(faces).to(device=dev, dtype=torch.int64)
+    pcd, counts = dense_lattice(v, f)
+    n = pcd.shape[0]
+    if order is None:
+        order = np.random.default_rng(seed).permutation(n)
+    order = torch.as_tensor(np.asarray(order), dtype=torch.int64, device=dev)
+    if order.shape != (n,):
+        raise ValueError(f'dtu_scores: order must be a permutation of the {n} points of the dense cloud')
+    pcd = pcd[order].contiguous()
+    keep, rounds = radius_downsample(pcd, DOWNSAMPLE_DENSITY)
+    data_down = pcd[keep].cpu().numpy()
+
+    BB = np.asarray(bb).astype(np.float32)
+    res = np.asarray(res)
+    obs_mask = np.asarray(obs_mask)
+    inbound = ((data_down >= BB[:1] - PATCH) & (data_down < BB[1:] + PATCH * 2)).sum(axis=-1) == 3
+    data_in = data_down[inbound]
+    data_grid = np.around((data_in - BB[:1]) / res).astype(np.int32)
+    grid_inbound = ((data_grid >= 0) & (data_grid < np.expand_dims(obs_mask.shape, 0))).sum(axis=-1) == 3
+    data_grid_in = data_grid[grid_inbound]
+    in_obs = obs_mask[data_grid_in[:, 0], data_grid_in[:, 1], data_grid_in[:, 2]].astype(np.bool_)
+    data_in_obs = data_in[grid_inbound][in_obs]
+
+    stl = np.asarray(stl, dtype=np.float64)
+    stl_hom = np.concatenate([stl, np.ones_like(stl[:, :1])], -1)
+    above = (np.asarray(plane).reshape((1, 4)) * stl_hom).sum(-1) > 0
+    stl_above = stl[above]
+
+    center = (BB[0].astype(np.float64) + BB[1].astype(np.float64)) / 2
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)         # noqa: E731
+    d_in = t(data_in)
+    dist_d2s = _nn_fp64(t(data_in_obs), t(stl), center)
+    dist_s2d = _nn_fp64(t(stl_above), d_in, center)
+    d2s, s2d = dist_d2s[dist_d2s < MAX_DIST], dist_s2d[dist_s2d < MAX_DIST]
+    mean_d2s = float(d2s.mean()) if len(d2s) else float('nan')
+    mean_s2d = float(s2d.mean()) if len(s2d) else float('nan')
+    return dict(acc=mean_d2s, comp=mean_s2d, avg=(mean_d2s + mean_s2d) / 2, n_vertices=n - int(counts.sum()), n_lattice=int(counts.sum()),
+                n_points=n, n_down=int(len(data_down)), n_in_obs=int(len(data_in_obs)), n_stl_above=int(len(stl_above)), n_d2s=int(len(d2s)),
+                n_s2d=int(len(s2d)), rounds=rounds)
+
+
+# ------------------------------------------------------------------------------------------------ files
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def read_ply_points(path):
+    """x, y, z of the `vertex` element of a PLY file (ascii or binary_little_endian) -> (n,3) float64.  Elements before `vertex` must have
+    fixed-size properties; what follows it is not read."""
+    with open(path, 'rb') as fh:
+        if fh.readline().strip() != b'ply':
+            raise ValueError(f'{path}: not a PLY file')
+        fmt, elements = None, []
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError(f'{path}: no end_header')
+            tok = line.decode('ascii', 'replace').split()
+            if not tok or tok[0] in ('comment', 'obj_info'):
+                continue
+            if tok[0] == 'end_header':
+                break
+            if tok[0] == 'format':
+                fmt = tok[1]
+            elif tok[0] == 'element':
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == 'property':
+                if tok[1] == 'list':
+                    elements[-1][2].append((tok[4], None))
+                else:
+                    elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+        if fmt not in ('ascii', 'binary_little_endian'):
+            raise ValueError(f'{path}: PLY format {fmt} is not supported (ascii, binary_little_endian)')
+        for name, count, props in elements:
+            if name == 'vertex':
+                if any(t is None for _, t in props):
+                    raise ValueError(f'{path}: list property in the vertex element')
+                names = [p for p, _ in props]
+                if fmt == 'ascii':
+                    rows = [fh.readline().split() for _ in range(count)]
+                    arr = np.array(rows, dtype=np.float64).reshape(count, len(props))
+                    return np.stack([arr[:, names.index(c)] for c in 'xyz'], 1)
+                dt = np.dtype([(p, '<' + t) for p, t in props])
+                arr = np.frombuffer(fh.read(dt.itemsize * count), dtype=dt, count=count)
+                return np.stack([arr[c].astype(np.float64) for c in 'xyz'], 1)
+            if any(t is None for _, t in props):
+                raise ValueError(f'{path}: variable-size element {name} before the vertices')
+            if fmt == 'ascii':
+                for _ in range(count):
+                    fh.readline()
+            else:
+                fh.read(np.dtype([(p, '<' + t) for p, t in props]).itemsize * count)
+    raise ValueError(f'{path}: no vertex element')
+
+
+def write_scores_tsv(path, acc, comp, avg):
+    """dtu_scores{suffix}.tsv exactly as dtu_eval.py:162-164 writes it (no newline after the values)"""
+    with open(path, 'w') as f:
+        f.write('acc\tcomp\tavg\n')
+        f.write(f'{float(acc)}\t{float(comp)}\t{float(avg)}')
+
+
+def load_dtu_scan(scan_id, dataset_dir):
+    """(obs_mask, bb, res, plane, stl) of a DTU scan: ObsMask/ObsMask{id}_10.mat, ObsMask/Plane{id}.mat, Points/stl/stl{id:03}_total.ply"""
+    from scipy.io import loadmat
+    m = loadmat(f'{dataset_dir}/ObsMask/ObsMask{scan_id}_10.mat')
+    plane = loadmat(f'{dataset_dir}/ObsMask/Plane{scan_id}.mat')['P']
+    stl = read_ply_points(f'{dataset_dir}/Points/stl/stl{scan_id:03}_total.ply')
+    return m['ObsMask'], m['BB'], m['Res'], plane, stl
+
+
+def evaluate_mesh(verts, faces, scan_id, dataset_dir, eval_dir, suffix='', seed=None, order=None, device=None):
+    """dtu_eval.py:47-164 on a mesh (verts (V,3) in the DTU frame, faces (F,3)) and a DTU directory laid out like the reference's: the
+    scores of dtu_scores, written to {eval_dir}/dtu_scores{suffix}.tsv in the reference's format -> the dtu_scores dict.  The
+    reference's `save_viz` point clouds are not produced."""
+    obs_mask, bb, res, plane, stl = load_dtu_scan(scan_id, dataset_dir)
+    dev = device if device is not None else (verts.device if torch.is_tensor(verts) and verts.is_cuda else None)
+    s = dtu_scores(verts, faces, obs_mask, bb, res, plane, stl, order=order, seed=seed, device=dev)
+    os.makedirs(eval_dir, exist_ok=True)
+    write_scores_tsv(os.path.join(str(eval_dir), f'dtu_scores{suffix}.tsv'), s['acc'], s['comp'], s['avg'])
+    return s
+
+
+def evaluate_dtu(model, scale_mat, scan_id, dataset_dir, eval_dir, suffix='', seed=None):
+    """trainer.py:255-264: the blocks of a trained model (filter_transparent=True, world coordinates: model.blocks_mesh) brought to the DTU
+    frame with `verts @ scale_mat[:3, :3] + scale_mat[:3, 3]` (the scale_mat of cameras.load_idr_cameras) and evaluated with
+    evaluate_mesh -> the dtu_scores dict (dtu_scores{suffix}.tsv in eval_dir)."""
+    verts, faces = model.blocks_mesh(filter_transparent=True)
+    scale = torch.as_tensor(scale_mat).to(device=verts.device, dtype=verts.dtype)
+    verts = verts @ scale[:3, :3] + scale[:3, 3]
+    return evaluate_mesh(verts, faces, scan_id, dataset_dir, eval_dir, suffix=suffix, seed=seed, device=verts.device)

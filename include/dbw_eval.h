@@ -1,0 +1,51 @@
+/*
+ * dbw_eval.h -- C ABI of the 3D evaluation entry points of libdbw_hip.so: exact nearest neighbours (the Chamfer distance of
+ * utils/chamfer.py, PyTorch3D's knn_points with K = 1) and the kernels of the official DTU protocol (utils/dtu_eval.py: the dense
+ * triangle lattice and the greedy radius downsample).  Python side: dbw_amd/eval3d.py, bound through _lib.EVAL_SIGNATURES.
+ *
+ * Conventions are those of dbw_hip.h: DEVICE pointers owned by the caller, contiguous; return 0 or a negative DBW_ERR_*, the text in
+ * dbw_last_error(); arguments are validated before any launch; kernels are enqueued on `stream`, no host synchronisation.
+ */
+#ifndef DBW_EVAL_H
+#define DBW_EVAL_H
+#include "dbw_hip.h"
+
+/* ABI revision of this header (dbw_eval_abi_version() returns the value the library was built with). */
+#define DBW_EVAL_ABI_VERSION 1
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int dbw_eval_abi_version(void);
+
+/* Exact 1-nearest neighbour of every x[n, i] among y[n, 0 .. y_lengths[n]), fp32:
+ *   dist2 = ((dx*dx + dy*dy) + dz*dz) with d = x - y, one rounding per operation; ties go to the lowest index.
+ *   x (N,P1,3), y (N,P2,3) fp32; x_lengths / y_lengths (N,) int64 or NULL (= P1 / P2); keys (N*P1) uint64 workspace;
+ *   dist2 (N,P1) fp32, idx (N,P1) int64.  A query at or past x_lengths[n] gets idx -1, dist2 0; a batch with y_lengths[n] == 0 gets
+ *   idx -1, dist2 +inf.  splits: number of y ranges per batch searched by separate workgroups and merged with a 64-bit atomic min on
+ *   (dist2 bits << 32 | idx), 0 = chosen from the sizes; the result does not depend on it.  P1, P2 < 2^31. */
+int dbw_nn_points(const float *x, const float *y, const int64_t *x_lengths, const int64_t *y_lengths, int N, int P1, int P2, int splits,
+                  void *keys, float *dist2, int64_t *idx, dbw_stream_t stream);
+
+/* DTU dense lattice (dtu_eval.py:21-30,56-78), fp64 in numpy's order of operations.  tri (F,3,3): the three vertices of every face.
+ * counts (F) int64: lattice points of each face (0 for a face of zero area). */
+int dbw_dtu_lattice_counts(const double *tri, int64_t F, int64_t *counts, dbw_stream_t stream);
+/* points (n_out,3) fp64: the lattice of face f at rows offsets[f] .. offsets[f] + counts[f], in np.mgrid row-major order.  A face whose
+ * range does not fit in n_out writes nothing. */
+int dbw_dtu_lattice_points(const double *tri, int64_t F, const int64_t *counts, const int64_t *offsets, int64_t n_out, double *points,
+                           dbw_stream_t stream);
+
+/* One round of the greedy radius downsample (dtu_eval.py:82-96) as a parallel maximal independent set.  points (n,3) fp64 sorted by
+ * cell_keys (n) int64 ascending, key = (cx * ny + cy) * nz + cz of a uniform grid of cell size >= radius whose cell coordinates start at 1
+ * (a border of empty cells on every side); rank (n) int64: each point's position in the processing order.  status_in / status_out (n)
+ * int32: 0 undecided, 1 kept, 2 removed.  An undecided point with an earlier kept point within radius (distance <= radius) is removed; one
+ * with no earlier undecided or kept point within radius is kept; the others stay undecided.  Repeat (swapping the two) until no point is
+ * undecided: the kept set is that of the sequential loop. */
+int dbw_radius_downsample_round(const double *points, const int64_t *cell_keys, const int64_t *rank, int64_t n, int64_t ny, int64_t nz,
+                                double radius, const int32_t *status_in, int32_t *status_out, dbw_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
