@@ -13,6 +13,7 @@
 //   regularisers      (model_ops.hip)     parsimony + overlap (samples drawn in registers) + its finish   [was 4]
 //   clip_bwd_tex      (project_clip.hip)  the blocks' projection backward next to the backward of their texture preparation [was 2]
 //   blocks_tail       (model_ops.hip)     backward of the blocks' pose / shape (from the points the prologue kept) + of their opacities [was 2]
+//   adam_tail         (texture.hip)       backward of the sky / ground texture preparation + Adam + the run's void latch + arena clear [was 2]
 //   + the env layer inside the fg pass (render_fused.hip) and the cross-stream signals inside scene_setup / work_scatter / the uv backward
 // (What is NOT fused, on purpose: a chain of dependent kernels on ONE stream enqueued from C runs without gaps -- measured -- so fusing
 // dependent kernels buys nothing unless the fusion is parallel over the same index space, and a "last workgroup finishes the job" epilogue
@@ -122,6 +123,24 @@ struct ClipBwdArgs {
     const int *num_faces, *c2o, *code; const float *cw, *gfvc; float *gverts;
 };
 int launch_clip_bwd_tex(const ClipBwdArgs &C, const dbw_texture_set &tex, hipStream_t s);
+
+// The step's last launch (texture.hip), behind the join with the env chain: the backward of the texture preparation of `tex` (the sky and
+// the ground: their texture and grad_texture inside the flat buffers) with dbw_texture_prep_bwd_sets's arithmetic, Adam on both lr groups
+// using those gradients from registers (bit-equal to the two launches), the run's void latch, and the zero-arena clear.  The maps' gradients
+// the launch reads lie in the arena: [hole_begin, hole_end) (bytes from zero_buf) is not cleared by the arena loop but by the lanes that
+// read them -- at decimation d > 1 one wave per cell, whose lanes 0..2 each clear the value they read, so that nobody clears a cell
+// another wave still reads.  An empty hole: the maps' gradients are left as they are.
+struct AdamTailArgs {
+    float *param, *grad, *exp_avg, *exp_avg_sq; const int64_t *group_end; const float *lr; int ngroups;
+    float beta1, beta2, eps; int step;
+    void *zero_buf; int64_t zero_bytes, hole_begin, hole_end;
+    dbw_texture_set tex[2]; int ntex;
+    const float *void_raised; float *void_flag;     // every thread: nothing moves when *void_raised != 0; the first thread: *void_flag = *void_raised
+};
+// adam_tail_fits: the sets' texture / grad_texture lie in the flat buffers at the same index, their maps' gradients inside the hole (if
+// any), the hole inside the arena (else the caller enqueues dbw_texture_prep_bwd_sets + dbw_adam_step_groups)
+bool adam_tail_fits(const AdamTailArgs &A);
+int launch_adam_tail(const AdamTailArgs &A, hipStream_t s);
 
 // the env layer folded into the fg pass (render_fused.hip): the env scene's workspace (per-tile lists and shading records filled by the
 // set-up kernels), its maps and background, and where its hard uv-fragments go (frag_layout 3: what the env backward reads)

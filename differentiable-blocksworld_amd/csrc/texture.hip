@@ -4,9 +4,11 @@
 #include "dbw_common.h"
 #include "loss_math.h"
 #include "texture_body.h"
+#include "step_kernels.h"
 #include "../../include/dbw_hip.h"
 
 #include <string.h>
+#include <algorithm>
 
 using namespace dbw;
 
@@ -159,6 +161,92 @@ __global__ void adam_groups_kernel(float *__restrict__ p, const float *__restric
         zero_buf[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+__device__ __forceinline__ float group_step_size(const AdamGroups &G, long long i) {
+    float step_size = G.step_size[0];
+#pragma unroll
+    for (int k = 1; k < MAX_SETS; ++k) step_size = i >= G.end[k - 1] ? G.step_size[k] : step_size;
+    return step_size;
+}
+
+// The training step's last launch (step_kernels.h: AdamTailArgs): the backward of the texture preparation of up to two sets whose texture and
+// gradient lie in the flat buffers, Adam on both lr groups with those gradients from registers, the run's void latch and the zero-arena clear.
+// The prepared maps' gradients lie in the arena (the hole): they are cleared by the lanes that read them, never by the arena loop.  The
+// grid is split by the amount of work: the first `nenv` workgroups run the texture sets, the others Adam on the remaining elements (a
+// compacted index that steps over the sets' ranges), so that neither half waits for the other's stragglers.
+struct AdamTex { const float *tex; const float *gsig; float *gmaps; int n, h, w, d; long long off; };
+struct AdamTailK {
+    float *p, *g, *m, *v; long long n; AdamGroups G; float beta1, beta2, eps, bc2_sqrt;
+    uint4 *zero_buf; long long zero_vec, hole_lo, hole_hi;
+    AdamTex t[2]; int ntex, clear_maps, nenv;
+    long long skip_lo[2], skip_len[2];       // the sets' ranges in ascending order (unused: lo = n, len = 0)
+    const float *void_raised; float *void_flag;
+};
+
+// the backward of one set's texture preparation -- the same arithmetic as texture_prep_bwd_body, element by element -- and Adam on its
+// elements, by threads etid of neth
+__device__ __forceinline__ void adam_tex_set(const AdamTailK &A, const AdamTex &t, bool skip, long long etid, long long neth) {
+    if (t.d <= 1) {
+        const long long total = (long long)t.n * t.h * t.w * 3;
+        for (long long i = etid; i < total; i += neth) {
+            const float s = tex_sigmoid(t.tex[i]);
+            float g = t.gmaps[i];
+            if (A.clear_maps) t.gmaps[i] = 0.f;
+            if (t.gsig) g += t.gsig[i];
+            const float gt = g * s * (1.f - s);
+            const long long o = t.off + i;
+            A.g[o] = gt;
+            if (!skip) adam_update(A.p[o], gt, A.m[o], A.v[o], group_step_size(A.G, o), A.beta1, A.beta2, A.eps, A.bc2_sqrt);
+        }
+        return;
+    }
+    // decimated: one wave per cell -- every lane reads the cell's three gradients, lanes 0..2 clear the one they read behind their uses of
+    // it, so no wave clears a cell another one still reads
+    const float inv = 1.f / (float)(t.d * t.d);
+    const int ch_ = t.h / t.d, cw_ = t.w / t.d, lane = threadIdx.x & 63;
+    const long long cells = (long long)t.n * ch_ * cw_;
+    for (long long c = etid >> 6; c < cells; c += neth >> 6) {
+        const int m = (int)(c / ((long long)ch_ * cw_));
+        const int r = (int)(c % ((long long)ch_ * cw_));
+        const int cy = r / cw_, cx = r % cw_;
+        const float gc[3] = {t.gmaps[c * 3], t.gmaps[c * 3 + 1], t.gmaps[c * 3 + 2]};
+        for (int q = lane; q < t.d * t.d; q += 64) {
+            const long long e = (((long long)m * t.h + cy * t.d + q / t.d) * t.w + cx * t.d + q % t.d) * 3;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const long long i = e + ch;
+                const float s = tex_sigmoid(t.tex[i]);
+                float g = gc[ch] * inv;
+                if (t.gsig) g += t.gsig[i];
+                const float gt = g * s * (1.f - s);
+                const long long o = t.off + i;
+                A.g[o] = gt;
+                if (!skip) adam_update(A.p[o], gt, A.m[o], A.v[o], group_step_size(A.G, o), A.beta1, A.beta2, A.eps, A.bc2_sqrt);
+            }
+        }
+        if (A.clear_maps && lane < 3) t.gmaps[c * 3 + lane] = 0.f;       // (program order: behind this lane's uses of gc)
+    }
+}
+
+__global__ __launch_bounds__(NT) void adam_groups_tex_kernel(const AdamTailK A) {
+    const bool skip = *A.void_raised != 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && A.void_flag) *A.void_flag = *A.void_raised;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+    const long long neth = (long long)A.nenv * blockDim.x;
+    if (tid < neth) {
+        for (int k = 0; k < A.ntex; ++k) adam_tex_set(A, A.t[k], skip, tid, neth);
+    } else if (!skip) {
+        const long long rest = A.n - A.skip_len[0] - A.skip_len[1];
+        for (long long j = tid - neth; j < rest; j += nth - neth) {
+            long long i = j;
+            if (i >= A.skip_lo[0]) i += A.skip_len[0];
+            if (i >= A.skip_lo[1]) i += A.skip_len[1];
+            adam_update(A.p[i], A.g[i], A.m[i], A.v[i], group_step_size(A.G, i), A.beta1, A.beta2, A.eps, A.bc2_sqrt);
+        }
+    }
+    for (long long i = tid; i < A.zero_vec; i += nth)
+        if (i < A.hole_lo || i >= A.hole_hi) A.zero_buf[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 inline unsigned grid_for(long long work) {
     long long b = (work + NT - 1) / NT;
     if (b < 1) b = 1;
@@ -215,6 +303,17 @@ TextureSets pack_sets(const dbw_texture_set *sets, int nsets) {
     TextureSets S;
     for (int i = 0; i < MAX_SETS; ++i) S.s[i] = sets[i < nsets ? i : 0];
     return S;
+}
+AdamGroups adam_groups(const int64_t *group_end, const float *lr, int ngroups, float beta1, float beta2, int step, float &bc2_sqrt) {
+    const long long n = group_end[ngroups - 1];
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    AdamGroups G;
+    for (int k = 0; k < MAX_SETS; ++k) {
+        G.end[k] = k < ngroups ? group_end[k] : n;
+        G.step_size[k] = (float)(lr[k < ngroups ? k : ngroups - 1] / bc1);
+    }
+    bc2_sqrt = (float)sqrt(bc2);
+    return G;
 }
 }  // namespace
 
@@ -273,15 +372,87 @@ extern "C" int dbw_adam_step_groups(float *param, const float *grad, float *exp_
     for (int k = 0; k < ngroups; ++k) DBW_REQUIRE(group_end[k] >= (k ? group_end[k - 1] : 0), "group ends must not decrease");
     const long long n = group_end[ngroups - 1];
     if (n == 0) return DBW_OK;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    AdamGroups G;
-    for (int k = 0; k < MAX_SETS; ++k) {
-        G.end[k] = k < ngroups ? group_end[k] : n;
-        G.step_size[k] = (float)(lr[k < ngroups ? k : ngroups - 1] / bc1);
-    }
+    float bc2_sqrt;
+    const AdamGroups G = adam_groups(group_end, lr, ngroups, beta1, beta2, step, bc2_sqrt);
     hipLaunchKernelGGL(adam_groups_kernel, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, G,
-                       beta1, beta2, eps, (float)sqrt(bc2), (uint4 *)zero_buf, (long long)(zero_bytes / 16), skip_flag);
+                       beta1, beta2, eps, bc2_sqrt, (uint4 *)zero_buf, (long long)(zero_bytes / 16), skip_flag);
     return dbw_check_launch("adam_groups_kernel");
+}
+
+bool dbw::adam_tail_fits(const AdamTailArgs &A) {
+    if (!A.param || !A.grad || !A.exp_avg || !A.exp_avg_sq || !A.group_end || !A.lr || !A.void_raised || A.ngroups < 1 || A.ngroups > MAX_SETS) return false;
+    if (A.ntex < 0 || A.ntex > 2 || A.zero_bytes < 0 || A.zero_bytes % 16 || ((uintptr_t)A.zero_buf & 15)) return false;
+    if (A.hole_begin < 0 || A.hole_begin > A.hole_end || A.hole_end > A.zero_bytes || A.hole_begin % 16 || A.hole_end % 16) return false;
+    const long long n = A.group_end[A.ngroups - 1];
+    const char *hb = (const char *)A.zero_buf + A.hole_begin, *he = (const char *)A.zero_buf + A.hole_end;
+    long long lo[2] = {0, 0}, hi[2] = {0, 0};
+    for (int k = 0; k < A.ntex; ++k) {
+        const dbw_texture_set &t = A.tex[k];
+        if (!t.texture || !t.grad_maps || !t.grad_texture || t.n < 1 || t.h < 1 || t.w < 1 || t.decim < 1 || t.h % t.decim || t.w % t.decim) return false;
+        lo[k] = (long long)(t.grad_texture - A.grad);
+        hi[k] = lo[k] + (long long)t.n * t.h * t.w * 3;
+        if (t.grad_texture < A.grad || hi[k] > n || t.texture != A.param + lo[k]) return false;
+        const char *mb = (const char *)t.grad_maps, *me = mb + (size_t)t.n * (t.h / t.decim) * (t.w / t.decim) * 3 * sizeof(float);
+        const char *zb = (const char *)A.zero_buf, *ze = zb + A.zero_bytes;
+        if (A.hole_end > A.hole_begin ? (mb < hb || me > he) : (mb < ze && me > zb)) return false;     // (read while the arena loop clears)
+    }
+    return A.ntex < 2 || hi[0] <= lo[1] || hi[1] <= lo[0];
+}
+
+int dbw::launch_adam_tail(const AdamTailArgs &A, hipStream_t s) {
+    DBW_REQUIRE(adam_tail_fits(A), "the texture sets must lie in the flat buffers, their maps' gradients in the hole of the arena");
+    DBW_REQUIRE(A.step >= 1, "step >= 1");
+    for (int k = 0; k < A.ngroups; ++k) DBW_REQUIRE(A.group_end[k] >= (k ? A.group_end[k - 1] : 0), "group ends must not decrease");
+    AdamTailK K;
+    memset(&K, 0, sizeof(K));
+    K.p = A.param; K.g = A.grad; K.m = A.exp_avg; K.v = A.exp_avg_sq; K.n = A.group_end[A.ngroups - 1];
+    K.G = adam_groups(A.group_end, A.lr, A.ngroups, A.beta1, A.beta2, A.step, K.bc2_sqrt);
+    K.beta1 = A.beta1; K.beta2 = A.beta2; K.eps = A.eps;
+    K.zero_buf = (uint4 *)A.zero_buf; K.zero_vec = A.zero_bytes / 16; K.hole_lo = A.hole_begin / 16; K.hole_hi = A.hole_end / 16;
+    K.ntex = A.ntex; K.clear_maps = A.hole_end > A.hole_begin ? 1 : 0;
+    for (int k = 0; k < A.ntex; ++k) {
+        const dbw_texture_set &t = A.tex[k];
+        K.t[k].tex = t.texture; K.t[k].gsig = t.grad_sig; K.t[k].gmaps = (float *)t.grad_maps;
+        K.t[k].n = t.n; K.t[k].h = t.h; K.t[k].w = t.w; K.t[k].d = t.decim; K.t[k].off = (long long)(t.grad_texture - A.grad);
+    }
+    K.void_raised = A.void_raised; K.void_flag = A.void_flag;
+    long long env = 0;
+    for (int k = 0; k < 2; ++k) {
+        K.skip_lo[k] = K.n; K.skip_len[k] = 0;
+        if (k < A.ntex) { K.skip_lo[k] = K.t[k].off; K.skip_len[k] = (long long)K.t[k].n * K.t[k].h * K.t[k].w * 3; env += K.skip_len[k]; }
+    }
+    if (K.skip_lo[1] < K.skip_lo[0]) {
+        std::swap(K.skip_lo[0], K.skip_lo[1]);
+        std::swap(K.skip_len[0], K.skip_len[1]);
+    }
+    unsigned grid = grid_for(K.n);
+    K.nenv = 0;
+    if (A.ntex) {
+        // the sets' share of the grid in proportion to their memory operations -- about 10 per element (texture, maps' and TV gradients in;
+        // the map cleared, the gradient out; then Adam's 3 + 3) against Adam's 7 -- at least one workgroup for each half
+        if (grid < 2) grid = 2;
+        const double we = 10.0 / 7.0 * (double)env;
+        const long long share = (long long)((double)grid * we / ((double)(K.n - env) + we) + 0.5);
+        K.nenv = (int)std::min<long long>(grid - 1, std::max<long long>(1, share));
+    }
+    hipLaunchKernelGGL(adam_groups_tex_kernel, dim3(grid), dim3(NT), 0, s, K);
+    return dbw_check_launch("adam_groups_tex_kernel");
+}
+
+// (tests: the step's last launch on the caller's buffers -- held against dbw_texture_prep_bwd_sets + dbw_adam_step_groups; not in the header)
+extern "C" int dbw_debug_adam_tail(float *param, float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *group_end, const float *lr,
+                                   int ngroups, float beta1, float beta2, float eps, int step, void *zero_buf, int64_t zero_bytes,
+                                   int64_t hole_begin, int64_t hole_end, const dbw_texture_set *sets, int nsets, const float *void_raised,
+                                   float *void_flag, dbw_stream_t stream) {
+    DBW_REQUIRE(nsets >= 0 && nsets <= 2 && (sets || nsets == 0), "0..2 texture sets");
+    AdamTailArgs A;
+    memset(&A, 0, sizeof(A));
+    A.param = param; A.grad = grad; A.exp_avg = exp_avg; A.exp_avg_sq = exp_avg_sq; A.group_end = group_end; A.lr = lr; A.ngroups = ngroups;
+    A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.step = step;
+    A.zero_buf = zero_buf; A.zero_bytes = zero_bytes; A.hole_begin = hole_begin; A.hole_end = hole_end;
+    for (int k = 0; k < nsets; ++k) A.tex[k] = sets[k];
+    A.ntex = nsets; A.void_raised = void_raised; A.void_flag = void_flag;
+    return launch_adam_tail(A, (hipStream_t)stream);
 }
 
 extern "C" int dbw_composite_mse(const float *fg, const float *env, const float *imgs, int N, int H, int W,

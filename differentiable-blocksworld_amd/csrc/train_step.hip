@@ -344,6 +344,7 @@ struct dbw_step_plan {
     unsigned sync_val[SYNC_FLAGS];      // last value stored behind each counter (host side)
     int voided_runs;                    // runs whose cross-stream wait gave up (seen at the next run): the plan then runs on events
     int force_timeout;                  // debug (dbw_debug_train_step_force_timeout): the next run's join polls for a value that never comes
+    bool last_tail;                     // the last run ended in the one-launch tail (launch_adam_tail)
 };
 
 extern "C" size_t dbw_train_step_workspace_bytes(const dbw_step_desc *desc) {
@@ -396,6 +397,7 @@ extern "C" dbw_step_plan *dbw_train_step_create(const dbw_step_desc *desc, void 
     for (hipEvent_t &e : p->ev_t)
         if (hipEventCreate(&e) != hipSuccess) { dbw_set_error("dbw_train_step_create: hipEventCreate failed"); dbw_train_step_destroy(p); return nullptr; }
     p->runs = 0; p->cur_flags = false; p->voided_runs = 0; p->force_timeout = 0; p->bin_turn = 0; p->bin_ready = 0; p->uniform_ready = 0; p->arena_clean = false; p->losses_pending = false;
+    p->last_tail = false;
     return p;
 }
 
@@ -536,6 +538,23 @@ extern "C" int dbw_train_step_run(dbw_step_plan *p, const dbw_step_inputs *in, d
     // ---- texture sets: sky, blocks, ground (dbw.py:273-293,306,331-334) ----
     dbw_texture_set sets[3];
     fill_texture_sets(d, L, ws, sets);
+
+    // The tail when Adam runs in the call (fuse bits 3 + 5) and the env backward ends after the uv backward -- many views on decimated maps,
+    // the headline: M waits for Rg itself behind the uv backward and runs the blocks' chain in front of its join with E (under the env
+    // backward's last ~80 us), E no longer waits for Rg; behind the join ONE launch (launch_adam_tail): the backward of the sky / ground
+    // texture preparation, Adam, the run's void latch -- behind the last poll of the run -- and the arena clear.  Where the uv backward ends
+    // last (few views: B <= serial_setup_max_views; the texture bins of the full-resolution maps) the parent order stays: a second poll on M
+    // would cost M a launch slot, and the sky / ground texture backward is free on E but not inside Adam (profiles/r08_experiments.md)
+    AdamTailArgs T;
+    memset(&T, 0, sizeof(T));
+    T.param = d.flat_param; T.grad = d.flat_grad; T.exp_avg = d.exp_avg; T.exp_avg_sq = d.exp_avg_sq; T.group_end = d.group_end; T.lr = in->lr;
+    T.ngroups = 2; T.beta1 = in->beta1; T.beta2 = in->beta2; T.eps = in->adam_eps; T.step = in->adam_step;
+    T.zero_buf = ws + L.arena_begin; T.zero_bytes = (int64_t)(L.arena_end - L.arena_begin);
+    T.hole_begin = (int64_t)(L.g_env_maps - L.arena_begin); T.hole_end = (int64_t)(L.g_maps_end - L.arena_begin);      // (the env maps' gradients)
+    T.tex[0] = sets[0]; T.tex[1] = sets[2]; T.ntex = 2;
+    T.void_raised = void_raised; T.void_flag = void_flag;
+    const bool adam_tail = in->with_adam && !defer && (d.fuse & 41) == 41 && two && in->B > d.serial_setup_max_views && !bins_on(d) &&
+                           adam_tail_fits(T);
 
     // ---- M: targets in the tile-planar layout (a fresh mini-batch; resident views come tiled) ----
     const float *target = in->imgs;
@@ -798,7 +817,7 @@ extern "C" int dbw_train_step_run(dbw_step_plan *p, const dbw_step_inputs *in, d
                                 IP(L.e.c2o), IP(L.e.code), FP(L.e.cw), FP(L.g_fvc_e), FP(L.g_env_verts), st));
         RC(dbw_posed_mesh_bwd(d.ground_base, d.n_ground_verts, d.R6_ground, d.T_ground, d.S_world, d.R_world, FP(L.g_env_verts) + (size_t)d.n_sky_verts * 3,
                               d.g_R6_ground, d.g_T_ground, st));
-        if (defer) return DBW_OK;
+        if (defer || adam_tail) return DBW_OK;         // (adam_tail: the sky / ground texture backward is M's, behind the join)
         // (Rg: the TV gradients of the sky / ground maps -- and, for M behind this chain: d / d alpha_full, the pose gradients of the overlap term)
         if (two) RC(await(st, F_REG, p->ev_reg));
         dbw_texture_set env_sets[2] = {sets[0], sets[2]};
@@ -838,6 +857,8 @@ extern "C" int dbw_train_step_run(dbw_step_plan *p, const dbw_step_inputs *in, d
         RC(signal(E, F_ENV_DONE, p->ev_env_done));
     }
     if (bins) RC(dbw_texbin_reduce(d.block_bin_info, cursor, ws + L.records, L.bin_cap, blayout, d.n_bins, FP(L.g_blk_maps), M));
+    // (adam_tail: the blocks' chain needs Rg -- the TV gradient of their maps, d / d alpha_full, the overlap pose gradients -- not E)
+    if (adam_tail) RC(await(M, F_REG, p->ev_reg));
     // the backward of the blocks' texture preparation, first in the tail: a data-parallel caller reduces the blocks' texture gradient -- 83 %
     // of the gradient bytes -- as soon as ev_blocks_ready says so, next to everything below.  It needs the TV gradient of the blocks' maps
     // (Rg): data parallel M waits for it here; on one GPU the launch moves behind the join with the env chain (which has waited for Rg), so
@@ -862,36 +883,48 @@ extern "C" int dbw_train_step_run(dbw_step_plan *p, const dbw_step_inputs *in, d
         RC(dbw_project_clip_bwd(FP(L.blk_verts), d.block_faces, in->R, in->T, d.Kmat, B, Vf, Ff, d.cam_eps, d.z_clip, d.perspective_correct, IP(L.f.num),
                                 IP(L.f.c2o), IP(L.f.code), FP(L.f.cw), FP(L.g_fvc_f), FP(L.g_blk_verts), M));
     if (!two) { RC(env_backward(M)); RC(loss_values(M)); }
-    if (two) RC(await(M, F_ENV_DONE, p->ev_env_done));           // the env chain, and through it the regularisers (E waited for Rg)
+    auto blocks_chain = [&]() -> int {
+        if (tail_merged) {
+            ClipBwdArgs C;
+            C.verts = FP(L.blk_verts); C.faces = d.block_faces; C.R = in->R; C.T = in->T; C.Kmat = d.Kmat; C.B = B; C.V = Vf; C.F = Ff;
+            C.eps = d.cam_eps; C.zc = d.z_clip; C.persp = d.perspective_correct;
+            C.num_faces = IP(L.f.num); C.c2o = IP(L.f.c2o); C.code = IP(L.f.code); C.cw = FP(L.f.cw); C.gfvc = FP(L.g_fvc_f); C.gverts = FP(L.g_blk_verts);
+            dbw_texture_set blk = sets[1];
+            if (!tv) blk.grad_sig = nullptr;
+            RC(launch_clip_bwd_tex(C, blk, M));
+        } else if (!early_textures) RC(blocks_textures());
+        if ((d.fuse & 8) && (d.fuse & 1)) {
+            BlocksTailArgs A;
+            memset(&A, 0, sizeof(A));
+            A.sq_eps = d.sq_eps; A.S = d.S; A.R6 = d.R6; A.T = d.T; A.sq_local = FP(L.sq_local); A.keep = IP(L.keep); A.nb = nb; A.nv = nv;
+            A.scale_min = d.scale_min; A.S_world = d.S_world; A.Rw = d.R_world; A.g_verts = FP(L.g_blk_verts);
+            A.g_sq_eps = d.g_sq_eps; A.g_S = d.g_S; A.g_R6 = d.g_R6; A.g_T = d.g_T;
+            A.alpha = FP(L.alpha); A.g_alpha_parts = coarse ? FP(L.g_fa) : nullptr; A.alpha_parts = 64; A.g_alpha_full = FP(L.g_alpha_full); A.g_logit = d.g_alpha_logit;
+            if (!adam_tail) { A.void_raised = void_raised; A.void_flag = void_flag; }     // (the run's latch: behind the join, in front of Adam)
+            RC(launch_blocks_tail(A, M));
+        } else {
+            RC(dbw_sq_blocks_bwd(d.sq_eps, d.S, d.R6, d.T, d.trig, IP(L.keep), 0, nb, nv, d.ratio_block_scene, d.scale_min, d.S_world, d.R_world, FP(L.g_blk_verts),
+                                 d.g_sq_eps, d.g_S, d.g_R6, d.g_T, M));
+            RC(dbw_block_alpha_bwd(FP(L.alpha), IP(L.keep), coarse ? FP(L.g_fa) : nullptr, 64, FP(L.g_alpha_full), nb, d.g_alpha_logit, M));
+            hipLaunchKernelGGL(void_latch_kernel, dim3(1), dim3(1), 0, M, (const float *)void_raised, void_flag);
+            RC(dbw_check_launch("void_latch_kernel"));
+        }
+        return DBW_OK;
+    };
+    if (adam_tail) RC(blocks_chain());                            // (under the env backward)
+    if (two) RC(await(M, F_ENV_DONE, p->ev_env_done));           // the env chain, and through it (unless adam_tail) the regularisers: E waited for Rg
     if (two && defer) RC(await(M, F_REG, p->ev_reg));            // (... which it did not when the texture tail is deferred)
-    if (tail_merged) {
-        ClipBwdArgs C;
-        C.verts = FP(L.blk_verts); C.faces = d.block_faces; C.R = in->R; C.T = in->T; C.Kmat = d.Kmat; C.B = B; C.V = Vf; C.F = Ff;
-        C.eps = d.cam_eps; C.zc = d.z_clip; C.persp = d.perspective_correct;
-        C.num_faces = IP(L.f.num); C.c2o = IP(L.f.c2o); C.code = IP(L.f.code); C.cw = FP(L.f.cw); C.gfvc = FP(L.g_fvc_f); C.gverts = FP(L.g_blk_verts);
-        dbw_texture_set blk = sets[1];
-        if (!tv) blk.grad_sig = nullptr;
-        RC(launch_clip_bwd_tex(C, blk, M));
-    } else if (!early_textures) RC(blocks_textures());
-    if ((d.fuse & 8) && (d.fuse & 1)) {
-        BlocksTailArgs A;
-        memset(&A, 0, sizeof(A));
-        A.sq_eps = d.sq_eps; A.S = d.S; A.R6 = d.R6; A.T = d.T; A.sq_local = FP(L.sq_local); A.keep = IP(L.keep); A.nb = nb; A.nv = nv;
-        A.scale_min = d.scale_min; A.S_world = d.S_world; A.Rw = d.R_world; A.g_verts = FP(L.g_blk_verts);
-        A.g_sq_eps = d.g_sq_eps; A.g_S = d.g_S; A.g_R6 = d.g_R6; A.g_T = d.g_T;
-        A.alpha = FP(L.alpha); A.g_alpha_parts = coarse ? FP(L.g_fa) : nullptr; A.alpha_parts = 64; A.g_alpha_full = FP(L.g_alpha_full); A.g_logit = d.g_alpha_logit;
-        A.void_raised = void_raised; A.void_flag = void_flag;          // (the run's latch: behind the join, in front of Adam)
-        RC(launch_blocks_tail(A, M));
-    } else {
-        RC(dbw_sq_blocks_bwd(d.sq_eps, d.S, d.R6, d.T, d.trig, IP(L.keep), 0, nb, nv, d.ratio_block_scene, d.scale_min, d.S_world, d.R_world, FP(L.g_blk_verts),
-                             d.g_sq_eps, d.g_S, d.g_R6, d.g_T, M));
-        RC(dbw_block_alpha_bwd(FP(L.alpha), IP(L.keep), coarse ? FP(L.g_fa) : nullptr, 64, FP(L.g_alpha_full), nb, d.g_alpha_logit, M));
-        hipLaunchKernelGGL(void_latch_kernel, dim3(1), dim3(1), 0, M, (const float *)void_raised, void_flag);
-        RC(dbw_check_launch("void_latch_kernel"));
-    }
+    if (!adam_tail) RC(blocks_chain());
 
     // ---- M: Adam on both learning-rate groups, which also clears the zero arena for the next run ----
-    if (in->with_adam) {
+    if (adam_tail) {
+        T.tex[0] = sets[0]; T.tex[1] = sets[2];
+        if (!tv) { T.tex[0].grad_sig = nullptr; T.tex[1].grad_sig = nullptr; }
+        RC(launch_adam_tail(T, M));
+        p->arena_clean = true;
+        p->last_tail = true;
+    } else if (in->with_adam) {
+        p->last_tail = false;
         RC(dbw_adam_step_groups(d.flat_param, d.flat_grad, d.exp_avg, d.exp_avg_sq, d.group_end, in->lr, 2, in->beta1, in->beta2, in->adam_eps, in->adam_step,
                                 ws + L.arena_begin, (int64_t)(L.arena_end - L.arena_begin), void_flag, M));
         p->arena_clean = true;
@@ -970,6 +1003,9 @@ extern "C" int dbw_debug_train_step_counters(dbw_step_plan *p, unsigned *seen12,
     return DBW_OK;
 }
 extern "C" int dbw_train_step_voided_runs(const dbw_step_plan *p) { return p ? p->voided_runs + (*(volatile unsigned *)p->host_timeouts != 0u ? 1 : 0) : -1; }
+
+// (tests: 1 if the last run with Adam in the call ended in the one-launch tail, 0 if in the texture backward + Adam launches; not in the header)
+extern "C" int dbw_debug_train_step_last_tail(const dbw_step_plan *p) { return p ? (p->last_tail ? 1 : 0) : -1; }
 
 extern "C" int64_t dbw_train_step_void_flag_offset(const dbw_step_plan *p) { return p ? (int64_t)p->L.losses + 7 * (int64_t)sizeof(float) : -1; }
 
