@@ -152,6 +152,27 @@ def _header_eval_abi_version():
 
 EVAL_ABI_VERSION = _header_eval_abi_version()
 
+# the lit visualisation renders: name -> argtypes, exactly the int-returning prototypes of include/dbw_viz.h (checked by
+# tests/test_viz_host.py); the one size_t-returning entry point next to them, like dbw_rasterize_workspace_bytes next to SIGNATURES
+VIZ_SIGNATURES = {
+    'dbw_vertex_normals': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p],
+    'dbw_render_lit_fwd': [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i,
+                           c_i, c_i, c_f, c_f, c_i, c_p, c_i, c_p, c_p, c_sz, c_p],
+}
+VIZ_OTHER_SIGNATURES = {
+    'dbw_render_lit_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i, c_i]),
+}
+
+
+def _header_viz_abi_version():
+    """DBW_VIZ_ABI_VERSION of include/dbw_viz.h (dbw_viz_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_viz.h')) as f:
+        return int(re.search(r'#define DBW_VIZ_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+VIZ_ABI_VERSION = _header_viz_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -200,6 +221,15 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = c_i
+    if hasattr(lib, 'dbw_viz_abi_version'):     # (absent from tuning builds of older sources: ops.render_scene_lit refuses to run on them)
+        lib.dbw_viz_abi_version.restype = c_i
+        for name, argtypes in VIZ_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
+        for name, (restype, argtypes) in VIZ_OTHER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import mesh as M
 from . import ops
-from .renderer import Renderer
+from .renderer import DIRECTION_LIGHT, Renderer
 from .structures import PackedScene
 
 DECIMATE_FACTOR = 8            # dbw.py:32
@@ -177,8 +177,11 @@ class DifferentiableBlocksWorld(nn.Module):
         self.register_buffer('_block_map_desc_dec', PackedScene.describe_maps([(TS, TS)] * N, [self.txt_padding] * N, dev, shift)[0],
                              persistent=False)
 
-    def _init_renderer(self, img_size, **kwargs):  # dbw.py:131-143 (renderer_light is visualisation-only: not built)
+    def _init_renderer(self, img_size, **kwargs):  # dbw.py:131-143
         kwargs = deepcopy(kwargs)
+        if kwargs.get('shading_type', 'raw') != 'raw' or kwargs.get('lights', {}).get('name', 'ambient') != 'ambient':
+            raise NotImplementedError("the model's training renderers need a backward pass: shading_type='raw' under ambient light only (flat / "
+                                      'Phong shading under a directional light is forward only: renderer_light)')
         self.renderer = Renderer(img_size, **kwargs)
         kwargs['sigma'] = 5e-6
         self.renderer_fine = Renderer(img_size, **kwargs)
@@ -186,6 +189,12 @@ class DifferentiableBlocksWorld(nn.Module):
         kwargs['sigma'] = 0
         kwargs['detach_bary'] = False
         self.renderer_env = Renderer(img_size, **kwargs)
+        # what a user looks at (predict_synthetic, dbw.py:245): flat shading under a directional light fixed to the camera, white background
+        kwargs['lights'] = {'name': 'directional', 'direction': [DIRECTION_LIGHT], 'ambient_color': [[0.7, 0.7, 0.7]],
+                            'diffuse_color': [[0.4, 0.4, 0.4]], 'specular_color': [[0., 0., 0.]]}
+        kwargs['shading_type'] = 'flat'
+        kwargs['background_color'] = (1, 1, 1)
+        self.renderer_light = Renderer(img_size, **kwargs)
 
     def _init_loss(self, **kwargs):                # dbw.py:145-163
         weights = {'rgb': kwargs.pop('rgb_weight', 1.0), 'perceptual': kwargs.pop('perceptual_weight', 0),
@@ -222,7 +231,7 @@ class DifferentiableBlocksWorld(nn.Module):
 
     def to(self, device):
         super().to(device)
-        for r in (self.renderer, self.renderer_fine, self.renderer_env):
+        for r in (self.renderer, self.renderer_fine, self.renderer_env, self.renderer_light):
             r.to(device)
         return self
 
@@ -381,7 +390,7 @@ class DifferentiableBlocksWorld(nn.Module):
     # ------------------------------------------------------------------------------------------------ rendering
     def _ensure_cameras(self, inp):
         if 'K' in inp and self.renderer.cameras.K is None:          # intrinsics frozen from the first sample (dbw.py:204-208)
-            for r in (self.renderer, self.renderer_fine, self.renderer_env):
+            for r in (self.renderer, self.renderer_fine, self.renderer_env, self.renderer_light):
                 r.update_cameras(device=inp['imgs'].device, K=inp['K'][0:1])
 
     def render_joined(self, inp, filter_transparent=False):
@@ -472,10 +481,13 @@ class DifferentiableBlocksWorld(nn.Module):
         return rec
 
     @torch.no_grad()
-    def predict_synthetic(self, inp, labels=None):
-        """Blocks alone in their synthetic colours (dbw.py:240-248), exact 4x anti-aliased hard render.  The reference shades them
-        with a directional light (`renderer_light`: phong shading, visualisation-only); here the colours are flat."""
+    def predict_synthetic(self, inp, labels=None, lit=False):
+        """Blocks alone in their synthetic colours (dbw.py:240-248), exact 4x anti-aliased hard render on a white background.  lit=True is
+        the reference's picture: flat shading under `renderer_light`'s directional light, which gives the blocks their visible shape
+        (values reach ambient + diffuse = 1.1: the reference clamps when it saves).  lit=False: every block in its one unshaded colour."""
         self._ensure_cameras(inp)
+        if self.renderer_light.cameras.K is None and self.renderer.cameras.K is not None:      # (intrinsics set on the other renderers directly)
+            self.renderer_light.update_cameras(device=inp['imgs'].device, K=self.renderer.cameras.K)
         was_training = self.training
         self.eval()
         with self._host_packed_rebuild():                  # host-packed: `colors` / `desc` below hold the kept blocks only
@@ -488,6 +500,8 @@ class DifferentiableBlocksWorld(nn.Module):
         colors = torch.from_numpy(M.get_fancy_cmap()(values.numpy())).float().to(blocks.verts.device)
         desc = PackedScene.describe_maps([(1, 1)] * len(colors), [(0, 0)] * len(colors), blocks.verts.device)[0]
         flat = PackedScene(blocks.verts, blocks.faces, blocks.face_uvs, blocks.face_map, desc, colors.reshape(-1).contiguous())
+        if lit:
+            return self.renderer_light.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]
         bg_renderer = Renderer(self.img_size, **{**self.renderer.init_kwargs, 'background_color': (1, 1, 1)})
         bg_renderer.update_cameras(device=blocks.verts.device, K=self.renderer.cameras.K)
         return bg_renderer.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]

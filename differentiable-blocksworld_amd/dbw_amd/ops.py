@@ -626,6 +626,83 @@ def render_fragments(verts, faces_i32, R, T, Kmat, cfg):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# lit visualisation renders (include/dbw_viz.h): directional light, flat / Phong shading, forward only
+# ---------------------------------------------------------------------------------------------------------------------
+def vertex_adjacency(faces_i32, V):
+    """CSR vertex -> (face, corner) adjacency of dbw_vertex_normals: (adj_start (V+1,) int32, adj (3F,) int32 entries face * 4 + corner), a
+    vertex's entries in ascending (face, corner) order.  Integer plumbing, built once per topology."""
+    flat = faces_i32.reshape(-1).long()
+    order = torch.argsort(flat, stable=True)              # entry e = face * 3 + corner
+    adj = (torch.div(order, 3, rounding_mode='floor') * 4 + order % 3).to(torch.int32).contiguous()
+    start = torch.zeros(V + 1, dtype=torch.int64, device=faces_i32.device)
+    start[1:] = torch.cumsum(torch.bincount(flat, minlength=V)[:V], 0)
+    return start.to(torch.int32).contiguous(), adj
+
+
+def _viz_lib():
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_viz_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no lit render entry points (include/dbw_viz.h): rebuild it')
+    return lib
+
+
+def vertex_normals(verts, faces_i32, adjacency=None):
+    """(V,3) area-weighted unit vertex normals (PyTorch3D's verts_normals_packed) of a packed scene; no grad."""
+    _viz_lib()
+    verts_c = _chk(verts.detach(), torch.float32, 'verts')
+    faces_c = _chk(faces_i32, torch.int32, 'faces')
+    V, F_ = verts_c.shape[0], faces_c.shape[0]
+    start, adj = adjacency if adjacency is not None else vertex_adjacency(faces_c, V)
+    out = torch.empty(V, 3, dtype=torch.float32, device=verts_c.device)
+    _lib.call('dbw_vertex_normals', _ptr(verts_c), _ptr(faces_c), _ptr(start), _ptr(adj), V, F_, _ptr(out), _stream(verts_c))
+    return out
+
+
+def light_dir_world(direction, R):
+    """The light is fixed to the camera (renderer.py:87-89): direction (1 | B, 3) @ R[b]^T -> (B,3), element-wise so that a view's
+    direction does not depend on the batch it is rendered in."""
+    d = direction.to(device=R.device, dtype=torch.float32).reshape(-1, 3)
+    return (d[:, 0:1] * R[:, :, 0] + d[:, 1:2] * R[:, :, 1] + d[:, 2:3] * R[:, :, 2]).contiguous()
+
+
+def render_scene_lit(verts, maps, faces_alpha, faces_i32, R, T, Kmat, face_uvs, face_map, map_desc, bg, cfg, direction, ambient, diffuse,
+                     phong=False, ssaa=1, adjacency=None):
+    """The lit render pass (include/dbw_viz.h: dbw_render_lit_fwd): colour = (ambient + diffuse * relu(n . d)) * texel, layered blend,
+    with ssaa == 4 rendered at 4x cfg.H x cfg.W and box-filtered in the kernel.  -> image (B,4,cfg.H,cfg.W).  direction (1 | B, 3): towards
+    the light, camera space; ambient / diffuse: three floats each.  Forward only: there is no autograd node."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (verts, maps, faces_alpha)):
+        raise NotImplementedError('render_scene_lit is forward only (the reference calls its lit renderers under no_grad): a differentiable '
+                                  'lit pass does not exist; call it under torch.no_grad() or detach the inputs')
+    if cfg.K > MAX_FACES_PER_PIXEL:
+        raise ValueError(f'faces_per_pixel={cfg.K} > {MAX_FACES_PER_PIXEL}')
+    if ssaa not in (1, 4):
+        raise ValueError(f'ssaa must be 1 or 4, got {ssaa}')
+    if ssaa == 4 and cfg.K != 1:
+        raise NotImplementedError('ssaa=4 resolves its 4x4 blocks inside the single-layer kernel: faces_per_pixel must be 1')
+    lib = _viz_lib()
+    verts_c = _chk(verts.detach(), torch.float32, 'verts')
+    maps_c = _chk(maps.detach(), torch.float32, 'maps')
+    fa = None if faces_alpha is None else _chk(faces_alpha.detach(), torch.float32, 'faces_alpha')
+    dev = verts_c.device
+    B = R.shape[0]
+    normals = vertex_normals(verts_c, faces_i32, adjacency) if phong else None
+    ldir = light_dir_world(direction, R)
+    cl = project_clip(verts_c, faces_i32, R, T, Kmat, cfg.eps, cfg.z_clip, cfg.persp)
+    fvc = cl['face_verts'].view(-1, 3, 3)
+    Ft = fvc.shape[0]
+    ws_bytes = lib.dbw_render_lit_workspace_bytes(Ft, B, cfg.F, cfg.H, cfg.W, ssaa)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+    img = torch.empty(B, 4, cfg.H, cfg.W, dtype=torch.float32, device=dev)
+    ka, kd = make_bg(ambient), make_bg(diffuse)
+    _lib.call('dbw_render_lit_fwd', _ptr(fvc), _ptr(cl['first_idx']), _ptr(cl['num_faces']), _ptr(cl['neighbor']), _ptr(cl['c2o']),
+              _ptr(cl['clip_code']), _ptr(cl['clip_w']), 2 * cfg.F, _ptr(face_uvs), _ptr(face_map), _ptr(map_desc), _ptr(maps_c), _ptr(fa),
+              _alpha_len(fa, map_desc, cfg.F), _ptr(verts_c), _ptr(faces_i32), _ptr(normals), _ptr(ldir), _bg_ptr(ka), _bg_ptr(kd), B, Ft,
+              cfg.H, cfg.W, cfg.K, cfg.F, float(cfg.sigma), float(cfg.blur), int(cfg.persp), _bg_ptr(bg), int(ssaa), _ptr(img), _ptr(ws),
+              ws_bytes, _stream(verts_c))
+    return img
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # texture preparation, param -> mesh, losses, optimiser
 # ---------------------------------------------------------------------------------------------------------------------
 class _TexturePrep(torch.autograd.Function):

@@ -3,8 +3,11 @@ src/model/renderer.py:24-60,84-98 (`Renderer(img_size, **cfg.model.renderer)`; `
 viz_purpose=False, faces_alpha=...) -> (B,4,H,W)` BCHW, premultiplied RGB + alpha), with everything below it
 (PyTorch3D MeshRenderer / MeshRasterizer / TexturesUV sampling / LayeredShader + layered_rgb_blend) replaced by the
 HIP path in libdbw_hip.so.  Only the configuration the hot path uses is implemented:
-perspective cameras with an explicit NDC K matrix, ambient white light, the 'raw' layered shader (clip_inside True or False).
+perspective cameras with an explicit NDC K matrix, ambient white light, the 'raw' layered shader (clip_inside True or False) -- and,
+for the pictures a user looks at (the reference's `renderer_light`, dbw.py:139-143, and the eye_light variants of render_views /
+render_rotated_views), a directional light with 'flat' or 'phong' shading through the forward-only lit kernel (include/dbw_viz.h).
 Anything else raises NotImplementedError instead of silently rendering something different."""
+import math
 from copy import deepcopy
 
 import torch
@@ -15,6 +18,7 @@ from . import ops
 from .structures import Meshes, PackedScene
 
 EPS = 1e-8          # renderer.py:20
+DIRECTION_LIGHT = [1, 0.25, -1]          # renderer.py:21
 
 
 class PerspectiveCameras:
@@ -32,8 +36,47 @@ class PerspectiveCameras:
         return self
 
 
+def _color3(v, name):
+    """One RGB triple as a (1,3) fp32 CPU tensor (the reference writes its lights as [[r, g, b]])."""
+    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1, 3)
+    if t.shape[0] != 1:
+        raise NotImplementedError(f'{name}: one value shared by the views, got {tuple(t.shape)}')
+    return t.clone()
+
+
 class AmbientLights:
-    ambient_color = ((1.0, 1.0, 1.0),)
+    """PyTorch3D's AmbientLights: ambient_color (default white), no diffuse, no specular term."""
+
+    def __init__(self, ambient_color=((1.0, 1.0, 1.0),)):
+        self.ambient_color = _color3(ambient_color, 'ambient_color')
+        self.diffuse_color = torch.zeros(1, 3)
+        self.specular_color = torch.zeros(1, 3)
+        self.direction = torch.tensor([[0., 1., 0.]])
+
+    def to(self, device):
+        return self
+
+
+SPECULAR_REASON = ('a non-zero specular_color is not rendered: PyTorch3D takes the camera centre of the specular term from a cameras object '
+                   'that does not carry the view\'s R, T, which cannot be verified without the library; every light the reference builds has '
+                   'specular_color 0 (note that PyTorch3D\'s own default is 0.2: pass specular_color=[[0, 0, 0]] explicitly)')
+
+
+class DirectionalLights:
+    """PyTorch3D's DirectionalLights (defaults: direction (0, 1, 0), ambient 0.5, diffuse 0.3, specular 0.2), host-side values: the
+    direction points FROM the surface TO the light, in camera space (Renderer fixes the light to the camera, renderer.py:87-89).  The
+    `_direction` ... copies are the constructor's values (renderer.py:74-78: reset_default_lights)."""
+
+    def __init__(self, direction=((0, 1, 0),), ambient_color=((0.5, 0.5, 0.5),), diffuse_color=((0.3, 0.3, 0.3),),
+                 specular_color=((0.2, 0.2, 0.2),)):
+        self.direction = torch.as_tensor(direction, dtype=torch.float32).reshape(-1, 3).clone()
+        self.ambient_color = _color3(ambient_color, 'ambient_color')
+        self.diffuse_color = _color3(diffuse_color, 'diffuse_color')
+        self.specular_color = _color3(specular_color, 'specular_color')
+        if bool((self.specular_color != 0).any()):
+            raise NotImplementedError(SPECULAR_REASON)
+        self._direction, self._ambient_color = self.direction, self.ambient_color
+        self._diffuse_color, self._specular_color = self.diffuse_color, self.specular_color
 
     def to(self, device):
         return self
@@ -55,8 +98,14 @@ class Renderer(nn.Module):
         if not kwargs.pop('layered_shader', True):
             raise NotImplementedError('only the layered shader is on the hot path (renderer.py:39-43)')
         self.clip_inside = bool(kwargs.pop('clip_inside', True))          # False: sigmoid(-d / sigma) instead of exp(-max(d, 0) / sigma), renderer.py:257-258
-        if kwargs.pop('shading_type', 'raw') != 'raw':
-            raise NotImplementedError("only shading_type='raw' (phong/flat/gouraud are visualisation-only)")
+        self.shading_type = kwargs.pop('shading_type', 'raw')
+        if self.shading_type == 'gouraud':
+            raise NotImplementedError("shading_type='gouraud' needs per-vertex textures, which the UV-textured scenes of this path do not have")
+        if self.shading_type not in ('raw', 'flat', 'phong'):
+            raise NotImplementedError(f"shading_type='{self.shading_type}': one of 'raw', 'flat', 'phong'")
+        if self.shading_type == 'raw' and isinstance(self.lights, DirectionalLights):
+            raise NotImplementedError("shading_type='raw' ignores the light: a directional light needs 'flat' or 'phong' (nothing in the "
+                                      'reference combines the two)')
         self.detach_bary = kwargs.pop('detach_bary', False)
         assert len(kwargs) == 0, kwargs
         # perspective_correct=None is inferred True for perspective cameras
@@ -72,9 +121,37 @@ class Renderer(nn.Module):
 
     def init_lights(self, **kwargs):
         kwargs = deepcopy(kwargs)
-        if kwargs.pop('name', 'ambient') != 'ambient':
-            raise NotImplementedError('only ambient lights are on the hot path (directional = visualisation)')
-        self.lights = AmbientLights()
+        name = kwargs.pop('name', 'ambient')
+        if name == 'point':
+            raise NotImplementedError("lights 'point' are not implemented (nothing in the reference builds one): 'ambient' or 'directional'")
+        if name not in ('ambient', 'directional'):
+            raise KeyError(name)
+        self.lights = {'ambient': AmbientLights, 'directional': DirectionalLights}[name](**kwargs)
+
+    # -- renderer.py:118-132
+    def update_lights(self, direction=None, ka=None, kd=None, ks=None):
+        if direction is not None:
+            self.lights.direction = torch.as_tensor(direction, dtype=torch.float32).reshape(-1, 3).clone()
+        if ka is not None:
+            self.lights.ambient_color = _color3(ka, 'ka')
+        if kd is not None:
+            self.lights.diffuse_color = _color3(kd, 'kd')
+        if ks is not None:
+            ks = _color3(ks, 'ks')
+            if bool((ks != 0).any()):
+                raise NotImplementedError(SPECULAR_REASON)
+            self.lights.specular_color = ks
+
+    def reset_default_lights(self):
+        self.lights.direction = self.lights._direction
+        self.lights.ambient_color = self.lights._ambient_color
+        self.lights.diffuse_color = self.lights._diffuse_color
+        self.lights.specular_color = self.lights._specular_color
+
+    @property
+    def lit(self):
+        """True: render_packed / forward go through the forward-only lit kernel (flat / Phong shading)."""
+        return self.shading_type != 'raw'
 
     @property
     def init_kwargs(self):
@@ -114,6 +191,8 @@ class Renderer(nn.Module):
                                       'update_cameras(K=...) first (dbw.py:204-208)')
         Kmat = self.cameras.K[0].to(R.device).contiguous()
         R, T = R.float().contiguous(), T.float().contiguous()
+        if self.lit:
+            return self._render_lit(scene, R, T, Kmat, faces_alpha, viz_purpose)
         cfg = self._cfg(scene.faces.shape[0], viz_purpose, lds_aggregate, getattr(scene, 'texbins', None), getattr(scene, 'const_faces', 0))
         if viz_purpose:
             with torch.no_grad():
@@ -122,6 +201,33 @@ class Renderer(nn.Module):
                 return F.avg_pool2d(img, kernel_size=4, stride=4)
         return ops.render_scene(scene.verts, scene.maps, faces_alpha, scene.faces, R, T, Kmat, scene.face_uvs, scene.face_map,
                                 scene.map_desc, self._bg, cfg)
+
+    def _render_lit(self, scene, R, T, Kmat, faces_alpha, viz_purpose):
+        """Flat / Phong shading under this renderer's light, which follows the camera (renderer.py:87-89; `self.lights` itself is not
+        touched).  viz_purpose: hard, one face per pixel, 4x4 super-samples resolved inside the kernel; else this renderer's own
+        faces_per_pixel and sigma at the image size.  Forward only."""
+        H, W = self.img_size
+        n_faces = scene.faces.shape[0]
+        if viz_purpose:
+            cfg, ssaa, faces_alpha = ops.RenderCfg(H, W, 1, 0.0, self.z_clip, self.perspective_correct, False, n_faces, EPS), 4, None
+        else:
+            cfg, ssaa = ops.RenderCfg(H, W, self.faces_per_pixel, self.sigma, self.z_clip, self.perspective_correct, self.detach_bary, n_faces,
+                                      EPS, clip_inside=self.clip_inside), 1
+        li = self.lights
+        if li.direction.shape[0] not in (1, R.shape[0]):
+            raise ValueError(f'{li.direction.shape[0]} light directions for {R.shape[0]} views')
+        adjacency = None
+        if self.shading_type == 'phong':          # the vertex -> (face, corner) table: once per topology
+            adjacency = getattr(scene, '_lit_adjacency', None)
+            if adjacency is None:
+                adjacency = ops.vertex_adjacency(scene.faces, scene.verts.shape[0])
+                try:
+                    scene._lit_adjacency = adjacency
+                except AttributeError:
+                    pass
+        return ops.render_scene_lit(scene.verts, scene.maps, faces_alpha, scene.faces, R, T, Kmat, scene.face_uvs, scene.face_map,
+                                    scene.map_desc, self._bg, cfg, li.direction, li.ambient_color.reshape(3).tolist(),
+                                    li.diffuse_color.reshape(3).tolist(), phong=self.shading_type == 'phong', ssaa=ssaa, adjacency=adjacency)
 
     # -- renderer.py:134-175: wireframe overlays (visualisation, SURVEY.md 8f N4) on the same rasteriser kernels
     def _as_scene(self, meshes):
@@ -182,3 +288,111 @@ class Renderer(nn.Module):
         else:
             scene = meshes
         return self.render_packed(scene, R, T, faces_alpha, viz_purpose)
+
+
+# -- renderer.py:290-380,411-414: view trajectories (tensors in, tensors out; writing videos / GIFs is left to the caller) --------------------
+def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, device='cpu'):
+    """PyTorch3D's look_at_view_transform for cameras that look at the origin with +Y up: dist, elev, azim (degrees; scalars or (N,)
+    tensors, broadcast) -> R (N,3,3), T (N,3).  Camera centre C = dist * (cos e sin a, sin e, cos e cos a); R's columns are the camera
+    axes (z = towards the origin, x = up x z, y = z x x, each normalised), T = -C @ R."""
+    dist, elev, azim = torch.broadcast_tensors(*[torch.as_tensor(v, dtype=torch.float32, device=device).reshape(-1) for v in (dist, elev, azim)])
+    e, a = elev * (math.pi / 180.0), azim * (math.pi / 180.0)
+    C = torch.stack([dist * torch.cos(e) * torch.sin(a), dist * torch.sin(e), dist * torch.cos(e) * torch.cos(a)], dim=-1)
+    up = torch.tensor([0., 1., 0.], device=C.device).expand_as(C)
+    z = F.normalize(-C, dim=-1, eps=1e-5)
+    x = F.normalize(torch.cross(up, z, dim=-1), dim=-1, eps=1e-5)
+    y = F.normalize(torch.cross(z, x, dim=-1), dim=-1, eps=1e-5)
+    degenerate = (x.abs() < 5e-3).all(dim=-1, keepdim=True)          # looking along the up axis: x from y and z instead
+    x = torch.where(degenerate, F.normalize(torch.cross(y, z, dim=-1), dim=-1, eps=1e-5), x)
+    R = torch.stack([x, y, z], dim=-1)
+    T = -(C[:, None] @ R)[:, 0]
+    return R, T
+
+
+def get_circle_traj(dist=1, a_scale=15, e_scale=15, N_views=50):
+    azim = torch.cos(torch.linspace(0, 2, N_views + 1) * math.pi)[:-1] * a_scale - 180
+    elev = torch.sin(torch.linspace(0, 2, N_views + 1) * math.pi)[:-1] * e_scale
+    return look_at_view_transform(dist, azim=azim, elev=elev)
+
+
+def _eye_light_renderer(renderer, direction, ambient):
+    """eye_light of render_views / render_rotated_views (renderer.py:301-310,343-351): an ambient renderer is swapped for a Phong one,
+    one face per pixel, under a directional light; a renderer that has a directional light already is kept."""
+    if not isinstance(renderer.lights, AmbientLights):
+        return renderer
+    kwargs = renderer.init_kwargs
+    kwargs['lights'] = {'name': 'directional', 'direction': [direction], 'ambient_color': [[ambient] * 3], 'diffuse_color': [[0.4, 0.4, 0.4]],
+                        'specular_color': [[0., 0., 0.]]}
+    kwargs['shading_type'] = 'phong'
+    kwargs['faces_per_pixel'] = 1
+    out = Renderer(renderer.img_size, **kwargs)
+    out.cameras = renderer.cameras
+    return out
+
+
+def _need_renderer(renderer):
+    if renderer is None:
+        raise NotImplementedError('renderer=None (the reference then builds FoV cameras): the HIP path needs perspective cameras with an '
+                                  'explicit NDC K, pass a Renderer whose update_cameras(K=...) was called')
+
+
+def _composite_bkg(views, bkg, img_size):
+    rec, alpha = torch.cat(views, dim=0).split([3, 1], dim=1)
+    if bkg is not None:
+        bkg = bkg.cpu()
+        if tuple(bkg.shape[-2:]) != tuple(img_size):
+            bkg = F.interpolate(bkg[None], size=tuple(img_size), mode='bilinear', align_corners=False)[0]
+        rec = rec * alpha + (1 - alpha) * bkg
+    return rec
+
+
+@torch.no_grad()
+def render_views(mesh, R, T, renderer=None, bkg=None, with_edges=False, linewidth=1, edge_colors=None, eye_light=False, with_alpha=False):
+    """The views (R[i], T[i]) of `mesh` (Meshes or PackedScene), exact 4x anti-aliased renders in batches of 10 (renderer.py:333-380) ->
+    (N,3,H,W) on the CPU, composited over `bkg` (3,H,W) where given, or (N,4,H,W) with_alpha.  with_edges: the wireframe painted on every
+    view (edge_colors: one RGB triple or one row per face of the scene)."""
+    _need_renderer(renderer)
+    if eye_light:
+        renderer = _eye_light_renderer(renderer, DIRECTION_LIGHT, 0.7)
+    scene = renderer._as_scene(mesh)
+    n_views = len(R)
+    views, B = [], 10
+    for k in range((n_views - 1) // B + 1):
+        R_view, T_view = R[k * B: (k + 1) * B], T[k * B: (k + 1) * B]
+        B_eff = len(R_view)
+        res = renderer(scene, R_view, T_view, viz_purpose=True)
+        if with_edges:
+            res, alpha = res.split([3, 1], dim=1)
+            colors = edge_colors
+            if isinstance(colors, torch.Tensor) and colors.dim() == 2:
+                colors = colors.to(res.device).repeat(B_eff, 1)
+            res = renderer.draw_edges(res, scene, R=R_view, T=T_view, linewidth=linewidth, colors=colors)
+            res = torch.cat([res, alpha], dim=1)
+        views.append(res.cpu())
+    if with_alpha:
+        return torch.cat(views, dim=0)
+    return _composite_bkg(views, bkg, renderer.img_size)
+
+
+@torch.no_grad()
+def render_rotated_views(mesh, renderer=None, n_views=50, elev=30, dist=2.5, R=None, T=None, bkg=None, eye_light=False):
+    """`mesh` seen from n_views azimuths around it (renderer.py:290-330): look_at cameras at unit distance composed with (R, T) where
+    given (elev / dist then count for nothing), else elevated by `elev` and pushed back by `dist` -> (n_views,3,H,W) on the CPU, clamped
+    to [0, 1]."""
+    _need_renderer(renderer)
+    if eye_light:
+        if R is not None:
+            raise NotImplementedError
+        renderer = _eye_light_renderer(renderer, [0, 0, -1], 0.6)
+    scene = renderer._as_scene(mesh)
+    dev = scene.verts.device
+    elev, dist = 0 if R is not None else elev, 0 if T is not None else dist
+    R = torch.eye(3, device=dev) if R is None else R.to(dev)
+    T = torch.zeros(3, device=dev) if T is None else T.to(dev)
+    azim = torch.linspace(-180, 180, n_views)
+    views, B = [], 10
+    for k in range((n_views - 1) // B + 1):
+        R_view = look_at_view_transform(dist=1, elev=elev, azim=azim[k * B: (k + 1) * B], device=dev)[0]
+        T_view = torch.tensor([[0., 0., float(dist)]], device=dev).expand(len(R_view), -1)
+        views.append(renderer(scene, (R_view @ R).contiguous(), (T_view + T).contiguous(), viz_purpose=True).clamp(0, 1).cpu())
+    return _composite_bkg(views, bkg, renderer.img_size)
