@@ -173,6 +173,23 @@ def _header_viz_abi_version():
 
 VIZ_ABI_VERSION = _header_viz_abi_version()
 
+# the 8-bit frame export: name -> argtypes, exactly the int-returning prototypes of include/dbw_export.h (checked by
+# tests/test_export_host.py).  A table of its own, like the two above.
+EXPORT_SIGNATURES = {
+    'dbw_frames_u8': [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+}
+FRAME_HWC, FRAME_EDGE_FIRST, FRAME_CLAMP_INPUT = 1, 2, 4      # DBW_FRAME_* of include/dbw_export.h
+
+
+def _header_export_abi_version():
+    """DBW_EXPORT_ABI_VERSION of include/dbw_export.h (dbw_export_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_export.h')) as f:
+        return int(re.search(r'#define DBW_EXPORT_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+EXPORT_ABI_VERSION = _header_export_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -230,6 +247,12 @@ def load():
         for name, (restype, argtypes) in VIZ_OTHER_SIGNATURES.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
+    if hasattr(lib, 'dbw_export_abi_version'):  # (absent from tuning builds of older sources: ops.frames_u8 refuses to run on them)
+        lib.dbw_export_abi_version.restype = c_i
+        for name, argtypes in EXPORT_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
     _lib = lib
     return lib
 

@@ -375,11 +375,35 @@ class DifferentiableBlocksWorld(nn.Module):
             return torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev)
         return scene.verts.detach().clone(), scene.faces.to(torch.int64)
 
-    def build_scene(self, filter_transparent=False):
-        """Background + ground + blocks as ONE scene (dbw.py:250-266), for the non-decoupled hard / SSAA evaluation render."""
-        env = self.build_env_scene()
+    def build_scene(self, filter_transparent=False, w_bkg=True, reduce_ground=False):
+        """Background + ground + blocks as ONE scene (dbw.py:250-266), for the non-decoupled hard / SSAA evaluation render.  w_bkg=False
+        leaves the sky dome out; reduce_ground scales the ground's x / z by 3 / z_far in front of its pose, UVs unchanged (dbw.py:282-285)
+        -- the clean mesh the evaluation exports."""
+        env = self.build_env_scene() if (w_bkg and not reduce_ground) else self._build_env_variant(w_bkg, reduce_ground)
         blocks = self.build_blocks_scene(filter_transparent=filter_transparent)
         return env if blocks is None else PackedScene.join([env, blocks])
+
+    def _build_env_variant(self, w_bkg, reduce_ground):
+        """build_env_scene without the sky dome and / or with the reduced ground: an export-time scene, built from the same tables."""
+        S_w, R_w, T_w = self._world_consts()
+        base = self._ground_base
+        if reduce_ground:
+            base = (base * torch.tensor([3 / self.z_far, 1, 3 / self.z_far], device=base.device)).contiguous()
+        ground_v = ops.posed_mesh(self.R_6d_ground, self.T_ground, base, S_w, R_w, T_w)
+        decim = self.decim_factor if (self.training and self.is_live('decimate_txt')) else 1
+        g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, decim)
+        desc = self._env_map_desc if decim == 1 else self._env_map_desc_dec
+        nf, nv = self._n_bkg_faces, self._bkg_verts.shape[0]
+        if w_bkg:
+            bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, decim)
+            scene = PackedScene(torch.cat([((self._bkg_verts * S_w) @ R_w + T_w).detach(), ground_v], 0), self._env_faces, self._env_face_uvs,
+                                self._env_face_map, desc, torch.cat([bkg_maps.reshape(-1), g_maps.reshape(-1)]))
+            scene.const_faces = nf
+            return scene
+        desc = desc[1:].clone()
+        desc[0, 0], desc[0, 6] = 0, 1
+        return PackedScene(ground_v, (self._env_faces[nf:] - nv).contiguous(), self._env_face_uvs[nf:].contiguous(),
+                           torch.zeros_like(self._env_face_map[nf:]), desc, g_maps.reshape(-1))
 
     def _shared_randn_like(self, t):
         """Opacity noise (and the overlap samples) must be identical on every data-parallel rank: they are
@@ -490,21 +514,29 @@ class DifferentiableBlocksWorld(nn.Module):
             self.renderer_light.update_cameras(device=inp['imgs'].device, K=self.renderer.cameras.K)
         was_training = self.training
         self.eval()
-        with self._host_packed_rebuild():                  # host-packed: `colors` / `desc` below hold the kept blocks only
-            blocks = self.build_blocks_scene(filter_transparent=True)
+        flat = self.build_synthetic_blocks()
         self.train(was_training)
-        if blocks is None:
+        if flat is None:
             return torch.ones_like(inp['imgs'])
+        if lit:
+            return self.renderer_light.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]
+        bg_renderer = Renderer(self.img_size, **{**self.renderer.init_kwargs, 'background_color': (1, 1, 1)})
+        bg_renderer.update_cameras(device=flat.verts.device, K=self.renderer.cameras.K)
+        return bg_renderer.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]
+
+    @torch.no_grad()
+    def build_synthetic_blocks(self):
+        """build_blocks(filter_transparent=True, synthetic_colors=True, as_scene=True) (dbw.py:297-346): the opaque blocks, each in its one
+        colour of the fancy colour map (a 1x1 map per block), or None when no block is left.  Host-packed: kept blocks only."""
+        with self._host_packed_rebuild():
+            blocks = self.build_blocks_scene(filter_transparent=True)
+        if blocks is None:
+            return None
         keep = (self.get_opacities() > 0.5).nonzero().flatten()
         values = torch.linspace(0, 1, self.n_blocks + 1)[1:][keep.cpu()]
         colors = torch.from_numpy(M.get_fancy_cmap()(values.numpy())).float().to(blocks.verts.device)
         desc = PackedScene.describe_maps([(1, 1)] * len(colors), [(0, 0)] * len(colors), blocks.verts.device)[0]
-        flat = PackedScene(blocks.verts, blocks.faces, blocks.face_uvs, blocks.face_map, desc, colors.reshape(-1).contiguous())
-        if lit:
-            return self.renderer_light.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]
-        bg_renderer = Renderer(self.img_size, **{**self.renderer.init_kwargs, 'background_color': (1, 1, 1)})
-        bg_renderer.update_cameras(device=blocks.verts.device, K=self.renderer.cameras.K)
-        return bg_renderer.render_packed(flat, inp['R'], inp['T'], viz_purpose=True)[:, :3]
+        return PackedScene(blocks.verts, blocks.faces, blocks.face_uvs, blocks.face_map, desc, colors.reshape(-1).contiguous())
 
     @torch.no_grad()
     def get_scene_face_colors(self, filter_transparent=False, w_env=True):       # dbw.py:420-431
@@ -609,6 +641,105 @@ class DifferentiableBlocksWorld(nn.Module):
         self.train(was_training)
         return OrderedDict([('n_blocks', n_blocks)] + [(k, m.avg) for k, m in meters.items()]
                            + [(f'alpha{k}', a.item()) for k, a in enumerate(opacities)])
+
+    # ------------------------------------------------------------------------------------------------ qualitative evaluation (dbw.py:495-554)
+    @torch.no_grad()
+    def qualitative_eval(self, loader, device, path=None, NV=240):
+        """The pictures, meshes and videos of a trained model, the file set of the reference (dbw.py:495-554), under `path`:
+        textures/{bkg,ground,block_XX}.png; rotated_mesh.*; mesh_full.obj and mesh.obj (without the sky dome, reduced ground), each with its
+        .mtl and .png; gt.ply (3000 points of loader.dataset.pc_gt under seed 123, where the dataset has one); and per input i (at most
+        10): i_inp, i_rec, i_rec_col, i_rec_col_inp, i_rec_syn_nobkg, i_rec_syn_nobkg_edged .png and the two trajectories i_rec_traj.*,
+        i_rec_traj_syn.* over R @ R_traj of get_circle_traj(N_views=NV).  Videos are mp4 where imageio imports, animated GIFs otherwise
+        (export.save_video); rotated_mesh has NV views too (the reference's 240 is its NV).  Stops after the meshes when no block is
+        opaque.  `loader`: any iterable of (inp, labels); its batch_size, or the size of the first batch, numbers the inputs.  Every frame is
+        converted to 8 bits on the GPU (renderer.render_views_u8, ops.frames_u8).  The train / eval state is put back on exit.
+        -> {'render': seconds in render + conversion + copy, 'encode': seconds in the file writers}."""
+        import time
+        from pathlib import Path
+        from . import export
+        from .renderer import get_circle_traj, render_rotated_views_u8, render_views_u8, _pooled_color
+        path = Path(path or '.')
+        path.mkdir(parents=True, exist_ok=True)
+        spent = {'render': 0.0, 'encode': 0.0}
+
+        def timed(kind, fn, *a, **k):
+            t0 = time.perf_counter()
+            out = fn(*a, **k)
+            spent[kind] += time.perf_counter() - t0
+            return out
+
+        def still(name, src, **k):
+            frame = timed('render', lambda: ops.frames_u8(src, **k)[0].cpu())
+            timed('encode', export.save_png, frame, path / name)
+
+        was_training = self.training
+        self.eval()
+        try:
+            # Textures: the prepared maps (sigmoid of the parameters), (n,h,w,3)
+            (path / 'textures').mkdir(exist_ok=True)
+            for name, param in (('bkg', self.texture_bkg), ('ground', self.texture_ground), ('block_', self.textures)):
+                frames = timed('render', lambda: ops.frames_u8(ops.texture_prep(param.detach())[0], hwc=True).cpu())
+                for k, frame in enumerate(frames):
+                    timed('encode', export.save_png, frame, path / 'textures' / (f'block_{str(k).zfill(2)}.png' if name == 'block_' else f'{name}.png'))
+
+            # Basic 3D
+            with self._host_packed_rebuild():       # host-packed: the colour table below has one row per KEPT face
+                meshes = self.build_scene(filter_transparent=True)
+                clean_mesh = self.build_scene(filter_transparent=True, w_bkg=False, reduce_ground=True)
+            colors = self.get_scene_face_colors(filter_transparent=True, w_env=False)
+            first = next(iter(loader))[0]
+            self._ensure_cameras({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in first.items()})
+            frames = timed('render', render_rotated_views_u8, meshes, renderer=self.renderer, n_views=NV, elev=30, dist=2.732)
+            timed('encode', export.save_video, frames, path / 'rotated_mesh.mp4')
+            timed('encode', export.save_scene_as_obj, meshes, path / 'mesh_full.obj')
+            timed('encode', export.save_scene_as_obj, clean_mesh, path / 'mesh.obj')
+            syn_blocks = self.build_synthetic_blocks()
+            if syn_blocks is None:
+                return spent
+            # GT pointcloud
+            gt = getattr(getattr(loader, 'dataset', None), 'pc_gt', None)
+            if gt is not None:
+                gt = torch.as_tensor(gt)
+                gt = gt[torch.randperm(len(gt), generator=torch.Generator().manual_seed(123))[:3000]]
+                timed('encode', export.save_ply, path / 'gt.ply', gt)
+
+            renderer, renderer_light = self.renderer, self.renderer_light
+            H, W = self.img_size
+            count, N = 0, 10
+            R_traj = get_circle_traj(N_views=NV)[0].to(device)
+            n_zeros = int(np.log10(N - 1)) + 1
+            BS = getattr(loader, 'batch_size', None)
+            grey = _pooled_color(torch.tensor([0.3, 0.3, 0.3], device=device))
+            for j, (inp, labels) in enumerate(loader):
+                if count >= N:
+                    break
+                inp = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in inp.items()}
+                img_src, R_src, T_src = inp['imgs'], inp['R'], inp['T']
+                BS = len(img_src) if BS is None else BS
+                B = min(len(img_src), N - count)
+                for k in range(B):
+                    i = str(j * BS + k).zfill(n_zeros)
+                    img = img_src[k:k + 1].float().contiguous()
+                    R, T = R_src[k:k + 1], T_src[k:k + 1]
+                    still(f'{i}_inp.png', img)
+                    rec = timed('render', renderer.render_viz, meshes, R, T)
+                    still(f'{i}_rec.png', rec)
+                    mask, col = timed('render', renderer.edge_layers, syn_blocks, R, T, (H, W), colors)
+                    still(f'{i}_rec_col.png', rec, mask=mask, edge_color=col)
+                    still(f'{i}_rec_col_inp.png', img, mask=mask, edge_color=col)
+                    rec = timed('render', renderer_light.render_viz, syn_blocks, R, T)
+                    still(f'{i}_rec_syn_nobkg.png', rec)
+                    mask, _ = timed('render', renderer_light.edge_layers, syn_blocks, R, T, (H, W), colors.new_zeros(3), linewidth=0.7)
+                    still(f'{i}_rec_syn_nobkg_edged.png', rec, mask=mask, edge_color=grey)
+                    R_v, T_v = (R @ R_traj).contiguous(), T.expand(NV, -1).contiguous()
+                    frames = timed('render', render_views_u8, meshes, R_v, T_v, renderer=renderer)
+                    timed('encode', export.save_video, frames, path / f'{i}_rec_traj.mp4')
+                    frames = timed('render', render_views_u8, syn_blocks, R_v, T_v, renderer=renderer_light)
+                    timed('encode', export.save_video, frames, path / f'{i}_rec_traj_syn.mp4')
+                count += B
+            return spent
+        finally:
+            self.train(was_training)
 
     # ------------------------------------------------------------------------------------------------ losses (dbw.py:361-408)
     def _perceptual_term(self, imgs, rec, coarse, view_ids=None):

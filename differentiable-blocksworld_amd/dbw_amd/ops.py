@@ -703,6 +703,53 @@ def render_scene_lit(verts, maps, faces_alpha, faces_i32, R, T, Kmat, face_uvs, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 8-bit frame export (include/dbw_export.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def frames_u8(src, bkg=None, mask=None, edge_color=None, hwc=False, edge_first=False, clamp_input=False, out=None):
+    """dbw_frames_u8: fp32 frames on the GPU -> (N,H,W,3) uint8 on the GPU, as the reference's convert_to_img quantises (clamp to [0, 1],
+    times 255, truncate).  src (N,C,H,W), C = 3 or 4 -- or (N,H,W,3) with hwc, the layout of the prepared texture maps.  bkg: three floats
+    or a (3,H,W) tensor, composited under a C = 4 source (premultiplied rgb: rgb * alpha + (1 - alpha) * bkg).  mask (N,1,H,W) with
+    edge_color three floats or (N,3,H,W): img * (1 - mask) + mask * colour, behind the composite, or in front of it with edge_first.
+    clamp_input clamps the source channels to [0, 1] first.  out: an (N,H,W,3) uint8 GPU tensor to fill."""
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_export_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no frame export entry point (include/dbw_export.h): rebuild it')
+    src_c = _chk(src, torch.float32, 'src')
+    if src_c.dim() != 4:
+        raise ValueError(f'src: four dimensions, got {tuple(src_c.shape)}')
+    (N, H, W, C) = src_c.shape if hwc else (src_c.shape[0], src_c.shape[2], src_c.shape[3], src_c.shape[1])
+    dev = src_c.device
+    bkg3 = bkg_img = edge3 = edge_img = mask_c = None
+    if bkg is not None:
+        if torch.is_tensor(bkg) and bkg.dim() == 3:
+            bkg_img = _chk(bkg, torch.float32, 'bkg')
+            if tuple(bkg_img.shape) != (3, H, W):
+                raise ValueError(f'bkg: (3,{H},{W}), got {tuple(bkg_img.shape)}')
+        else:
+            bkg3 = make_bg(torch.as_tensor(bkg).reshape(3).tolist())
+    if mask is not None:
+        mask_c = _chk(mask, torch.float32, 'mask')
+        if tuple(mask_c.shape) != (N, 1, H, W):
+            raise ValueError(f'mask: ({N},1,{H},{W}), got {tuple(mask_c.shape)}')
+        if torch.is_tensor(edge_color) and edge_color.dim() == 4:
+            edge_img = _chk(edge_color, torch.float32, 'edge_color')
+            if tuple(edge_img.shape) != (N, 3, H, W):
+                raise ValueError(f'edge_color: ({N},3,{H},{W}), got {tuple(edge_img.shape)}')
+        elif edge_color is not None:
+            edge3 = make_bg(torch.as_tensor(edge_color).reshape(3).tolist())
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (N, H, W, 3)):
+        raise ValueError(f'out: a contiguous ({N},{H},{W},3) uint8 GPU tensor')
+    flags = (_lib.FRAME_HWC if hwc else 0) | (_lib.FRAME_EDGE_FIRST if edge_first else 0) | (_lib.FRAME_CLAMP_INPUT if clamp_input else 0)
+    if N == 0:                  # (an empty tensor has no address to validate)
+        return out
+    _lib.call('dbw_frames_u8', _ptr(src_c), N, C, H, W, flags, _bg_ptr(bkg3), _ptr(bkg_img), _ptr(mask_c), _bg_ptr(edge3), _ptr(edge_img),
+              _ptr(out), _stream(src_c))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # texture preparation, param -> mesh, losses, optimiser
 # ---------------------------------------------------------------------------------------------------------------------
 class _TexturePrep(torch.autograd.Function):

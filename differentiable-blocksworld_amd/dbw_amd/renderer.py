@@ -267,16 +267,41 @@ class Renderer(nn.Module):
             T = torch.zeros(1, 3, device=dev).expand(B, -1)
         colors = torch.as_tensor((1., 0., 0.) if colors is None else colors, dtype=torch.float32, device=dev)
         size = tuple(img.shape[-2:])
+        mask, face_img = self.edge_layers(scene, R, T, size, colors, linewidth, antialias)
+        if face_img is None:
+            face_img = colors[None, :, None, None].expand(B, -1, *((size[0] * 4, size[1] * 4) if antialias else size))
+            if antialias:
+                face_img = F.avg_pool2d(face_img, kernel_size=4, stride=4)
+        return img * (1 - mask) + mask * face_img
+
+    @torch.no_grad()
+    def edge_layers(self, scene, R, T, size, colors, linewidth=1, antialias=True):
+        """The two layers draw_edges blends over an image of `size`: the mask (B,1,H,W) and, for one colour per packed face (colors
+        (B*F,3)), the colour image (B,3,H,W) -- None for a single colour.  antialias: both are rasterised at 4x and average-pooled."""
         if antialias:
             size, linewidth = (size[0] * 4, size[1] * 4), linewidth * 4
         mask, pix2face = self.render_edges(scene, R, T, image_size=size, linewidth=linewidth, return_pix2face=True)
-        if colors.dim() == 2:
-            face_img = colors[pix2face].permute(0, 3, 1, 2)                       # one colour per face (empty pixels: last row, masked)
-        else:
-            face_img = colors[None, :, None, None].expand(B, -1, *size)
+        face_img = colors[pix2face].permute(0, 3, 1, 2) if colors.dim() == 2 else None      # (empty pixels: last row, masked)
         if antialias:
-            mask, face_img = [F.avg_pool2d(t, kernel_size=4, stride=4) for t in (mask, face_img)]
-        return img * (1 - mask) + mask * face_img
+            mask = F.avg_pool2d(mask, kernel_size=4, stride=4)
+            face_img = None if face_img is None else F.avg_pool2d(face_img, kernel_size=4, stride=4)
+        return mask, face_img
+
+    def render_viz(self, scene, R, T):
+        """(B,4,H,W): the exact 4x anti-aliased hard render of render_packed(viz_purpose=True), through the lit kernel for every renderer
+        -- it resolves its 4x4 super-samples in registers, no 4H x 4W image exists.  An unlit ('raw') renderer is an ambient gain of 1
+        and no diffuse term there (tests/test_gpu_lit.py bounds the difference to the pooled raw render: RESOLVE_ATOL)."""
+        if self.lit:
+            return self.render_packed(scene, R, T, viz_purpose=True)
+        if self.cam_name != 'perspective' or self.cameras.K is None:
+            raise NotImplementedError('the HIP path needs perspective cameras with an explicit NDC K: call '
+                                      'update_cameras(K=...) first (dbw.py:204-208)')
+        H, W = self.img_size
+        cfg = ops.RenderCfg(H, W, 1, 0.0, self.z_clip, self.perspective_correct, False, scene.faces.shape[0], EPS)
+        Kmat = self.cameras.K[0].to(R.device).contiguous()
+        return ops.render_scene_lit(scene.verts, scene.maps, None, scene.faces, R.float().contiguous(), T.float().contiguous(), Kmat, scene.face_uvs,
+                                    scene.face_map, scene.map_desc, self._bg, cfg, torch.tensor([[0., 0., -1.]]), [1., 1., 1.], [0., 0., 0.],
+                                    phong=False, ssaa=4)
 
     def forward(self, meshes, R, T, viz_purpose=False, **kwargs):
         faces_alpha = kwargs.pop('faces_alpha', None)
@@ -396,3 +421,137 @@ def render_rotated_views(mesh, renderer=None, n_views=50, elev=30, dist=2.5, R=N
         T_view = torch.tensor([[0., 0., float(dist)]], device=dev).expand(len(R_view), -1)
         views.append(renderer(scene, (R_view @ R).contiguous(), (T_view + T).contiguous(), viz_purpose=True).clamp(0, 1).cpu())
     return _composite_bkg(views, bkg, renderer.img_size)
+
+
+# -- the same trajectories as 8-bit frames: what an image or a video file holds (include/dbw_export.h) ----------------------------------------
+FRAME_WORKSPACE_BYTES = 256 << 20          # device memory one chunk of views may take (render workspace + fp32 image + edge layers)
+
+
+def _views_per_chunk(scene, img_size, n_views, with_edges=False):
+    """Views rendered per launch: as many as fit FRAME_WORKSPACE_BYTES, from the lit kernel's own workspace size (the clipper emits at
+    most two faces per face) and the planes a view keeps on the device."""
+    H, W = img_size
+    F_ = int(scene.faces.shape[0])
+    per_view = int(ops._viz_lib().dbw_render_lit_workspace_bytes(2 * F_, 1, F_, H, W, 4)) + H * W * (16 + 2 * 3)
+    if with_edges:           # the 4x edge rasterisation: fragments and the two pooled layers
+        per_view += 16 * H * W * 4 * 8 + H * W * 16
+    return max(1, min(n_views, FRAME_WORKSPACE_BYTES // max(per_view, 1)))
+
+
+def _host_frames(n, H, W, out):
+    if out is None:
+        return torch.empty(n, H, W, 3, dtype=torch.uint8, pin_memory=True)
+    if out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != (n, H, W, 3):
+        raise ValueError(f'out: a contiguous ({n},{H},{W},3) uint8 host tensor (pinned, for the copy to overlap the next render)')
+    return out
+
+
+def _stream_frames(chunks, n, H, W, device, out=None):
+    """chunks yields (count, fill): fill(dst) enqueues the render and the conversion of `count` frames into the (count,H,W,3) uint8 device
+    tensor dst on the current stream.  Each chunk is copied to the host on a second stream, ordered by events: chunk k copies while
+    chunk k + 1 renders; two device buffers alternate.  -> the (n,H,W,3) uint8 host tensor, complete on return."""
+    out = _host_frames(n, H, W, out)
+    cur, copy = torch.cuda.current_stream(device), torch.cuda.Stream(device)
+    bufs, copied, pos = [None, None], [None, None], 0
+    for k, (count, fill) in enumerate(chunks):
+        slot = k & 1
+        if bufs[slot] is None or bufs[slot].shape[0] < count:
+            bufs[slot] = torch.empty(count, H, W, 3, dtype=torch.uint8, device=device)
+        if copied[slot] is not None:
+            cur.wait_event(copied[slot])               # the copy of chunk k - 2 has left this buffer
+        fill(bufs[slot][:count])
+        done = torch.cuda.Event()
+        done.record(cur)
+        with torch.cuda.stream(copy):
+            copy.wait_event(done)
+            out[pos:pos + count].copy_(bufs[slot][:count], non_blocking=True)
+            copied[slot] = torch.cuda.Event()
+            copied[slot].record(copy)
+        pos += count
+    copy.synchronize()
+    assert pos == n
+    return out
+
+
+def _bkg_on_device(bkg, img_size, device):
+    """The background of _composite_bkg (resized on the host exactly as there), on the device."""
+    if bkg is None:
+        return None
+    bkg = bkg.cpu().float()
+    if tuple(bkg.shape[-2:]) != tuple(img_size):
+        bkg = F.interpolate(bkg[None], size=tuple(img_size), mode='bilinear', align_corners=False)[0]
+    return bkg.contiguous().to(device)
+
+
+def _pooled_color(colors):
+    """One colour after draw_edges' 4x4 average pooling of its constant image (sixteen equal addends need not sum to 16 c in fp32)."""
+    return F.avg_pool2d(colors.reshape(1, 3, 1, 1).expand(1, 3, 4, 4), kernel_size=4, stride=4).reshape(3).tolist()
+
+
+@torch.no_grad()
+def render_views_u8(mesh, R, T, renderer=None, bkg=None, with_edges=False, linewidth=1, edge_colors=None, eye_light=False, out=None, chunk=None):
+    """render_views as 8-bit frames: the views (R[i], T[i]) of `mesh`, exact 4x anti-aliased renders -> (N,H,W,3) uint8 on the HOST (pinned;
+    or `out`, filled in place), quantised as the reference's convert_to_img does (clamp to [0, 1], times 255, truncate).  Same arguments
+    as render_views; composite, edge blend, quantisation and interleave run on the device (dbw_frames_u8), so 3 bytes per pixel cross to the
+    host instead of 16, and the copy of a chunk overlaps the render of the next.  Every renderer goes through the lit kernel
+    (Renderer.render_viz).  chunk: views per launch (default: what fits FRAME_WORKSPACE_BYTES); the frames do not depend on it."""
+    _need_renderer(renderer)
+    if eye_light:
+        renderer = _eye_light_renderer(renderer, DIRECTION_LIGHT, 0.7)
+    scene = renderer._as_scene(mesh)
+    dev = scene.verts.device
+    H, W = renderer.img_size
+    n_views = len(R)
+    B = int(chunk) if chunk else _views_per_chunk(scene, (H, W), n_views, with_edges)
+    bkg_dev = _bkg_on_device(bkg, (H, W), dev)
+    colors = color3 = None
+    if with_edges:
+        colors = torch.as_tensor((1., 0., 0.) if edge_colors is None else edge_colors, dtype=torch.float32, device=dev)
+        if colors.dim() != 2:
+            color3 = _pooled_color(colors)
+
+    def chunks():
+        for k in range((n_views - 1) // B + 1):
+            R_view, T_view = R[k * B: (k + 1) * B], T[k * B: (k + 1) * B]
+
+            def fill(dst, R_view=R_view, T_view=T_view):
+                res = renderer.render_viz(scene, R_view, T_view)
+                mask = col = None
+                if with_edges:
+                    per_face = colors.repeat(len(R_view), 1) if color3 is None else colors
+                    mask, col = renderer.edge_layers(scene, R_view, T_view, (H, W), per_face, linewidth=linewidth)
+                    col = color3 if col is None else col
+                ops.frames_u8(res, bkg=bkg_dev, mask=mask, edge_color=col, edge_first=True, out=dst)
+            yield len(R_view), fill
+    return _stream_frames(chunks(), n_views, H, W, dev, out)
+
+
+@torch.no_grad()
+def render_rotated_views_u8(mesh, renderer=None, n_views=50, elev=30, dist=2.5, R=None, T=None, bkg=None, eye_light=False, out=None, chunk=None):
+    """render_rotated_views as 8-bit frames (see render_views_u8): `mesh` from n_views azimuths -> (n_views,H,W,3) uint8 on the host."""
+    _need_renderer(renderer)
+    if eye_light:
+        if R is not None:
+            raise NotImplementedError
+        renderer = _eye_light_renderer(renderer, [0, 0, -1], 0.6)
+    scene = renderer._as_scene(mesh)
+    dev = scene.verts.device
+    H, W = renderer.img_size
+    elev, dist = 0 if R is not None else elev, 0 if T is not None else dist
+    R = torch.eye(3, device=dev) if R is None else R.to(dev)
+    T = torch.zeros(3, device=dev) if T is None else T.to(dev)
+    azim = torch.linspace(-180, 180, n_views)
+    B = int(chunk) if chunk else _views_per_chunk(scene, (H, W), n_views)
+    bkg_dev = _bkg_on_device(bkg, (H, W), dev)
+
+    def chunks():
+        for k in range((n_views - 1) // B + 1):
+            az = azim[k * B: (k + 1) * B]
+
+            def fill(dst, az=az):
+                R_view = look_at_view_transform(dist=1, elev=elev, azim=az, device=dev)[0]
+                T_view = torch.tensor([[0., 0., float(dist)]], device=dev).expand(len(R_view), -1)
+                res = renderer.render_viz(scene, (R_view @ R).contiguous(), (T_view + T).contiguous())
+                ops.frames_u8(res, bkg=bkg_dev, clamp_input=bkg_dev is not None, out=dst)      # (render_rotated_views clamps before it composites)
+            yield len(az), fill
+    return _stream_frames(chunks(), n_views, H, W, dev, out)

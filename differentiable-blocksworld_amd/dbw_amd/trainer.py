@@ -2,7 +2,8 @@
 checkpointing with the semantics of the reference's src/scheduler.py:26-69, src/optimizer.py:6-18 and
 src/trainer.py:109-169,201-209, driving `ShardedTrainStep` (flat parameter buffer, fused Adam, optional RCCL all-reduce).
 
-Host-side scalars only; nothing here touches pixels.  No logging / visualisation / evaluation plumbing (out of scope)."""
+Host-side scalars only; nothing here touches pixels.  No logging / visualisation plumbing (out of scope); `evaluate` ends a run like
+the reference's trainer.py:241-272."""
 import time
 from collections import Counter
 
@@ -160,6 +161,27 @@ class Trainer:
         for _ in range(self.epoch, (n_epoches or self.n_epoches) + 1):
             last = self.run_epoch()
         return last
+
+    # trainer.py:241-272
+    def evaluate(self, loader, run_dir, dtu=None):
+        """The end of a run: qualitative_eval into run_dir/quali_eval, quantitative_eval (hard inference) into run_dir/final_scores.tsv
+        (a line of names, a line of values, '{:.5f}'), and -- dtu = dict(scale_mat=, scan_id=, dataset_dir=), further keywords of
+        eval3d.evaluate_dtu allowed -- the official DTU scores of the blocks into run_dir.  loader: an iterable of (inp, labels) that can be
+        walked twice.  -> the scores (with the DTU dict under 'dtu' where asked for)."""
+        import os
+        run_dir = str(run_dir)
+        os.makedirs(os.path.join(run_dir, 'quali_eval'), exist_ok=True)
+        device = self.views['imgs'].device
+        self.model.eval()
+        self.model.qualitative_eval(loader, device, path=os.path.join(run_dir, 'quali_eval'))
+        scores = self.model.quantitative_eval(loader, device, hard_inference=True)
+        with open(os.path.join(run_dir, 'final_scores.tsv'), mode='w') as f:
+            f.write('\t'.join(scores.keys()) + '\n')
+            f.write('\t'.join('{:.5f}'.format(float(v)) for v in scores.values()) + '\n')
+        if dtu is not None:
+            from .eval3d import evaluate_dtu
+            scores = dict(scores, dtu=evaluate_dtu(self.model, eval_dir=run_dir, **dtu))
+        return scores
 
     # trainer.py:201-209 / 84-107
     def state_dict(self):
