@@ -190,6 +190,27 @@ def _header_export_abi_version():
 
 EXPORT_ABI_VERSION = _header_export_abi_version()
 
+# the image ingest: name -> argtypes, exactly the int-returning prototypes of include/dbw_ingest.h (checked by tests/test_ingest_host.py);
+# the one size_t-returning entry point next to them.  dbw_resample_table returns its ksize (> 0) or a negative DBW_ERR_*: not for call().
+INGEST_SIGNATURES = {
+    'dbw_resample_table': [c_i, c_i, c_p, c_sz],
+    'dbw_images_resample_u8': [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_i, c_p],
+}
+INGEST_OTHER_SIGNATURES = {
+    'dbw_images_resample_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+}
+RESAMPLE_AUTO, RESAMPLE_GENERAL, RESAMPLE_FUSED = 0, 1, 2     # DBW_RESAMPLE_* of include/dbw_ingest.h
+
+
+def _header_ingest_abi_version():
+    """DBW_INGEST_ABI_VERSION of include/dbw_ingest.h (dbw_ingest_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_ingest.h')) as f:
+        return int(re.search(r'#define DBW_INGEST_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+INGEST_ABI_VERSION = _header_ingest_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -253,6 +274,15 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = c_i
+    if hasattr(lib, 'dbw_ingest_abi_version'):  # (absent from tuning builds of older sources: ops.resample_u8 refuses to run on them)
+        lib.dbw_ingest_abi_version.restype = c_i
+        for name, argtypes in INGEST_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
+        for name, (restype, argtypes) in INGEST_OTHER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 

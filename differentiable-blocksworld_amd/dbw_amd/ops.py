@@ -750,6 +750,65 @@ def frames_u8(src, bkg=None, mask=None, edge_color=None, hwc=False, edge_first=F
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# image ingest (include/dbw_ingest.h)
+# ---------------------------------------------------------------------------------------------------------------------
+_RESAMPLE_TABLES = {}
+_RESAMPLE_FORMS = {'auto': _lib.RESAMPLE_AUTO, 'general': _lib.RESAMPLE_GENERAL, 'fused': _lib.RESAMPLE_FUSED}
+
+
+def resample_table(in_size, out_size, device=None):
+    """dbw_resample_table: the (out_size, ksize + 2) int32 rows [xmin, n, k_0 .. k_{ksize-1}] of one axis, on the host -- or, with a
+    device, the copy of them resident there, made once per (in_size, out_size, device)."""
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_ingest_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no image ingest entry point (include/dbw_ingest.h): rebuild it')
+    key = (int(in_size), int(out_size), None if device is None else str(torch.device(device)))
+    if key not in _RESAMPLE_TABLES:
+        if device is not None:
+            _RESAMPLE_TABLES[key] = resample_table(in_size, out_size).to(device)
+        else:
+            ksize = lib.dbw_resample_table(key[0], key[1], None, 0)
+            if ksize <= 0:
+                raise RuntimeError(f'dbw_resample_table failed (rc={ksize}): {lib.dbw_last_error().decode()}')
+            t = torch.zeros(key[1], ksize + 2, dtype=torch.int32)
+            rc = lib.dbw_resample_table(key[0], key[1], t.data_ptr(), t.numel())
+            if rc != ksize:
+                raise RuntimeError(f'dbw_resample_table failed (rc={rc}): {lib.dbw_last_error().decode()}')
+            _RESAMPLE_TABLES[key] = t
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_u8(src_u8, size, out='f32', form='auto'):
+    """dbw_images_resample_u8: (N,Hin,Win,3) uint8 frames on the GPU -> what the reference's Compose([Resize(size), ToTensor()]) makes of
+    them on the host, bit for bit (Pillow's antialiased BILINEAR resample in 8-bit fixed point, then uint8 / 255 in fp32).  size (Hout,Wout).
+    out: 'f32' -> (N,3,Hout,Wout) fp32, the layout of views['imgs']; 'u8' -> (N,Hout,Wout,3) uint8; 'both' -> the pair.  form: 'auto', or
+    'general' / 'fused' to force one of the two kernel forms (the same bytes; 'fused' refuses ratios above 5)."""
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_ingest_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no image ingest entry point (include/dbw_ingest.h): rebuild it')
+    if out not in ('f32', 'u8', 'both') or form not in _RESAMPLE_FORMS:
+        raise ValueError(f"out: 'f32', 'u8' or 'both', form: 'auto', 'general' or 'fused'; got {out!r}, {form!r}")
+    src = _chk(src_u8, torch.uint8, 'src_u8')
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f'src_u8: (N,Hin,Win,3), got {tuple(src.shape)}')
+    N, Hin, Win, _ = src.shape
+    Hout, Wout = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if Hout <= 0 or Wout <= 0 or Hin <= 0 or Win <= 0:
+        raise ValueError(f'bad size: {(Hin, Win)} -> {(Hout, Wout)}')
+    dev = src.device
+    f32 = torch.empty(N, 3, Hout, Wout, dtype=torch.float32, device=dev) if out != 'u8' else None
+    u8 = torch.empty(N, Hout, Wout, 3, dtype=torch.uint8, device=dev) if out != 'f32' else None
+    if N > 0:
+        tx = resample_table(Win, Wout, dev) if Win != Wout else None
+        ty = resample_table(Hin, Hout, dev) if Hin != Hout else None
+        ws_bytes = 0 if form == 'fused' else lib.dbw_images_resample_workspace_bytes(N, Hin, Win, Hout, Wout)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        _lib.call('dbw_images_resample_u8', _ptr(src), N, Hin, Win, Hout, Wout, _ptr(tx), _ptr(ty), _ptr(f32), _ptr(u8), _ptr(ws), ws_bytes,
+                  _RESAMPLE_FORMS[form], _stream(src))
+    return {'f32': f32, 'u8': u8, 'both': (f32, u8)}[out]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # texture preparation, param -> mesh, losses, optimiser
 # ---------------------------------------------------------------------------------------------------------------------
 class _TexturePrep(torch.autograd.Function):

@@ -1,0 +1,82 @@
+"""python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N] [--lpips-vgg F --lpips-lin F | --no-perceptual]
+
+A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
+to it, then the file), the scenes of cfg['dataset'] are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
+saved as <runs-root>/<dataset>/<tag>/model.pkl (Trainer.state_dict) and evaluated by Trainer.evaluate on the test split -- for a DTU scan
+whose evaluation data (ObsMask/, Points/stl/) lies under <data-root>/DTU, the official scores too.
+
+The perceptual term needs the weights of a VGG16 and of the LPIPS heads, which do not ship with the package: a config with
+perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so)."""
+import argparse
+import os
+import sys
+
+import torch
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m dbw_amd.train', description='Train and evaluate a model specified by one of the YAML configs')
+    ap.add_argument('-c', '--config', required=True, help='config file (its default.yml is looked up next to it)')
+    ap.add_argument('-d', '--default', default=None, help='default config file, instead of the default.yml next to --config')
+    ap.add_argument('-t', '--tag', required=True, help='run tag: the run directory is <runs-root>/<dataset name>/<tag>')
+    ap.add_argument('--data-root', required=True, help='the directory that holds DTU/ and BlendedMVS/')
+    ap.add_argument('--runs-root', required=True)
+    ap.add_argument('--epochs', type=int, default=None, help='override training.n_epoches')
+    ap.add_argument('--lpips-vgg', default=None, help="state dict of torchvision's vgg16().features (torch.save)")
+    ap.add_argument('--lpips-lin', default=None, help="state dict with lpips' lin{k}.model.1.weight tensors (torch.save)")
+    ap.add_argument('--no-perceptual', action='store_true', help='train without the perceptual term')
+    ap.add_argument('--device', default='cuda:0')
+    return ap.parse_args(argv)
+
+
+def prepare_config(args):
+    """The config of a run, with the perceptual term settled: kept (both weight files given), dropped (--no-perceptual) or refused."""
+    from .dataset import load_config
+    cfg = load_config(args.config, args.default)
+    loss = cfg.get('model', {}).get('loss', {})
+    if (loss.get('perceptual_weight') or 0) > 0:
+        if args.no_perceptual:
+            print(f"--no-perceptual: perceptual_weight {loss['perceptual_weight']} -> 0, the run optimises the other terms only")
+            loss['perceptual_weight'] = 0
+        elif not (args.lpips_vgg and args.lpips_lin):
+            raise SystemExit(f"{args.config}: perceptual_weight = {loss['perceptual_weight']} needs the LPIPS network's weights, which do not "
+                             'ship with this package: give --lpips-vgg and --lpips-lin, or --no-perceptual to train without the term')
+    if args.epochs is not None:
+        cfg.setdefault('training', {})['n_epoches'] = args.epochs
+    return cfg
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cfg = prepare_config(args)
+    from . import create_model
+    from .dataset import create_train_val_test
+    from .trainer import Trainer
+    run_dir = os.path.join(args.runs_root, cfg['dataset']['name'], args.tag)
+    os.makedirs(run_dir, exist_ok=True)
+    seed = cfg['training'].get('seed', 4321)
+    torch.manual_seed(seed)
+    train, val, test = create_train_val_test(cfg, args.data_root, args.device)
+    model = create_model(cfg, train.img_size).to(args.device).train()
+    if 'perceptual' in model.loss_weights:
+        from .lpips_vgg import LPIPSVGG
+        net = LPIPSVGG()
+        net.load_weights(torch.load(args.lpips_vgg, map_location='cpu'), torch.load(args.lpips_lin, map_location='cpu'))
+        model.set_perceptual(net.to(args.device))
+    trainer = Trainer(cfg, model, train.views(args.device))
+    print(f'Trainer init: config_file={args.config}, run_dir={run_dir}, n_epoches={trainer.n_epoches}')
+    last = trainer.run()
+    if last is not None:
+        print('last step: ' + ', '.join(f'{k}={float(v):.5f}' for k, v in last.items()))
+    torch.save(trainer.state_dict(), os.path.join(run_dir, 'model.pkl'))
+    dtu = None
+    dtu_dir = os.path.join(args.data_root, 'DTU')
+    if train.name == 'dtu' and os.path.isdir(os.path.join(dtu_dir, 'ObsMask')) and os.path.isdir(os.path.join(dtu_dir, 'Points', 'stl')):
+        dtu = dict(scale_mat=train.scale_mat.to(args.device), scan_id=int(train.tag.replace('scan', '')), dataset_dir=dtu_dir)
+    scores = trainer.evaluate(test.loader(trainer.batch_size, args.device), run_dir, dtu=dtu)
+    print('final_scores: ' + ', '.join(f'{k}={v:.5f}' for k, v in scores.items() if not isinstance(v, dict)))
+    return scores
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])
