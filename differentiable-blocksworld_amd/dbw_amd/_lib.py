@@ -211,6 +211,22 @@ def _header_ingest_abi_version():
 
 INGEST_ABI_VERSION = _header_ingest_abi_version()
 
+# the lens rectification: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by tests/test_lens_host.py).
+LENS_SIGNATURES = {
+    'dbw_images_undistort_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+}
+LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h
+
+
+def _header_lens_abi_version():
+    """DBW_LENS_ABI_VERSION of include/dbw_lens.h (dbw_lens_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_lens.h')) as f:
+        return int(re.search(r'#define DBW_LENS_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+LENS_ABI_VERSION = _header_lens_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -283,6 +299,12 @@ def load():
         for name, (restype, argtypes) in INGEST_OTHER_SIGNATURES.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
+    if hasattr(lib, 'dbw_lens_abi_version'):    # (absent from tuning builds of older sources: ops.undistort_u8 refuses to run on them)
+        lib.dbw_lens_abi_version.restype = c_i
+        for name, argtypes in LENS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
     _lib = lib
     return lib
 

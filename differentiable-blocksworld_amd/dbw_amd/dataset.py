@@ -1,5 +1,5 @@
-"""Scene ingest: a DTU / BlendedMVS scene directory on disk -> the resident `views` dict Trainer(cfg, model, views) consumes, the
-(inp, labels) loaders the evaluations walk, and the reference's YAML configs.  Restates src/dataset/dtu.py, src/dataset/bmvs.py,
+"""Scene ingest: a DTU / BlendedMVS scene directory, or a capture of one's own with a transforms.json (CustomScene), on disk -> the
+resident `views` dict Trainer(cfg, model, views) consumes, the (inp, labels) loaders the evaluations walk, and the reference's YAML configs.  Restates src/dataset/dtu.py, src/dataset/bmvs.py,
 src/dataset/__init__.py and utils.load_yaml of the reference.
 
 The reference resizes every image on the host, per item, with Compose([Resize(img_size), ToTensor()]) on a PIL image.  Here each file is
@@ -74,10 +74,12 @@ def decode_rgb(path):
 
 class ImageStore:
     """The decoded frames of one scene directory, resident on one device: (N,3,H,W) fp32 targets of one img_size, filled file by file the
-    first time a view is asked for, and optionally the raw (N,Hraw,Wraw,3) uint8 stack.  The three splits of a scene share one store."""
+    first time a view is asked for, and optionally the raw (N,Hraw,Wraw,3) uint8 stack.  The three splits of a scene share one store.
+    prepare: a callable from the uploaded (n,Hraw,Wraw,3) uint8 chunk on the device to a chunk of the same kind, applied before the
+    resize (a custom scene's lens rectification); the raw stack keeps what came off disk."""
 
-    def __init__(self, files, img_size, chunk=16):
-        self.files, self.img_size, self.chunk = list(files), tuple(img_size), chunk
+    def __init__(self, files, img_size, chunk=16, prepare=None):
+        self.files, self.img_size, self.chunk, self.prepare = list(files), tuple(img_size), chunk, prepare
         self.device = self.imgs = self.raw = None
         self.have, self.have_raw = np.zeros(len(self.files), bool), np.zeros(len(self.files), bool)
 
@@ -115,7 +117,7 @@ class ImageStore:
                 events[slot] = torch.cuda.Event()
                 events[slot].record(torch.cuda.current_stream(device))
             idx = torch.as_tensor(part, device=device)
-            self.imgs[idx] = ops.resample_u8(raw, self.img_size, out='f32')
+            self.imgs[idx] = ops.resample_u8(raw if self.prepare is None else self.prepare(raw), self.img_size, out='f32')
             if self.raw is not None:
                 self.raw[idx] = raw
                 self.have_raw[part] = True
@@ -220,11 +222,218 @@ class BMVSScene(_Scene):
         return n if self.split == 'train' else min(5 if self.split == 'val' else 10, n)
 
 
+# ---- custom scenes: a transforms.json capture ----------------------------------------------------------------------------------------------
+LENS_COEFFS = ('k1', 'k2', 'k3', 'k4', 'p1', 'p2')
+CAMERA_KEYS = ('fl_x', 'fl_y', 'cx', 'cy', 'w', 'h') + LENS_COEFFS
+TRAIN_SPLIT_FRACTION = 0.9                                                  # Nerfstudio's default split of a capture
+
+
+def lens_source(H, W, intr, dist, zoom, i, j):
+    """The map of csrc/lens_math.h in fp64: the source INDEX coordinates (u, v) of the output pixels (i, j) (arrays) of an H x W frame
+    rectified with the focal lengths zoom * (fx, fy).  intr = (fx, fy, cx, cy), dist = (k1, k2, k3, k4, p1, p2)."""
+    fx, fy, cx, cy = [float(v) for v in intr]
+    k1, k2, k3, k4, p1, p2 = [float(v) for v in dist]
+    x = (np.asarray(j, np.float64) + 0.5 - cx) / (zoom * fx)
+    y = (np.asarray(i, np.float64) + 0.5 - cy) / (zoom * fy)
+    r2 = x * x + y * y
+    d = 1 + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * k4)))
+    xd = x * d + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+    yd = y * d + 2 * p2 * x * y + p1 * (r2 + 2 * y * y)
+    return xd * fx + cx - 0.5, yd * fy + cy - 0.5
+
+
+def lens_zoom(H, W, intr, dist):
+    """The smallest zoom s >= 1 at which every border pixel centre of the rectified H x W frame reads inside the source frame
+    (0 <= u <= W - 1, 0 <= v <= H - 1): no black or smeared border reaches the loss, which has no mask.  1.0 where that holds at s = 1;
+    otherwise [1, 2] is bisected 40 times and the upper end returned.  ValueError where s = 2 does not suffice."""
+    i = np.concatenate([np.zeros(W), np.full(W, H - 1), np.arange(H), np.arange(H)])
+    j = np.concatenate([np.arange(W), np.arange(W), np.zeros(H), np.full(H, W - 1)])
+
+    def inside(s):
+        u, v = lens_source(H, W, intr, dist, s, i, j)
+        return bool(np.all((u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)))           # (False for a NaN)
+
+    if inside(1.0):
+        return 1.0
+    if not inside(2.0):
+        raise ValueError(f'lens_zoom: the border of a {H}x{W} frame leaves the source even at a zoom of 2 (intr={tuple(intr)}, dist={tuple(dist)})')
+    lo, hi = 1.0, 2.0
+    for _ in range(40):
+        mid = 0.5 * (lo + hi)
+        if inside(mid):
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def _rotation_to_z(up):
+    """The Rodrigues rotation that takes the unit vector `up` to (0, 0, 1): the identity where they coincide, a half turn about an axis
+    orthogonal to `up` where they are opposite."""
+    z = np.array([0.0, 0.0, 1.0])
+    v, c = np.cross(up, z), float(up @ z)
+    if c > 1 - 1e-12:
+        return np.eye(3)
+    if c < -1 + 1e-12:
+        a = np.cross(up, np.eye(3)[int(np.argmin(np.abs(up)))])
+        a /= np.linalg.norm(a)
+        return 2 * np.outer(a, a) - np.eye(3)
+    vx = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+    return np.eye(3) + vx + vx @ vx * ((1 - c) / float(v @ v))
+
+
+def normalize_poses(c2w, method='poses'):
+    """(N,4,4) camera-to-world matrices -> (the normalised ones, F): F (4,4) is the similarity from the file's frame to the normalised
+    one, the rigid part applied to the whole matrices and the scale to their translations.  'poses' is Nerfstudio's default recipe: the
+    mean camera up goes to +z, the mean camera position to the origin, the largest |coordinate| of a camera position to 1.  'none': the
+    identity."""
+    c2w = np.array(c2w, dtype=np.float64)
+    F = np.eye(4)
+    if method == 'none':
+        return c2w, F
+    if method != 'poses':
+        raise ValueError(f"normalize: 'poses' or 'none', got {method!r}")
+    up = c2w[:, :3, 1].mean(0)
+    rot = _rotation_to_z(up / np.linalg.norm(up))
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = rot, -rot @ c2w[:, :3, 3].mean(0)
+    c2w = M @ c2w
+    scale = 1.0 / float(np.abs(c2w[:, :3, 3]).max())
+    c2w[:, :3, 3] *= scale
+    F = np.diag([scale, scale, scale, 1.0]) @ M
+    return c2w, F
+
+
+class CustomScene(_Scene):
+    """A capture of one's own: <root>/custom/<tag>/transforms.json -- top-level fl_x, fl_y, cx, cy, w, h, optional k1..k4, p1, p2 and
+    camera_model (OPENCV or PINHOLE; a PINHOLE file's coefficients are not read), and per frame a file_path relative to the json and an
+    OpenGL camera-to-world transform_matrix -- as ns-process-data, instant-ngp exporters and COLMAP converters write it.  Restates
+    src/dataset/nerfstudio.py:35-77 without the `nerfstudio` package, and rectifies the frames on the device (ops.undistort_u8, zoomed so
+    that every pixel is valid: lens_zoom) where the reference trains a pinhole renderer on the distorted ones; undistort=False is the
+    reference's behaviour.  The train split holds ceil(0.9 N) frames spread evenly, test the others (shuffled under the seed len(tag)),
+    val none.  scale_mat: the normalised frame back to the file's; pc_gt: the points of `ply_file_path` or points.ply, normalised."""
+    name, folder = 'custom', 'custom'
+
+    def __init__(self, root, tag, split, downscale_factor=1, img_size=None, undistort=True, normalize='poses', view_ids=None, store=None):
+        import json
+        self.split, self.tag = split, tag
+        self.data_path = Path(root) / self.folder / tag
+        path = self.data_path / 'transforms.json'
+        if not path.exists():
+            raise FileNotFoundError(f'{path.absolute()} does not exist')
+        with open(path) as fp:
+            meta = json.load(fp)
+        frames = meta.get('frames') or []
+        if not frames:
+            raise ValueError(f'{path}: no frames')
+        model = meta.get('camera_model')
+        if model not in (None, 'OPENCV', 'PINHOLE'):
+            raise NotImplementedError(f"{path}: camera_model '{model}' is not supported (OPENCV and PINHOLE are)")
+        cam = {}
+        for k in CAMERA_KEYS:
+            given = [f[k] for f in frames if k in f]
+            if k in meta:
+                cam[k] = meta[k]
+            elif len(given) == len(frames):
+                cam[k] = given[0]
+            elif given or k not in LENS_COEFFS:
+                raise ValueError(f"{path}: '{k}' is neither given at the top level nor on every frame")
+            else:
+                cam[k] = 0.0
+            if any(float(v) != float(cam[k]) for v in given):
+                raise NotImplementedError(f"{path}: per-frame intrinsics differ ('{k}'): the model keeps one K for all views")
+        h, w = int(cam['h']), int(cam['w'])
+        self.raw_img_size = (h, w)
+        self.intr = tuple(float(cam[k]) for k in ('fl_x', 'fl_y', 'cx', 'cy'))
+        self.dist = tuple(0.0 if model == 'PINHOLE' else float(cam[k]) for k in LENS_COEFFS)
+
+        self.input_files = [self._frame_file(path.parent, f['file_path']) for f in frames]
+        from PIL import Image
+        for f in self.input_files:
+            with Image.open(f) as im:
+                if im.size != (w, h):
+                    raise ValueError(f"{f}: {im.size[::-1]}, transforms.json says {(h, w)}")
+        if img_size is not None:
+            self.img_size = (img_size, img_size) if isinstance(img_size, int) else tuple(img_size)
+        else:
+            self.img_size = tuple(round(x / downscale_factor) for x in self.raw_img_size)           # nerfstudio.py:55
+
+        N = len(frames)
+        n_train = int(np.ceil(TRAIN_SPLIT_FRACTION * N))
+        train = np.linspace(0, N - 1, n_train).astype(int).tolist()
+        if split == 'train':
+            self.view_ids = train if view_ids is None else list(deepcopy(view_ids))
+        elif split == 'test':
+            self.view_ids = [i for i in range(N) if i not in set(train)]
+            np.random.RandomState(len(tag)).shuffle(self.view_ids)                                  # nerfstudio.py:46-48
+        else:
+            self.view_ids = []
+
+        rectify = bool(undistort) and any(c != 0 for c in self.dist)
+        self.zoom = lens_zoom(h, w, self.intr, self.dist) if rectify else 1.0
+        intr, dist, zoom = self.intr, self.dist, self.zoom
+        self.prepare = (lambda raw: ops.undistort_u8(raw, intr, dist, zoom)) if rectify else None
+
+        c2w = np.stack([np.asarray(f['transform_matrix'], dtype=np.float64)[:4, :4] for f in frames])
+        if c2w.shape[1] == 3:
+            c2w = np.concatenate([c2w, np.tile(np.array([[[0.0, 0.0, 0.0, 1.0]]]), (N, 1, 1))], 1)
+        parser = path.parent / 'dataparser_transforms.json'
+        if parser.exists():
+            with open(parser) as fp:
+                dp = json.load(fp)
+            M = np.eye(4)
+            M[:3, :4] = np.asarray(dp['transform'], dtype=np.float64)[:3, :4]
+            scale = float(dp.get('scale', 1.0))
+            c2w = M @ c2w
+            c2w[:, :3, 3] *= scale
+            F = np.diag([scale, scale, scale, 1.0]) @ M
+        else:
+            c2w, F = normalize_poses(c2w, normalize)
+        self.cam2world = torch.from_numpy(c2w).float()
+        self.scale_mat = torch.from_numpy(np.linalg.inv(F)).float()
+
+        # nerfstudio.py:59-77
+        wh = np.array([w, h], dtype=np.float64)
+        scale = wh.min() / 2.0
+        p0 = -(np.array(self.intr[2:]) - wh / 2.0) / scale
+        focal = self.zoom * np.array(self.intr[:2]) / scale
+        K = np.array([[focal[0], 0, p0[0], 0], [0, focal[1], p0[1], 0], [0, 0, 0, 1], [0, 0, 1, 0]])
+        self.K = torch.from_numpy(K).float().expand(N, -1, -1)
+        w2c = np.linalg.inv(c2w)
+        flip = np.array([-1.0, 1.0, -1.0])
+        self.R = torch.from_numpy(w2c[:, :3, :3].transpose(0, 2, 1) * flip).float()
+        self.T = torch.from_numpy(w2c[:, :3, 3] * flip).float()
+
+        self.pc_gt = torch.zeros(1, 3)
+        ply = path.parent / meta['ply_file_path'] if meta.get('ply_file_path') else path.parent / 'points.ply'
+        if ply.exists():
+            from .eval3d import read_ply_points
+            points = np.asarray(read_ply_points(ply), dtype=np.float64)
+            self.pc_gt = torch.from_numpy(points @ F[:3, :3].T + F[:3, 3]).float()
+
+        if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size
+                                  or (store.prepare is None) != (self.prepare is None)):
+            raise ValueError('store: made for other files, another img_size or another lens treatment')
+        self.store = store if store is not None else ImageStore(self.input_files, self.img_size, prepare=self.prepare)
+
+    @staticmethod
+    def _frame_file(folder, file_path):
+        f = folder / file_path
+        if f.suffix == '':
+            found = [g for g in (f.with_name(f.name + '.' + e) for e in IMG_EXTENSIONS) if g.exists()]
+            if not found:
+                raise FileNotFoundError(f"{f.absolute()}: no file with one of the extensions {IMG_EXTENSIONS}")
+            return found[0].absolute()
+        if not f.exists():
+            raise FileNotFoundError(f'{f.absolute()} does not exist')
+        return f.absolute()
+
+
 def get_scene_class(name):
     if name == 'nerfstudio':
         raise NotImplementedError("dataset 'nerfstudio': the reference reads these scenes through the `nerfstudio` package, which is not "
                                   'installed here; DTU and BlendedMVS scenes are supported')
-    return {'dtu': DTUScene, 'bmvs': BMVSScene}[name]
+    return {'dtu': DTUScene, 'bmvs': BMVSScene, 'custom': CustomScene}[name]
 
 
 def create_train_val_test(cfg, root, device=None):

@@ -809,6 +809,42 @@ def resample_u8(src_u8, size, out='f32', form='auto'):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# lens rectification (include/dbw_lens.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def lens_params(intr, dist, zoom=1.0):
+    """The HOST `lens` array of dbw_images_undistort_u8, a (12,) fp32 CPU tensor [fx, fy, cx, cy, 1/(zoom fx), 1/(zoom fy), k1, k2, k3, k4, p1, p2], from
+    intr = (fx, fy, cx, cy) in pixels of the source frames and dist = (k1, k2, k3, k4, p1, p2).  The reciprocals are taken in fp64 and
+    rounded once."""
+    intr, dist = [float(v) for v in intr], [float(v) for v in dist]
+    if len(intr) != 4 or len(dist) != 6:
+        raise ValueError(f'intr: (fx, fy, cx, cy), dist: (k1, k2, k3, k4, p1, p2); got {len(intr)} and {len(dist)} values')
+    zoom = float(zoom)
+    if not (zoom > 0 and intr[0] > 0 and intr[1] > 0):
+        raise ValueError(f'zoom and the focal lengths must be positive, got zoom={zoom}, fx={intr[0]}, fy={intr[1]}')
+    return torch.tensor(intr + [1.0 / (zoom * intr[0]), 1.0 / (zoom * intr[1])] + dist, dtype=torch.float64).to(torch.float32)
+
+
+def undistort_u8(raw_u8, intr, dist, zoom=1.0):
+    """dbw_images_undistort_u8: (N,H,W,3) uint8 frames on the GPU, taken through a lens with OpenCV's radial-tangential distortion `dist` =
+    (k1, k2, k3, k4, p1, p2) and the intrinsics `intr` = (fx, fy, cx, cy), -> the (N,H,W,3) uint8 frames of the pinhole camera with the
+    focal lengths zoom * (fx, fy) and the same principal point, bilinear (csrc/lens_math.h).  One map for all N frames."""
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_lens_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no lens rectification entry point (include/dbw_lens.h): rebuild it')
+    src = _chk(raw_u8, torch.uint8, 'raw_u8')
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f'raw_u8: (N,H,W,3), got {tuple(src.shape)}')
+    N, H, W, _ = src.shape
+    if H < 2 or W < 2:
+        raise ValueError(f'frames of {(H, W)}: at least 2 x 2')
+    lens = lens_params(intr, dist, zoom)
+    out = torch.empty_like(src)
+    if N > 0:
+        _lib.call('dbw_images_undistort_u8', _ptr(src), N, H, W, lens.data_ptr(), _ptr(out), _stream(src))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # texture preparation, param -> mesh, losses, optimiser
 # ---------------------------------------------------------------------------------------------------------------------
 class _TexturePrep(torch.autograd.Function):

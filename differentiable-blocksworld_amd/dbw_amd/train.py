@@ -1,7 +1,7 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N] [--lpips-vgg F --lpips-lin F | --no-perceptual]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
-to it, then the file), the scenes of cfg['dataset'] are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
+to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
 saved as <runs-root>/<dataset>/<tag>/model.pkl (Trainer.state_dict) and evaluated by Trainer.evaluate on the test split -- for a DTU scan
 whose evaluation data (ObsMask/, Points/stl/) lies under <data-root>/DTU, the official scores too.
 
@@ -19,7 +19,7 @@ def parse_args(argv=None):
     ap.add_argument('-c', '--config', required=True, help='config file (its default.yml is looked up next to it)')
     ap.add_argument('-d', '--default', default=None, help='default config file, instead of the default.yml next to --config')
     ap.add_argument('-t', '--tag', required=True, help='run tag: the run directory is <runs-root>/<dataset name>/<tag>')
-    ap.add_argument('--data-root', required=True, help='the directory that holds DTU/ and BlendedMVS/')
+    ap.add_argument('--data-root', required=True, help='the directory that holds DTU/, BlendedMVS/ and custom/ (custom/<tag>/transforms.json: a capture of your own)')
     ap.add_argument('--runs-root', required=True)
     ap.add_argument('--epochs', type=int, default=None, help='override training.n_epoches')
     ap.add_argument('--lpips-vgg', default=None, help="state dict of torchvision's vgg16().features (torch.save)")
@@ -73,6 +73,9 @@ def main(argv=None):
     dtu_dir = os.path.join(args.data_root, 'DTU')
     if train.name == 'dtu' and os.path.isdir(os.path.join(dtu_dir, 'ObsMask')) and os.path.isdir(os.path.join(dtu_dir, 'Points', 'stl')):
         dtu = dict(scale_mat=train.scale_mat.to(args.device), scan_id=int(train.tag.replace('scan', '')), dataset_dir=dtu_dir)
+    if len(test) == 0:                          # (a custom capture of fewer than 10 frames: the 0.9 split leaves none out)
+        print(f"the test split of '{train.tag}' is empty: evaluating on the {len(train)} training views")
+        test = train
     scores = trainer.evaluate(test.loader(trainer.batch_size, args.device), run_dir, dtu=dtu)
     print('final_scores: ' + ', '.join(f'{k}={v:.5f}' for k, v in scores.items() if not isinstance(v, dict)))
     return scores
