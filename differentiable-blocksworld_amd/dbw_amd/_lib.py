@@ -227,6 +227,28 @@ def _header_lens_abi_version():
 
 LENS_ABI_VERSION = _header_lens_abi_version()
 
+# the run monitor: name -> argtypes, exactly the int-returning prototypes of include/dbw_monitor.h (checked by tests/test_runlog_host.py);
+# the one size_t-returning entry point next to them.
+MONITOR_SIGNATURES = {
+    'dbw_image_scores': [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    'dbw_meter_add': [c_p, c_p, c_i, c_d, c_i64, c_p],
+    'dbw_meter_reset': [c_p, c_i, c_p],
+}
+MONITOR_OTHER_SIGNATURES = {
+    'dbw_image_scores_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
+}
+METER_MAX_VALUES = 16                                         # DBW_METER_MAX_VALUES of include/dbw_monitor.h
+
+
+def _header_monitor_abi_version():
+    """DBW_MONITOR_ABI_VERSION of include/dbw_monitor.h (dbw_monitor_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_monitor.h')) as f:
+        return int(re.search(r'#define DBW_MONITOR_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+MONITOR_ABI_VERSION = _header_monitor_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -305,6 +327,15 @@ def load():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = c_i
+    if hasattr(lib, 'dbw_monitor_abi_version'):  # (absent from tuning builds of older sources: ops.image_scores / runlog refuse to run on them)
+        lib.dbw_monitor_abi_version.restype = c_i
+        for name, argtypes in MONITOR_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
+        for name, (restype, argtypes) in MONITOR_OTHER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 

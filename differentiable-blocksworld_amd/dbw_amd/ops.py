@@ -750,6 +750,58 @@ def frames_u8(src, bkg=None, mask=None, edge_color=None, hwc=False, edge_first=F
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# run monitor (include/dbw_monitor.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def _monitor_lib():
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_monitor_abi_version'):
+        raise RuntimeError('the loaded libdbw_hip.so has no run monitor entry points (include/dbw_monitor.h): rebuild it')
+    return lib
+
+
+def image_score_sums(a, b, padding=False, return_map=False):
+    """dbw_image_scores as it stands: a, b (N,3,H,W) fp32 on the GPU -> out (N,2) fp64 on the GPU, [sum (a - b)^2, sum of the SSIM map] per
+    image (and the (N,3,H',W') map with return_map).  Two launches on the current stream, no host read."""
+    lib = _monitor_lib()
+    a_c, b_c = _chk(a, torch.float32, 'a'), _chk(b, torch.float32, 'b')
+    if a_c.dim() != 4 or a_c.shape[1] != 3 or a_c.shape != b_c.shape:
+        raise ValueError(f'a, b: two (N,3,H,W) tensors, got {tuple(a_c.shape)} and {tuple(b_c.shape)}')
+    N, _, H, W = a_c.shape
+    if not padding and (H < 11 or W < 11):
+        raise ValueError(f'images of {(H, W)} hold no 11 x 11 window: SSIM without padding needs H >= 11 and W >= 11')
+    Hp, Wp = (H, W) if padding else (H - 10, W - 10)
+    dev = a_c.device
+    out = torch.empty(N, 2, dtype=torch.float64, device=dev)
+    ssim_map = torch.empty(N, 3, Hp, Wp, dtype=torch.float32, device=dev) if return_map else None
+    if N > 0:
+        ws = torch.empty(lib.dbw_image_scores_workspace_bytes(N, H, W, int(bool(padding))) // 8, dtype=torch.float64, device=dev)
+        _lib.call('dbw_image_scores', _ptr(a_c), _ptr(b_c), N, H, W, int(bool(padding)), _ptr(ws), _ptr(ssim_map), _ptr(out), _stream(a_c))
+    return (out, ssim_map) if return_map else out
+
+
+def image_scores(a, b, padding=False, return_map=False):
+    """Mean squared error and mean SSIM per image of a against b, (N,3,H,W) fp32 in [0, 1] -> (mse (N,), ssim (N,)) fp64 on the device of
+    the inputs (and the (N,3,H',W') SSIM map with return_map); padding=False keeps the windows inside the image, as the evaluation does.
+    On the GPU one dbw_image_scores; CPU tensors go through metrics.ssim_map."""
+    if not a.is_cuda:
+        from .metrics import ssim_map as _ssim_map
+        if a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape:
+            raise ValueError(f'a, b: two (N,3,H,W) tensors, got {tuple(a.shape)} and {tuple(b.shape)}')
+        if not padding and (a.shape[2] < 11 or a.shape[3] < 11):
+            raise ValueError(f'images of {tuple(a.shape[2:])} hold no 11 x 11 window: SSIM without padding needs H >= 11 and W >= 11')
+        m = _ssim_map(a.float(), b.float(), padding=bool(padding))
+        mse = ((a.double() - b.double()) ** 2).flatten(1).mean(1)
+        res = (mse, m.double().flatten(1).mean(1))
+        return res + (m,) if return_map else res
+    r = image_score_sums(a, b, padding, return_map)
+    out, m = r if return_map else (r, None)
+    H, W = a.shape[2:]
+    Hp, Wp = (H, W) if padding else (H - 10, W - 10)
+    res = (out[:, 0] / (3 * H * W), out[:, 1] / (3 * Hp * Wp))
+    return res + (m,) if return_map else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # image ingest (include/dbw_ingest.h)
 # ---------------------------------------------------------------------------------------------------------------------
 _RESAMPLE_TABLES = {}

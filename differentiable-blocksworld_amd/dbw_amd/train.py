@@ -1,9 +1,15 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N] [--lpips-vgg F --lpips-lin F | --no-perceptual]
+                          [--resume [TAG]] [--no-record]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
 saved as <runs-root>/<dataset>/<tag>/model.pkl (Trainer.state_dict) and evaluated by Trainer.evaluate on the test split -- for a DTU scan
 whose evaluation data (ObsMask/, Points/stl/) lies under <data-root>/DTU, the official scores too.
+
+The run is recorded as the reference records it (runlog.RunRecorder: train_metrics.tsv, val_metrics.tsv with the scores of the validation
+split, the image logs, model.pkl at every validation tick, model_<epoch>.pkl at training.save_epoches); --no-record trains without and
+writes model.pkl at the end only.  training.resume: TAG (or --resume [TAG], default: this run's tag) continues the run of
+<runs-root>/<dataset>/<TAG>/model.pkl where it stopped; training.pretrained: TAG starts from that run's weights.
 
 The perceptual term needs the weights of a VGG16 and of the LPIPS heads, which do not ship with the package: a config with
 perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so)."""
@@ -25,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument('--lpips-vgg', default=None, help="state dict of torchvision's vgg16().features (torch.save)")
     ap.add_argument('--lpips-lin', default=None, help="state dict with lpips' lin{k}.model.1.weight tensors (torch.save)")
     ap.add_argument('--no-perceptual', action='store_true', help='train without the perceptual term')
+    ap.add_argument('--resume', nargs='?', const=True, default=None, metavar='TAG', help="continue the run TAG of this dataset (default: --tag's own run)")
+    ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
     ap.add_argument('--device', default='cuda:0')
     return ap.parse_args(argv)
 
@@ -51,9 +59,17 @@ def main(argv=None):
     cfg = prepare_config(args)
     from . import create_model
     from .dataset import create_train_val_test
+    from .runlog import RunRecorder, resolve_start
     from .trainer import Trainer
     run_dir = os.path.join(args.runs_root, cfg['dataset']['name'], args.tag)
     os.makedirs(run_dir, exist_ok=True)
+    resume, pretrained = resolve_start(cfg['training'], args.tag, args.resume)
+    start = {}
+    for key, tag in (('resume', resume), ('pretrained', pretrained)):
+        if tag is not None:
+            start[key] = os.path.join(args.runs_root, cfg['dataset']['name'], str(tag), 'model.pkl')
+            if not os.path.exists(start[key]):
+                raise SystemExit(f'training.{key} = {tag}: {start[key]} does not exist')
     seed = cfg['training'].get('seed', 4321)
     torch.manual_seed(seed)
     train, val, test = create_train_val_test(cfg, args.data_root, args.device)
@@ -65,10 +81,21 @@ def main(argv=None):
         model.set_perceptual(net.to(args.device))
     trainer = Trainer(cfg, model, train.views(args.device))
     print(f'Trainer init: config_file={args.config}, run_dir={run_dir}, n_epoches={trainer.n_epoches}')
+    if args.no_record:
+        if 'resume' in start:                   # (a recorded run's model.pkl may stop inside an epoch: the position and the schedule are the recorder's to read)
+            from .runlog import load_checkpoint
+            pos = load_checkpoint(trainer, torch.load(start['resume'], map_location=args.device, weights_only=False))
+            print(f'Training state: epoch={pos[0]}, batch={pos[1]}, lr={trainer.step_fn.lrs[0]}')
+        elif 'pretrained' in start:
+            model.load_state_dict(torch.load(start['pretrained'], map_location=args.device, weights_only=False)['model_state'])
+    else:
+        rec = RunRecorder(trainer, run_dir, val=val.loader(trainer.batch_size, args.device) if len(val) else None, **start)
+        print(f'Training state: epoch={rec.epoch_start}, batch={rec.batch_start}, lr={trainer.step_fn.lrs[0]}')
     last = trainer.run()
     if last is not None:
         print('last step: ' + ', '.join(f'{k}={float(v):.5f}' for k, v in last.items()))
-    torch.save(trainer.state_dict(), os.path.join(run_dir, 'model.pkl'))
+    if args.no_record:                          # (a recorded run wrote it, with the state a resume needs)
+        torch.save(trainer.state_dict(), os.path.join(run_dir, 'model.pkl'))
     dtu = None
     dtu_dir = os.path.join(args.data_root, 'DTU')
     if train.name == 'dtu' and os.path.isdir(os.path.join(dtu_dir, 'ObsMask')) and os.path.isdir(os.path.join(dtu_dir, 'Points', 'stl')):

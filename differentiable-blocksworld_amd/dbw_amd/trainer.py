@@ -2,8 +2,9 @@
 checkpointing with the semantics of the reference's src/scheduler.py:26-69, src/optimizer.py:6-18 and
 src/trainer.py:109-169,201-209, driving `ShardedTrainStep` (flat parameter buffer, fused Adam, optional RCCL all-reduce).
 
-Host-side scalars only; nothing here touches pixels.  No logging / visualisation plumbing (out of scope); `evaluate` ends a run like
-the reference's trainer.py:241-272."""
+Host-side scalars only; nothing here touches pixels.  The record of a run -- metric files, image logs, checkpoints, resuming -- is
+runlog.RunRecorder's, which this loop calls when one is attached (`trainer.recorder`); without one the loop is what it was.  `evaluate`
+ends a run like the reference's trainer.py:241-272."""
 import time
 from collections import Counter
 
@@ -79,7 +80,9 @@ class Trainer:
         sch = dict(tr.get('scheduler') or {})
         if sch.pop('name', 'multi_step') != 'multi_step':
             raise NotImplementedError('only the multi_step scheduler')
-        self.model, self.views = model, views
+        self.cfg, self.model, self.views = cfg, model, views
+        self.recorder = None                # runlog.RunRecorder attaches itself here
+        self._resume_pos = None             # (view order, batches done) of an epoch a resumed run re-enters: set by the recorder
         model.sync_free = sync_free
         self.step_fn = ShardedTrainStep(model, lr=lr, lr_texture=lr_txt, betas=opt.pop('betas', (0.9, 0.999)), eps=opt.pop('eps', 1e-8),
                                         process_group=process_group, seed=tr.get('seed'))
@@ -124,9 +127,16 @@ class Trainer:
 
     def run_epoch(self, shuffle=True):
         """One pass over this rank's views in mini-batches (DataLoader(shuffle=True) equivalent), then the per-epoch
-        scheduler / model step (trainer.py:127,163-169)."""
+        scheduler / model step (trainer.py:127,163-169).  A run resumed inside an epoch walks the rest of that epoch's order."""
         V = self.local['imgs'].shape[0]
-        order = torch.randperm(V, generator=self._perm_gen) if shuffle else torch.arange(V)
+        first = 0
+        if self._resume_pos is not None:
+            (order, first), self._resume_pos = self._resume_pos, None
+        else:
+            order = torch.randperm(V, generator=self._perm_gen) if shuffle else torch.arange(V)
+        rec = self.recorder
+        if rec is not None:
+            rec.begin_epoch(order)
         if self.view_ids:
             # the criterion is shared by whoever holds the model: if its cache is not (or no longer) the one of THESE views -- new weights,
             # another Trainer on other views -- the ids would index foreign features; built again (a forward pass over the views, once)
@@ -138,13 +148,16 @@ class Trainer:
         # Uneven shards (49 views over 8 ranks: 7,6,...,6; batch 4 -> two steps everywhere, the second of sizes 3,2,...,2): all ranks
         # run n_batches steps -- a rank that has run out of views steps on an EMPTY batch (regularisers only) -- so that the
         # sequence of collectives is the same everywhere, and the MSE normalisation of a step is the size of its global batch
-        for b in range(self.n_batches):
-            idx = order[b * self.batch_size:(b + 1) * self.batch_size].to(self.local['imgs'].device)
+        for b in range(first, self.n_batches):
+            ids = order[b * self.batch_size:(b + 1) * self.batch_size]
+            idx = ids.to(self.local['imgs'].device)
             batch = {k: v[idx] for k, v in self.local.items()}
             if self.view_ids:
                 batch['view_ids'] = idx
             last, _ = self.run_single_batch_train(batch, self.global_count(b))
             n_img += idx.numel()
+            if rec is not None:
+                rec.after_step(self.epoch, b + 1, last, ids)
         if self.local['imgs'].is_cuda:
             torch.cuda.synchronize()
         self.time_per_img = (time.time() - t_start) / max(n_img, 1)
@@ -154,12 +167,28 @@ class Trainer:
         opac = self.model.get_opacities()
         if (opac > 0.01).sum() == 0:
             raise RuntimeError('No more blocks....')                   # trainer.py:152-154
+        if rec is not None:
+            rec.after_epoch(self.epoch - 1)
         return last
 
     def run(self, n_epoches=None):
         last = None
-        for _ in range(self.epoch, (n_epoches or self.n_epoches) + 1):
-            last = self.run_epoch()
+        rec = self.recorder
+        if rec is None:
+            for _ in range(self.epoch, (n_epoches or self.n_epoches) + 1):
+                last = self.run_epoch()
+            return last
+        try:
+            rec.begin_run()
+            for _ in range(self.epoch, (n_epoches or self.n_epoches) + 1):
+                last = self.run_epoch()
+            rec.finish()
+        except BaseException:
+            try:                            # the writer threads end with the run, however it ends -- and the run's own error is the one raised
+                rec.close()
+            except Exception:
+                pass
+            raise
         return last
 
     # trainer.py:241-272

@@ -1,0 +1,58 @@
+/*
+ * dbw_monitor.h -- C ABI of the run monitor of libdbw_hip.so: what a training run records between two host reads.  Image scores (squared
+ * error and SSIM of rendered against held-out views, the reference's mse2psnr / SSIMLoss, src/model/loss.py:28-29,124-156) in one kernel per
+ * batch, and a table of running loss sums that the step's device scalars are added to without the host reading them (the reference calls
+ * .item() on every loss after every step, src/trainer.py:143).
+ * Python side: dbw_amd/ops.py (image_scores) and dbw_amd/runlog.py (DeviceMeter), bound through _lib.MONITOR_SIGNATURES.  The arithmetic is
+ * csrc/score_math.h.
+ *
+ * Conventions are those of dbw_hip.h: DEVICE pointers owned by the caller, contiguous, unless said otherwise; return 0 or a negative
+ * DBW_ERR_*, the text in dbw_last_error(); arguments are validated before any launch; kernels are enqueued on `stream`, no host
+ * synchronisation.
+ */
+#ifndef DBW_MONITOR_H
+#define DBW_MONITOR_H
+#include "dbw_hip.h"
+
+/* ABI revision of this header (dbw_monitor_abi_version() returns the value the library was built with). */
+#define DBW_MONITOR_ABI_VERSION 1
+
+#define DBW_METER_MAX_VALUES 16 /* values per dbw_meter_add */
+#define DBW_SSIM_WINDOW 11      /* taps of the Gaussian window (sigma 1.5) */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int dbw_monitor_abi_version(void);
+
+/* Bytes of `workspace` that dbw_image_scores needs for these sizes (one fp64 pair per workgroup); 0 for sizes it refuses. */
+size_t dbw_image_scores_workspace_bytes(int N, int H, int W, int padding);
+
+/* a, b (N,3,H,W) fp32 -> out (N,2) fp64:
+ *   out[n][0] = sum over the 3*H*W elements of (a - b)^2, difference and square taken in fp64;
+ *   out[n][1] = sum over the 3*H'*W' elements of the SSIM map of image n.
+ * SSIM: 11 taps, sigma 1.5, the weights computed in fp64, normalised and rounded to fp32; rows filtered first, then columns, in fp32; the
+ * five statistics a, b, a*a, b*b, a*b; C1 = 0.01^2, C2 = 0.03^2.  Each 11-tap filter is a COMPENSATED dot product (Dot2: an fmaf gives every
+ * product's rounding error, a two-sum every partial sum's; csrc/score_math.h), i.e. the dot product rounded once -- not the left-to-right
+ * separable sum a convolution makes: against dbw_amd.metrics.ssim_map the map differs in the last bits (about 1e-6 per pixel on noise, up
+ * to 5e-4 where flat regions cancel in E[x^2] - mu^2), and is the closer of the two to the fp64 definition.  padding = 0 keeps the windows that lie inside
+ * the image, H' = H - 10, W' = W - 10 (H < 11 or W < 11: DBW_ERR_INVALID); padding = 1 pads with zeros, H' = H, W' = W.
+ * ssim_map, when not NULL: (N,3,H',W') fp32, receives the map.  workspace: dbw_image_scores_workspace_bytes(...) bytes, 8-byte aligned.
+ * No atomics: the partial sums of an image are added in index order, two calls on the same inputs give the same bits.  Rows whose W is a
+ * multiple of 4 and whose a / b are 16-byte aligned are read as 16-byte loads; any other shape element by element, same results. */
+int dbw_image_scores(const float *a, const float *b, int N, int H, int W, int padding, void *workspace, float *ssim_map, double *out,
+                     dbw_stream_t stream);
+
+/* table: n + 2 doubles on the device; vals: HOST array of n <= DBW_METER_MAX_VALUES DEVICE pointers, each to one fp32.  One kernel:
+ *   table[i] += (double)*vals[i] * weight  (i < n),   table[n] += weight,
+ *   table[n + 1] = step if it is negative and any *vals[i] is not finite (the first such step stays). */
+int dbw_meter_add(double *table, const float *const *vals, int n, double weight, int64_t step, dbw_stream_t stream);
+
+/* table[0 .. n] = 0, table[n + 1] = -1. */
+int dbw_meter_reset(double *table, int n, dbw_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
