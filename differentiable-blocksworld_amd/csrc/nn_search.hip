@@ -11,6 +11,7 @@
 // (dist2, idx) and the merge is exact and independent of the order of arrival.
 #include "dbw_common.h"
 #include "nn_math.h"
+#include "nn_search.h"
 #include "../../include/dbw_eval.h"
 
 #include <math.h>
@@ -166,12 +167,7 @@ __global__ void radius_round_kernel(const double *__restrict__ pts, const int64_
 
 extern "C" int dbw_eval_abi_version(void) { return DBW_EVAL_ABI_VERSION; }      // (history: include/dbw_eval.h)
 
-extern "C" int dbw_nn_points(const float *x, const float *y, const int64_t *x_lengths, const int64_t *y_lengths, int N, int P1, int P2,
-                             int splits, void *keys, float *dist2, int64_t *idx, dbw_stream_t stream) {
-    DBW_REQUIRE(x && y && keys && dist2 && idx, "null pointer");
-    DBW_REQUIRE(N > 0 && P1 > 0 && P2 > 0 && splits >= 0, "bad size");
-    DBW_REQUIRE((long long)N * P1 < (1ll << 40) && (long long)P1 * 3 < (1ll << 40), "too large");
-    const hipStream_t st = (hipStream_t)stream;
+int dbw_nn_search_plan(const char *caller, int N, int P1, int P2, int splits) {
     const long long bx = (P1 + NN_BLOCK * NN_Q - 1) / (NN_BLOCK * NN_Q);
     if (splits == 0) {
         // at most as many workgroups as the chip holds at once (CUs x resident workgroups per CU): one round, no partial second one;
@@ -191,15 +187,35 @@ extern "C" int dbw_nn_points(const float *x, const float *y, const int64_t *x_le
         if (splits < 1) splits = 1;
     }
     if (splits > P2) splits = P2;
-    DBW_REQUIRE(bx * splits < (1ll << 31) && N < 65536 && splits < 65536, "grid too large");
+    if (!(bx * splits < (1ll << 31) && N < 65536 && splits < 65536)) {      // (DBW_REQUIRE's text, under the entry point's name)
+        dbw_set_error("%s: %s", caller, "grid too large");
+        return DBW_ERR_INVALID;
+    }
+    return splits;
+}
+
+int dbw_nn_search_launch(const float *x, const float *y, const int64_t *x_lengths, const int64_t *y_lengths, int N, int P1, int P2,
+                         int splits, void *keys, hipStream_t st) {
+    const long long bx = (P1 + NN_BLOCK * NN_Q - 1) / (NN_BLOCK * NN_Q);
     const int chunk = (int)((P2 + splits - 1) / splits);
     if (hipMemsetAsync(keys, 0xff, (size_t)N * P1 * sizeof(unsigned long long), st) != hipSuccess) {
-        dbw_set_error("dbw_nn_points: hipMemsetAsync failed");
+        dbw_set_error("nearest-neighbour search: hipMemsetAsync failed");
         return DBW_ERR_LAUNCH;
     }
     hipLaunchKernelGGL(nn_search_kernel, dim3((unsigned)bx, (unsigned)splits, (unsigned)N), dim3(NN_BLOCK), 0, st, x, y, x_lengths,
                        y_lengths, P1, P2, chunk, splits > 1 ? 1 : 0, (unsigned long long *)keys);
-    int rc = dbw_check_launch("nn_search_kernel");
+    return dbw_check_launch("nn_search_kernel");
+}
+
+extern "C" int dbw_nn_points(const float *x, const float *y, const int64_t *x_lengths, const int64_t *y_lengths, int N, int P1, int P2,
+                             int splits, void *keys, float *dist2, int64_t *idx, dbw_stream_t stream) {
+    DBW_REQUIRE(x && y && keys && dist2 && idx, "null pointer");
+    DBW_REQUIRE(N > 0 && P1 > 0 && P2 > 0 && splits >= 0, "bad size");
+    DBW_REQUIRE((long long)N * P1 < (1ll << 40) && (long long)P1 * 3 < (1ll << 40), "too large");
+    const hipStream_t st = (hipStream_t)stream;
+    splits = dbw_nn_search_plan(__func__, N, P1, P2, splits);
+    if (splits < 0) return splits;
+    int rc = dbw_nn_search_launch(x, y, x_lengths, y_lengths, N, P1, P2, splits, keys, st);
     if (rc) return rc;
     const long long tot = (long long)N * P1;
     hipLaunchKernelGGL(nn_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const unsigned long long *)keys,

@@ -249,6 +249,26 @@ def _header_monitor_abi_version():
 
 MONITOR_ABI_VERSION = _header_monitor_abi_version()
 
+# the gradient ICP: name -> argtypes, exactly the int-returning prototypes of include/dbw_icp.h (checked by tests/test_icp_host.py); the one
+# size_t-returning entry point next to them.
+ICP_SIGNATURES = {
+    'dbw_icp_run': [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_d, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+}
+ICP_OTHER_SIGNATURES = {
+    'dbw_icp_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
+}
+ICP_TRACE_PER_INSTANCE = 15                                   # DBW_ICP_TRACE_PER_INSTANCE of include/dbw_icp.h
+
+
+def _header_icp_abi_version():
+    """DBW_ICP_ABI_VERSION of include/dbw_icp.h (dbw_icp_abi_version() of the library is compared with it)."""
+    import re
+    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_icp.h')) as f:
+        return int(re.search(r'#define DBW_ICP_ABI_VERSION (\d+)', f.read()).group(1))
+
+
+ICP_ABI_VERSION = _header_icp_abi_version()
+
 
 def load():
     """Load (building in-tree with hipcc if the .so is absent or stale and hipcc exists)."""
@@ -334,6 +354,15 @@ def load():
             fn.argtypes = argtypes
             fn.restype = c_i
         for name, (restype, argtypes) in MONITOR_OTHER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
+    if hasattr(lib, 'dbw_icp_abi_version'):      # (absent from tuning builds of older sources: eval3d.icp_run refuses to run on them)
+        lib.dbw_icp_abi_version.restype = c_i
+        for name, argtypes in ICP_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = c_i
+        for name, (restype, argtypes) in ICP_OTHER_SIGNATURES.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

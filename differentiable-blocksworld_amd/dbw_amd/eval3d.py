@@ -11,6 +11,10 @@ nearest neighbours, the DTU dense lattice and its radius downsample -- is HIP (c
     dtu_scores(v, f, obs_mask, ...)       dtu_eval.py:47-160 on arrays                                 -> dict(acc, comp, avg, counts)
     evaluate_mesh(v, f, scan_id, ...)     dtu_eval.py:47-164 on a DTU directory, writes dtu_scores{suffix}.tsv
     evaluate_dtu(model, scale_mat, ...)   trainer.py:255-264: the live blocks of a model, scaled by scale_mat, evaluated
+    gradient_icp(pc_pred, pc_gt, ...)     utils/icp.py:11-78, the whole loop in one call (include/dbw_icp.h) -> (upd_pc_pred, [R, T, s])
+    gradient_icp_torch(...)               the same loop in torch, any device and dtype: the CPU path and the yardstick of the GPU tests
+    normalize_mesh(verts, faces, ...)     utils/mesh.py:25-44 for one mesh                             -> (verts, faces)
+    evaluate_aligned(model, points, ...)  the ICP-aligned scores (metrics.MeshEvaluator) of a model's live blocks, aligned_scores.tsv
 """
 import ctypes
 import math
@@ -518,3 +522,200 @@ def evaluate_dtu(model, scale_mat, scan_id, dataset_dir, eval_dir, suffix='', se
     scale = torch.as_tensor(scale_mat).to(device=verts.device, dtype=verts.dtype)
     verts = verts @ scale[:3, :3] + scale[:3, 3]
     return evaluate_mesh(verts, faces, scan_id, dataset_dir, eval_dir, suffix=suffix, seed=seed, device=verts.device)
+
+
+# ------------------------------------------------------------------------------------------------ ICP-aligned evaluation
+def normalize_mesh(verts, faces, center=True, scale_mode='unit_cube', use_center_mass=False):
+    """utils/mesh.py:25-44 for one mesh (verts (V,3), faces (F,3)) -> (verts, faces): centred on the middle of its bounding box, then scaled
+    to fit [-0.5, 0.5]^3 ('unit_cube'), the sphere of diameter 1 ('unit_sphere') or not at all ('none' / None).  `use_center_mass` (the mean
+    of 100 000 random surface samples in the reference) is refused: it makes the frame depend on the random draw."""
+    if use_center_mass:
+        raise NotImplementedError('normalize_mesh: use_center_mass draws random samples to centre the mesh; only the bounding-box centre is built')
+    if center:
+        verts = verts - 0.5 * (verts.max(0).values + verts.min(0).values)
+    if scale_mode == 'none' or scale_mode is None:
+        return verts, faces
+    if scale_mode == 'unit_cube':
+        scale = verts.abs().max() * 2
+    elif scale_mode == 'unit_sphere':
+        scale = verts.norm(dim=1).max() * 2
+    else:
+        raise NotImplementedError(f'normalize_mesh: scale_mode {scale_mode!r}')
+    return verts * (1 / scale), faces
+
+
+def keep_best_history(losses, N=1):
+    """The keep-best rule of icp.py:27-28,65-74 on a loss history (csrc/icp_math.h states it for the device) -> (best_loss, best_iter,
+    checks): checks = [(iteration, meter average, kept)] for every iteration with it % 10 == 0; best_iter -1 and best_loss 1e6 if no check
+    ever beat 1e6."""
+    loss_min, best, acc, cnt, checks = 1e6, -1, 0.0, 0, []
+    for it, loss in enumerate(losses):
+        acc += float(loss) * N
+        cnt += N
+        if it % 10 == 0:
+            avg = acc / cnt
+            if avg < loss_min:
+                loss_min, best = avg, it
+            checks.append((it, avg, best == it))
+            acc, cnt = 0.0, 0
+    return loss_min, best, checks
+
+
+def _print_checks(trace, N):
+    for _, avg, kept in keep_best_history(trace['loss'].tolist(), N)[2]:      # what icp.py prints with verbose=True
+        print(avg, 'save checkpoint') if kept else print(avg)
+
+
+def gradient_icp_torch(pc_pred, pc_gt, estimate_scale=True, anisotropic_scale=False, lr=0.01, n_iter=300, verbose=False,
+                       return_trace=False):
+    """The per-instance loop of utils/icp.py:59-78 in torch, on any device and in the dtype of pc_pred: chamfer_distance (its searches run
+    on the HIP kernel for device tensors), mesh.rotation_6d_to_matrix, torch.optim.Adam, a host read of the loss per iteration.
+    -> (upd_pc_pred, [Rf (N,3,3), Tf (N,3), sf (N,3) or (N,1)]) [, trace].  The kept parameters are COPIES taken at the check (the
+    reference keeps `T.detach()` / `s.detach()`, views that Adam goes on updating in place, so it returns the kept R with the LAST T and s
+    whenever n_iter - 1 is not a kept check; that is not restated)."""
+    from .mesh import rotation_6d_to_matrix
+    if pc_pred.dim() != 3 or pc_gt.dim() != 3 or len(pc_pred) != len(pc_gt):
+        raise ValueError('expected points to be of shape (N, P, D), with the same N')
+    dev, dt, N = pc_pred.device, pc_pred.dtype, len(pc_pred)
+    pc_pred, pc_gt = pc_pred.detach(), pc_gt.detach().to(dt)
+    with torch.enable_grad():
+        R6 = torch.nn.Parameter(torch.tensor([[1., 0., 0., 0., 1., 0.]], dtype=dt, device=dev).repeat(N, 1))
+        T = torch.nn.Parameter(torch.zeros(N, 3, dtype=dt, device=dev))
+        if estimate_scale:
+            s = torch.nn.Parameter(torch.ones(N, 3 if anisotropic_scale else 1, dtype=dt, device=dev))
+            params = [R6, T, s]
+        else:
+            s = torch.ones(N, 3, dtype=dt, device=dev)
+            params = [R6, T]
+        snap = lambda: [rotation_6d_to_matrix(R6).detach().clone(), T.detach().clone(), s.detach().clone()]      # noqa: E731
+        argmin, losses, hist = snap(), [], []
+        loss_min, best, acc, cnt = 1e6, -1, 0.0, 0
+        opt = torch.optim.Adam(params, lr=lr)
+        for it in range(n_iter):
+            opt.zero_grad()
+            loss = chamfer_distance(s[:, None] * pc_pred @ rotation_6d_to_matrix(R6) + T[:, None], pc_gt)[0]
+            loss.backward()
+            opt.step()
+            losses.append(loss.item())
+            acc += losses[-1] * N
+            cnt += N
+            if return_trace:
+                hist.append(snap())
+            if it % 10 == 0:
+                if acc / cnt < loss_min:
+                    loss_min, best, argmin = acc / cnt, it, snap()
+                acc, cnt = 0.0, 0
+    Rf, Tf, sf = argmin
+    upd = sf[:, None] * pc_pred @ Rf + Tf[:, None]
+    trace = dict(loss=torch.tensor(losses, dtype=torch.float64), best_loss=loss_min, best_iter=best)
+    if return_trace:
+        for k, name in enumerate('RTs'):
+            trace[name] = torch.stack([h[k] for h in hist]) if hist else torch.zeros((0,) + argmin[k].shape, dtype=dt, device=dev)
+    if verbose:
+        _print_checks(trace, N)
+    return (upd, [Rf, Tf, sf], trace) if return_trace else (upd, [Rf, Tf, sf])
+
+
+def _icp_call(name, *args):
+    lib = _lib.load()
+    if not hasattr(lib, 'dbw_icp_abi_version'):
+        raise RuntimeError(f'{_lib.LIB_PATH} has no gradient ICP entry points (include/dbw_icp.h): rebuild it')
+    if lib.dbw_icp_abi_version() != _lib.ICP_ABI_VERSION:
+        raise RuntimeError(f'the library was built for ICP ABI {lib.dbw_icp_abi_version()}, include/dbw_icp.h declares '
+                           f'{_lib.ICP_ABI_VERSION}: rebuild it')
+    if name == 'dbw_icp_workspace_bytes':
+        return lib.dbw_icp_workspace_bytes(*args)
+    _lib.call(name, *args)
+
+
+def icp_run(pc_pred, pc_gt, estimate_scale=True, anisotropic_scale=False, lr=0.01, n_iter=300, splits=0, with_trace=False):
+    """dbw_icp_run on device tensors pc_pred (N,P1,3), pc_gt (N,P2,3): the whole alignment enqueued by one call, nothing read by the host
+    -> dict(cloud (N,P1,3), R (N,3,3), T (N,3), s (N,3), best (2,) fp64 = [kept loss average, kept iteration], trace (n_iter, 1 + 15 N)
+    fp64 or None), all on the device, fp32 unless said.  `splits`: as in nn_points; the result does not depend on it."""
+    if pc_pred.dim() != 3 or pc_gt.dim() != 3 or pc_pred.shape[2] != 3 or pc_gt.shape[2] != 3 or len(pc_pred) != len(pc_gt):
+        raise ValueError(f'icp_run: pc_pred (N,P1,3) and pc_gt (N,P2,3) expected, got {tuple(pc_pred.shape)} and {tuple(pc_gt.shape)}')
+    if pc_pred.device.type != 'cuda' or pc_gt.device != pc_pred.device:
+        raise ValueError('icp_run: both clouds must be on the same cuda device (CPU tensors: gradient_icp_torch)')
+    N, P1, _ = pc_pred.shape
+    P2 = pc_gt.shape[1]
+    dev = pc_pred.device
+    p = pc_pred.detach().to(torch.float32).contiguous()
+    g = pc_gt.detach().to(torch.float32).contiguous()
+    n_iter = int(n_iter)
+    nbytes = _icp_call('dbw_icp_workspace_bytes', N, P1, P2, n_iter)
+    if nbytes == 0:
+        raise ValueError(f'icp_run: sizes N={N}, P1={P1}, P2={P2}, n_iter={n_iter} are refused (empty clouds, or too large)')
+    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    out = dict(cloud=torch.empty_like(p), R=torch.empty(N, 3, 3, dtype=torch.float32, device=dev),
+               T=torch.empty(N, 3, dtype=torch.float32, device=dev), s=torch.empty(N, 3, dtype=torch.float32, device=dev),
+               best=torch.empty(2, dtype=torch.float64, device=dev),
+               trace=torch.empty(n_iter, 1 + _lib.ICP_TRACE_PER_INSTANCE * N, dtype=torch.float64, device=dev) if with_trace else None)
+    with torch.cuda.device(dev):
+        _icp_call('dbw_icp_run', _p(p), _p(g), N, P1, P2, int(bool(estimate_scale)), int(bool(anisotropic_scale)), float(lr), n_iter, int(splits),
+                  _p(ws), _p(out['cloud']), _p(out['R']), _p(out['T']), _p(out['s']), _p(out['best']),
+                  _p(out['trace']) if with_trace and n_iter else ctypes.c_void_p(0), _stream(dev))
+    return out
+
+
+def gradient_icp(pc_pred, pc_gt, estimate_scale=True, anisotropic_scale=False, lr=0.01, n_iter=300, batch_size=None, shared_params=False,
+                 verbose=False, return_trace=False):
+    """utils/icp.py:11-78: aligns pc_pred (N,P1,3) to pc_gt (N,P2,3) by minimising the Chamfer distance over a rotation, a translation and
+    a scale per instance with Adam, keeping the best check of every 10th iteration -> (upd_pc_pred, [Rf (N,3,3), Tf (N,3), sf]) with
+    upd_pc_pred = sf[:, None] * pc_pred @ Rf + Tf[:, None]; sf is (N,1) for an isotropic scale, (N,3) otherwise.  return_trace=True appends a
+    dict: loss (n_iter,) fp64, R / T / s after every iteration's step, best_loss, best_iter.
+
+    Device tensors run the loop behind one call (icp_run), CPU tensors gradient_icp_torch.  The mini-batch variant (`batch_size`) and
+    `shared_params=True` (one transform for all instances, which the mini-batches need) are not built: the evaluator uses neither."""
+    if batch_size is not None or shared_params:
+        raise NotImplementedError('gradient_icp: batch_size / shared_params=True (the mini-batch ICP with one transform shared by all instances, '
+                                  'icp.py:30-57) is not built: MeshEvaluator aligns every instance on its own with full clouds')
+    if pc_pred.dim() != 3 or pc_gt.dim() != 3 or len(pc_pred) != len(pc_gt):
+        raise ValueError('expected points to be of shape (N, P, D), with the same N')
+    if pc_pred.device.type == 'cpu' and pc_gt.device.type == 'cpu':
+        return gradient_icp_torch(pc_pred, pc_gt, estimate_scale, anisotropic_scale, lr, n_iter, verbose, return_trace)
+    N, dt = len(pc_pred), pc_pred.dtype
+    o = icp_run(pc_pred, pc_gt, estimate_scale, anisotropic_scale, lr, n_iter, with_trace=return_trace or verbose)
+    iso = estimate_scale and not anisotropic_scale
+    res = [o['R'].to(dt), o['T'].to(dt), (o['s'][:, :1] if iso else o['s']).to(dt)]
+    if not (return_trace or verbose):
+        return o['cloud'].to(dt), res
+    tr, best = o['trace'].cpu(), o['best'].tolist()
+    rts = tr[:, 1:].reshape(len(tr), N, _lib.ICP_TRACE_PER_INSTANCE)
+    trace = dict(loss=tr[:, 0].clone(), best_loss=best[0], best_iter=int(best[1]), R=rts[..., :9].reshape(len(tr), N, 3, 3).to(dt),
+                 T=rts[..., 9:12].to(dt), s=(rts[..., 12:13] if iso else rts[..., 12:15]).to(dt))
+    if verbose:
+        _print_checks(trace, N)
+    return (o['cloud'].to(dt), res, trace) if return_trace else (o['cloud'].to(dt), res)
+
+
+def unit_cube_frame(points):
+    """(offset (3,), scale) that bring a cloud (.., 3) to the unit cube by its own bounding box: (points - offset) / scale has its box
+    centred on 0 and its largest absolute coordinate at 0.5."""
+    flat = points.reshape(-1, 3)
+    offset = 0.5 * (flat.max(0).values + flat.min(0).values)
+    return offset, (flat - offset).abs().max() * 2
+
+
+def evaluate_aligned(model, points, normals=None, eval_dir=None, generator=None, samples=None, **evaluator_kwargs):
+    """The ICP-aligned 3D scores of a trained model against a ground-truth cloud that shares neither frame nor scale with it (a
+    BlendedMVS or custom scene: there is no DTU protocol for it).  The live blocks (model.blocks_mesh(filter_transparent=True)) and
+    `points` (P,3) [, `normals` (P,3)] are brought to the unit cube by the ground truth's own bounding box, then scored by
+    metrics.MeshEvaluator (keywords in evaluator_kwargs; `generator` / `samples`: MeshEvaluator.evaluate) -> OrderedDict of scores;
+    with eval_dir, {eval_dir}/aligned_scores.tsv: a line of names, a line of '{:.5f}' values, like final_scores.tsv."""
+    from .metrics import MeshEvaluator
+    verts, faces = model.blocks_mesh(filter_transparent=True)
+    verts = verts.detach()
+    gt = torch.as_tensor(points).to(device=verts.device, dtype=verts.dtype).reshape(-1, 3)
+    offset, scale = unit_cube_frame(gt)
+    gt, verts = (gt - offset) / scale, (verts - offset) / scale
+    if normals is not None:
+        normals = torch.as_tensor(normals).to(device=verts.device, dtype=verts.dtype).reshape(1, -1, 3)
+    names = evaluator_kwargs.pop('names', [n for n in MeshEvaluator.default_names
+                                            if not n.startswith('3D-IoU') and (normals is not None or not n.startswith('normal'))])
+    scores = MeshEvaluator(names=names, **evaluator_kwargs).evaluate((verts, faces), gt[None], normals, generator=generator, samples=samples)
+    if eval_dir is not None:
+        os.makedirs(str(eval_dir), exist_ok=True)
+        with open(os.path.join(str(eval_dir), 'aligned_scores.tsv'), mode='w') as f:
+            f.write('\t'.join(scores.keys()) + '\n')
+            f.write('\t'.join('{:.5f}'.format(float(v)) for v in scores.values()) + '\n')
+    return scores

@@ -192,11 +192,13 @@ class Trainer:
         return last
 
     # trainer.py:241-272
-    def evaluate(self, loader, run_dir, dtu=None):
+    def evaluate(self, loader, run_dir, dtu=None, aligned=None):
         """The end of a run: qualitative_eval into run_dir/quali_eval, quantitative_eval (hard inference) into run_dir/final_scores.tsv
         (a line of names, a line of values, '{:.5f}'), and -- dtu = dict(scale_mat=, scan_id=, dataset_dir=), further keywords of
-        eval3d.evaluate_dtu allowed -- the official DTU scores of the blocks into run_dir.  loader: an iterable of (inp, labels) that can be
-        walked twice.  -> the scores (with the DTU dict under 'dtu' where asked for)."""
+        eval3d.evaluate_dtu allowed -- the official DTU scores of the blocks into run_dir; aligned = dict(points=, normals=), further
+        keywords of eval3d.evaluate_aligned allowed -- the ICP-aligned Chamfer / normal scores against a ground-truth cloud in any frame
+        into run_dir/aligned_scores.tsv.  loader: an iterable of (inp, labels) that can be walked twice.  -> the scores (with the DTU dict
+        under 'dtu' and the aligned scores under 'aligned' where asked for)."""
         import os
         run_dir = str(run_dir)
         os.makedirs(os.path.join(run_dir, 'quali_eval'), exist_ok=True)
@@ -210,6 +212,9 @@ class Trainer:
         if dtu is not None:
             from .eval3d import evaluate_dtu
             scores = dict(scores, dtu=evaluate_dtu(self.model, eval_dir=run_dir, **dtu))
+        if aligned is not None:
+            from .eval3d import evaluate_aligned
+            scores = dict(scores, aligned=dict(evaluate_aligned(self.model, eval_dir=run_dir, **aligned)))
         return scores
 
     # trainer.py:201-209 / 84-107
