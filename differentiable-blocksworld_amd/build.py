@@ -20,7 +20,8 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, '..', 'include', h) for h in ('dbw_hip.h', 'dbw_eval.h', 'dbw_viz.h', 'dbw_export.h', 'dbw_ingest.h', 'dbw_lens.h', 'dbw_monitor.h', 'dbw_icp.h')] + [__file__]
+    inc = os.path.join(HERE, '..', 'include')
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(inc, h) for h in os.listdir(inc) if h.endswith('.h')] + [__file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

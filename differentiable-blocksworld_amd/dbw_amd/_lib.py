@@ -2,23 +2,26 @@
 
 The library is the product: there is NO CPU fallback.  If it cannot be loaded, or a call fails, a RuntimeError is
 raised (never a silent eager/PyTorch path)."""
+import collections
 import ctypes
+import functools
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdbw_hip.so')
 _lib = None
 
 
-def _header_abi_version():
-    """DBW_ABI_VERSION of include/dbw_hip.h: the one place the revision is written down (csrc/util.hip returns it, tests/test_abi.py and
-    __graft_entry__.build() compare the loaded library with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_hip.h')) as f:
-        return int(re.search(r'#define DBW_ABI_VERSION (\d+)', f.read()).group(1))
+@functools.lru_cache(maxsize=None)
+def header_define(header, macro):
+    """The integer `#define macro` of include/<header>: the one place a revision or a shared constant is written down (the library returns
+    it, the tests and __graft_entry__.build() compare the loaded library with it)."""
+    with open(os.path.join(_HERE, '..', '..', 'include', header)) as f:
+        return int(re.search(r'#define %s (\d+)' % macro, f.read()).group(1))
 
 
-ABI_VERSION = _header_abi_version()
+ABI_VERSION = header_define('dbw_hip.h', 'DBW_ABI_VERSION')
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -133,7 +136,7 @@ OTHER_SIGNATURES = {
     'dbw_lpips_head_blocks': (c_i, [c_i, c_i]),
 }
 
-# the 3D evaluation entry points: name -> argtypes, exactly the prototypes of include/dbw_eval.h (checked by tests/test_eval3d_host.py).
+# the 3D evaluation entry points: name -> argtypes, exactly the prototypes of include/dbw_eval.h (checked by tests/test_abi_families.py).
 # A table of their own: SIGNATURES / OTHER_SIGNATURES stay the prototypes of include/dbw_hip.h.
 EVAL_SIGNATURES = {
     'dbw_nn_points': [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
@@ -141,19 +144,10 @@ EVAL_SIGNATURES = {
     'dbw_dtu_lattice_points': [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p],
     'dbw_radius_downsample_round': [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_d, c_p, c_p, c_p],
 }
-
-
-def _header_eval_abi_version():
-    """DBW_EVAL_ABI_VERSION of include/dbw_eval.h (dbw_eval_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_eval.h')) as f:
-        return int(re.search(r'#define DBW_EVAL_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-EVAL_ABI_VERSION = _header_eval_abi_version()
+EVAL_ABI_VERSION = header_define('dbw_eval.h', 'DBW_EVAL_ABI_VERSION')
 
 # the lit visualisation renders: name -> argtypes, exactly the int-returning prototypes of include/dbw_viz.h (checked by
-# tests/test_viz_host.py); the one size_t-returning entry point next to them, like dbw_rasterize_workspace_bytes next to SIGNATURES
+# tests/test_abi_families.py); the one size_t-returning entry point next to them, like dbw_rasterize_workspace_bytes next to SIGNATURES
 VIZ_SIGNATURES = {
     'dbw_vertex_normals': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p],
     'dbw_render_lit_fwd': [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i,
@@ -162,35 +156,17 @@ VIZ_SIGNATURES = {
 VIZ_OTHER_SIGNATURES = {
     'dbw_render_lit_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i, c_i]),
 }
-
-
-def _header_viz_abi_version():
-    """DBW_VIZ_ABI_VERSION of include/dbw_viz.h (dbw_viz_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_viz.h')) as f:
-        return int(re.search(r'#define DBW_VIZ_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-VIZ_ABI_VERSION = _header_viz_abi_version()
+VIZ_ABI_VERSION = header_define('dbw_viz.h', 'DBW_VIZ_ABI_VERSION')
 
 # the 8-bit frame export: name -> argtypes, exactly the int-returning prototypes of include/dbw_export.h (checked by
-# tests/test_export_host.py).  A table of its own, like the two above.
+# tests/test_abi_families.py).  A table of its own, like the two above.
 EXPORT_SIGNATURES = {
     'dbw_frames_u8': [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 FRAME_HWC, FRAME_EDGE_FIRST, FRAME_CLAMP_INPUT = 1, 2, 4      # DBW_FRAME_* of include/dbw_export.h
+EXPORT_ABI_VERSION = header_define('dbw_export.h', 'DBW_EXPORT_ABI_VERSION')
 
-
-def _header_export_abi_version():
-    """DBW_EXPORT_ABI_VERSION of include/dbw_export.h (dbw_export_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_export.h')) as f:
-        return int(re.search(r'#define DBW_EXPORT_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-EXPORT_ABI_VERSION = _header_export_abi_version()
-
-# the image ingest: name -> argtypes, exactly the int-returning prototypes of include/dbw_ingest.h (checked by tests/test_ingest_host.py);
+# the image ingest: name -> argtypes, exactly the int-returning prototypes of include/dbw_ingest.h (checked by tests/test_abi_families.py);
 # the one size_t-returning entry point next to them.  dbw_resample_table returns its ksize (> 0) or a negative DBW_ERR_*: not for call().
 INGEST_SIGNATURES = {
     'dbw_resample_table': [c_i, c_i, c_p, c_sz],
@@ -200,34 +176,16 @@ INGEST_OTHER_SIGNATURES = {
     'dbw_images_resample_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
 }
 RESAMPLE_AUTO, RESAMPLE_GENERAL, RESAMPLE_FUSED = 0, 1, 2     # DBW_RESAMPLE_* of include/dbw_ingest.h
+INGEST_ABI_VERSION = header_define('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION')
 
-
-def _header_ingest_abi_version():
-    """DBW_INGEST_ABI_VERSION of include/dbw_ingest.h (dbw_ingest_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_ingest.h')) as f:
-        return int(re.search(r'#define DBW_INGEST_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-INGEST_ABI_VERSION = _header_ingest_abi_version()
-
-# the lens rectification: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by tests/test_lens_host.py).
+# the lens rectification: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by tests/test_abi_families.py).
 LENS_SIGNATURES = {
     'dbw_images_undistort_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
 }
 LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h
+LENS_ABI_VERSION = header_define('dbw_lens.h', 'DBW_LENS_ABI_VERSION')
 
-
-def _header_lens_abi_version():
-    """DBW_LENS_ABI_VERSION of include/dbw_lens.h (dbw_lens_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_lens.h')) as f:
-        return int(re.search(r'#define DBW_LENS_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-LENS_ABI_VERSION = _header_lens_abi_version()
-
-# the run monitor: name -> argtypes, exactly the int-returning prototypes of include/dbw_monitor.h (checked by tests/test_runlog_host.py);
+# the run monitor: name -> argtypes, exactly the int-returning prototypes of include/dbw_monitor.h (checked by tests/test_abi_families.py);
 # the one size_t-returning entry point next to them.
 MONITOR_SIGNATURES = {
     'dbw_image_scores': [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
@@ -238,18 +196,9 @@ MONITOR_OTHER_SIGNATURES = {
     'dbw_image_scores_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
 }
 METER_MAX_VALUES = 16                                         # DBW_METER_MAX_VALUES of include/dbw_monitor.h
+MONITOR_ABI_VERSION = header_define('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION')
 
-
-def _header_monitor_abi_version():
-    """DBW_MONITOR_ABI_VERSION of include/dbw_monitor.h (dbw_monitor_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_monitor.h')) as f:
-        return int(re.search(r'#define DBW_MONITOR_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-MONITOR_ABI_VERSION = _header_monitor_abi_version()
-
-# the gradient ICP: name -> argtypes, exactly the int-returning prototypes of include/dbw_icp.h (checked by tests/test_icp_host.py); the one
+# the gradient ICP: name -> argtypes, exactly the int-returning prototypes of include/dbw_icp.h (checked by tests/test_abi_families.py); the one
 # size_t-returning entry point next to them.
 ICP_SIGNATURES = {
     'dbw_icp_run': [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_d, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
@@ -258,16 +207,22 @@ ICP_OTHER_SIGNATURES = {
     'dbw_icp_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
 }
 ICP_TRACE_PER_INSTANCE = 15                                   # DBW_ICP_TRACE_PER_INSTANCE of include/dbw_icp.h
+ICP_ABI_VERSION = header_define('dbw_icp.h', 'DBW_ICP_ABI_VERSION')
 
-
-def _header_icp_abi_version():
-    """DBW_ICP_ABI_VERSION of include/dbw_icp.h (dbw_icp_abi_version() of the library is compared with it)."""
-    import re
-    with open(os.path.join(_HERE, '..', '..', 'include', 'dbw_icp.h')) as f:
-        return int(re.search(r'#define DBW_ICP_ABI_VERSION (\d+)', f.read()).group(1))
-
-
-ICP_ABI_VERSION = _header_icp_abi_version()
+# the add-on boundaries, one row per header beside include/dbw_hip.h: a new family is a row here and an id of tests/test_abi_families.py.
+# `what` completes "the loaded libdbw_hip.so has no ..." of family().
+Family = collections.namedtuple('Family', 'header macro version_fn signatures other_signatures what')
+FAMILIES = {
+    'eval': Family('dbw_eval.h', 'DBW_EVAL_ABI_VERSION', 'dbw_eval_abi_version', EVAL_SIGNATURES, {}, '3D evaluation entry points'),
+    'viz': Family('dbw_viz.h', 'DBW_VIZ_ABI_VERSION', 'dbw_viz_abi_version', VIZ_SIGNATURES, VIZ_OTHER_SIGNATURES, 'lit render entry points'),
+    'export': Family('dbw_export.h', 'DBW_EXPORT_ABI_VERSION', 'dbw_export_abi_version', EXPORT_SIGNATURES, {}, 'frame export entry point'),
+    'ingest': Family('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION', 'dbw_ingest_abi_version', INGEST_SIGNATURES, INGEST_OTHER_SIGNATURES,
+                     'image ingest entry point'),
+    'lens': Family('dbw_lens.h', 'DBW_LENS_ABI_VERSION', 'dbw_lens_abi_version', LENS_SIGNATURES, {}, 'lens rectification entry point'),
+    'monitor': Family('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION', 'dbw_monitor_abi_version', MONITOR_SIGNATURES, MONITOR_OTHER_SIGNATURES,
+                      'run monitor entry points'),
+    'icp': Family('dbw_icp.h', 'DBW_ICP_ABI_VERSION', 'dbw_icp_abi_version', ICP_SIGNATURES, ICP_OTHER_SIGNATURES, 'gradient ICP entry points'),
+}
 
 
 def load():
@@ -311,61 +266,31 @@ def load():
         if hasattr(lib, name):                  # (absent from tuning builds of older sources)
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
-    if hasattr(lib, 'dbw_eval_abi_version'):    # (absent from tuning builds of older sources: eval3d refuses to run on them)
-        lib.dbw_eval_abi_version.restype = c_i
-        for name, argtypes in EVAL_SIGNATURES.items():
+    for f in FAMILIES.values():
+        if not hasattr(lib, f.version_fn):      # (absent from tuning builds of older sources: family() refuses to run on them)
+            continue
+        getattr(lib, f.version_fn).restype = c_i
+        for name, argtypes in f.signatures.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = c_i
-    if hasattr(lib, 'dbw_viz_abi_version'):     # (absent from tuning builds of older sources: ops.render_scene_lit refuses to run on them)
-        lib.dbw_viz_abi_version.restype = c_i
-        for name, argtypes in VIZ_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-        for name, (restype, argtypes) in VIZ_OTHER_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, restype
-    if hasattr(lib, 'dbw_export_abi_version'):  # (absent from tuning builds of older sources: ops.frames_u8 refuses to run on them)
-        lib.dbw_export_abi_version.restype = c_i
-        for name, argtypes in EXPORT_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-    if hasattr(lib, 'dbw_ingest_abi_version'):  # (absent from tuning builds of older sources: ops.resample_u8 refuses to run on them)
-        lib.dbw_ingest_abi_version.restype = c_i
-        for name, argtypes in INGEST_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-        for name, (restype, argtypes) in INGEST_OTHER_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, restype
-    if hasattr(lib, 'dbw_lens_abi_version'):    # (absent from tuning builds of older sources: ops.undistort_u8 refuses to run on them)
-        lib.dbw_lens_abi_version.restype = c_i
-        for name, argtypes in LENS_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-    if hasattr(lib, 'dbw_monitor_abi_version'):  # (absent from tuning builds of older sources: ops.image_scores / runlog refuse to run on them)
-        lib.dbw_monitor_abi_version.restype = c_i
-        for name, argtypes in MONITOR_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-        for name, (restype, argtypes) in MONITOR_OTHER_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, restype
-    if hasattr(lib, 'dbw_icp_abi_version'):      # (absent from tuning builds of older sources: eval3d.icp_run refuses to run on them)
-        lib.dbw_icp_abi_version.restype = c_i
-        for name, argtypes in ICP_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
-        for name, (restype, argtypes) in ICP_OTHER_SIGNATURES.items():
+        for name, (restype, argtypes) in f.other_signatures.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
+    return lib
+
+
+def family(name):
+    """The loaded library, once it is known to hold the add-on family `name` of FAMILIES at the revision its header declares.  A library
+    without the family still loads (tuning builds of older sources through DBW_HIP_LIB): the refusal comes here, where the family is used."""
+    f = FAMILIES[name]
+    lib = load()
+    if not hasattr(lib, f.version_fn):
+        raise RuntimeError(f'the loaded libdbw_hip.so has no {f.what} (include/{f.header}): rebuild it')
+    got, want = getattr(lib, f.version_fn)(), header_define(f.header, f.macro)
+    if got != want:
+        raise RuntimeError(f'the library was built for {name} ABI {got}, include/{f.header} declares {want}: rebuild it')
     return lib
 
 

@@ -41,12 +41,7 @@ def _stream(dev):
 
 
 def _call(name, *args):
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_eval_abi_version'):
-        raise RuntimeError(f'{_lib.LIB_PATH} has no 3D evaluation entry points (include/dbw_eval.h): rebuild it')
-    if lib.dbw_eval_abi_version() != _lib.EVAL_ABI_VERSION:
-        raise RuntimeError(f'the library was built for eval ABI {lib.dbw_eval_abi_version()}, include/dbw_eval.h declares '
-                           f'{_lib.EVAL_ABI_VERSION}: rebuild it')
+    _lib.family('eval')
     _lib.call(name, *args)
 
 
@@ -617,12 +612,7 @@ def gradient_icp_torch(pc_pred, pc_gt, estimate_scale=True, anisotropic_scale=Fa
 
 
 def _icp_call(name, *args):
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_icp_abi_version'):
-        raise RuntimeError(f'{_lib.LIB_PATH} has no gradient ICP entry points (include/dbw_icp.h): rebuild it')
-    if lib.dbw_icp_abi_version() != _lib.ICP_ABI_VERSION:
-        raise RuntimeError(f'the library was built for ICP ABI {lib.dbw_icp_abi_version()}, include/dbw_icp.h declares '
-                           f'{_lib.ICP_ABI_VERSION}: rebuild it')
+    lib = _lib.family('icp')
     if name == 'dbw_icp_workspace_bytes':
         return lib.dbw_icp_workspace_bytes(*args)
     _lib.call(name, *args)

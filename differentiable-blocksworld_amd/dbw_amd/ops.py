@@ -640,10 +640,7 @@ def vertex_adjacency(faces_i32, V):
 
 
 def _viz_lib():
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_viz_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no lit render entry points (include/dbw_viz.h): rebuild it')
-    return lib
+    return _lib.family('viz')
 
 
 def vertex_normals(verts, faces_i32, adjacency=None):
@@ -711,9 +708,7 @@ def frames_u8(src, bkg=None, mask=None, edge_color=None, hwc=False, edge_first=F
     or a (3,H,W) tensor, composited under a C = 4 source (premultiplied rgb: rgb * alpha + (1 - alpha) * bkg).  mask (N,1,H,W) with
     edge_color three floats or (N,3,H,W): img * (1 - mask) + mask * colour, behind the composite, or in front of it with edge_first.
     clamp_input clamps the source channels to [0, 1] first.  out: an (N,H,W,3) uint8 GPU tensor to fill."""
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_export_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no frame export entry point (include/dbw_export.h): rebuild it')
+    lib = _lib.family('export')
     src_c = _chk(src, torch.float32, 'src')
     if src_c.dim() != 4:
         raise ValueError(f'src: four dimensions, got {tuple(src_c.shape)}')
@@ -753,10 +748,7 @@ def frames_u8(src, bkg=None, mask=None, edge_color=None, hwc=False, edge_first=F
 # run monitor (include/dbw_monitor.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def _monitor_lib():
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_monitor_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no run monitor entry points (include/dbw_monitor.h): rebuild it')
-    return lib
+    return _lib.family('monitor')
 
 
 def image_score_sums(a, b, padding=False, return_map=False):
@@ -811,9 +803,7 @@ _RESAMPLE_FORMS = {'auto': _lib.RESAMPLE_AUTO, 'general': _lib.RESAMPLE_GENERAL,
 def resample_table(in_size, out_size, device=None):
     """dbw_resample_table: the (out_size, ksize + 2) int32 rows [xmin, n, k_0 .. k_{ksize-1}] of one axis, on the host -- or, with a
     device, the copy of them resident there, made once per (in_size, out_size, device)."""
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_ingest_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no image ingest entry point (include/dbw_ingest.h): rebuild it')
+    lib = _lib.family('ingest')
     key = (int(in_size), int(out_size), None if device is None else str(torch.device(device)))
     if key not in _RESAMPLE_TABLES:
         if device is not None:
@@ -835,9 +825,7 @@ def resample_u8(src_u8, size, out='f32', form='auto'):
     them on the host, bit for bit (Pillow's antialiased BILINEAR resample in 8-bit fixed point, then uint8 / 255 in fp32).  size (Hout,Wout).
     out: 'f32' -> (N,3,Hout,Wout) fp32, the layout of views['imgs']; 'u8' -> (N,Hout,Wout,3) uint8; 'both' -> the pair.  form: 'auto', or
     'general' / 'fused' to force one of the two kernel forms (the same bytes; 'fused' refuses ratios above 5)."""
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_ingest_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no image ingest entry point (include/dbw_ingest.h): rebuild it')
+    lib = _lib.family('ingest')
     if out not in ('f32', 'u8', 'both') or form not in _RESAMPLE_FORMS:
         raise ValueError(f"out: 'f32', 'u8' or 'both', form: 'auto', 'general' or 'fused'; got {out!r}, {form!r}")
     src = _chk(src_u8, torch.uint8, 'src_u8')
@@ -880,9 +868,7 @@ def undistort_u8(raw_u8, intr, dist, zoom=1.0):
     """dbw_images_undistort_u8: (N,H,W,3) uint8 frames on the GPU, taken through a lens with OpenCV's radial-tangential distortion `dist` =
     (k1, k2, k3, k4, p1, p2) and the intrinsics `intr` = (fx, fy, cx, cy), -> the (N,H,W,3) uint8 frames of the pinhole camera with the
     focal lengths zoom * (fx, fy) and the same principal point, bilinear (csrc/lens_math.h).  One map for all N frames."""
-    lib = _lib.load()
-    if not hasattr(lib, 'dbw_lens_abi_version'):
-        raise RuntimeError('the loaded libdbw_hip.so has no lens rectification entry point (include/dbw_lens.h): rebuild it')
+    lib = _lib.family('lens')
     src = _chk(raw_u8, torch.uint8, 'raw_u8')
     if src.dim() != 4 or src.shape[3] != 3:
         raise ValueError(f'raw_u8: (N,H,W,3), got {tuple(src.shape)}')

@@ -2,28 +2,16 @@
 ops.frames_u8, and the quantisation rule restated with torch.  Used by tests/test_host_frame_math.py (against the reference's bytes) and
 by tests/test_gpu_export.py (as the yardstick of the kernel)."""
 import ctypes
-import os
-import subprocess
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from host_build import host_lib
+
 HWC, EDGE_FIRST, CLAMP_INPUT = 1, 2, 4
-_LIB = None
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_frame_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_frame_math.cpp'), os.path.join(csrc, 'frame_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('frame_math')
 
 
 def _p(t):

@@ -2,14 +2,11 @@
 ops.undistort_u8, and the cases the tests share.  Used by tests/test_host_lens_math.py (against an fp64 restatement written there),
 tests/test_custom_scene_host.py and tests/test_gpu_lens.py (as the yardstick of the kernel)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 SHAPES = [(24, 32), (23, 37)]                                   # (H, W): the second with an odd width and row bases off the dword grid
 COEFFS = [(0.12, 0.02, 0.0, 0.0, 0.003, -0.002),                # (k1, k2, k3, k4, p1, p2)
@@ -38,17 +35,7 @@ def frames(N, H, W, seed=0):
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_lens_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_lens_math.cpp'), os.path.join(csrc, 'lens_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('lens_math')
 
 
 def source_host(H, W, lens):

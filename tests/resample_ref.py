@@ -5,14 +5,14 @@ and tests/test_gpu_ingest.py (as the yardstick of the kernel)."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import torch
 
+from host_build import host_lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden', 'resample_pil.npz')
-_LIB = None
 
 # (Hin, Win) -> (Hout, Wout) of tests/golden/resample_pil.npz, by tag (tests/golden/make_resample_golden.py writes them)
 SHAPES = {
@@ -55,17 +55,7 @@ def make_input(tag):
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_resample_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_resample_math.cpp'), os.path.join(csrc, 'resample_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('resample_math')
 
 
 def table_host(in_size, out_size):

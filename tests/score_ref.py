@@ -10,12 +10,13 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from host_build import host_lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
 SRCS = [os.path.join(HERE, 'host_score_math.cpp'), os.path.join(CSRC, 'score_math.h'), os.path.join(CSRC, 'raster_math.h')]
 NOISE_SHAPES = [(11, 11), (12, 16), (23, 37), (37, 70)]
 RENDER_SHAPE = (48, 64)
-_LIB = None
 _CACHE = {}
 
 
@@ -24,15 +25,7 @@ def _stale(out):
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_score_math.so')
-        if _stale(so):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', SRCS[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('score_math')
 
 
 def sanitized_program():

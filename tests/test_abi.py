@@ -6,42 +6,23 @@ import re
 
 import pytest
 
+import abi_header as AH
 from conftest import ROOT
 from dbw_amd import _lib
 
 HEADER = os.path.join(ROOT, 'include', 'dbw_hip.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
-         'dbw_stream_t': ctypes.c_void_p}
-
-
-def parse_header():
-    src = open(HEADER).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r'\b(int64_t|int|size_t|void \*|void|const char \*|dbw_step_plan \*)\s*(dbw_\w+)\s*\(([^;{]*?)\)\s*;', src, flags=re.S):
-        args = ' '.join(args.split())
-        types = []
-        if args and args != 'void':
-            for a in args.split(','):
-                a = a.strip()
-                if '*' in a:
-                    types.append(ctypes.c_void_p)
-                else:
-                    types.append(CTYPE[a.replace('const ', '').split()[0]])
-        protos[name] = (ret.strip(), types)
-    return protos
 
 
 def test_library_builds_and_loads_without_gpu():
     lib = _lib.load()
     assert os.path.exists(_lib.LIB_PATH)
-    assert lib.dbw_abi_version() == _lib.ABI_VERSION == int(re.search(r'#define DBW_ABI_VERSION (\d+)', open(HEADER).read()).group(1))
+    assert lib.dbw_abi_version() == _lib.ABI_VERSION == AH.defines('dbw_hip.h')['DBW_ABI_VERSION']
     assert lib.dbw_last_error() is not None
 
 
 def test_every_declared_symbol_is_exported_with_matching_signature():
     lib = _lib.load()
-    protos = parse_header()
+    protos = AH.prototypes('dbw_hip.h')
     assert len(protos) == 57
     for name, (ret, types) in protos.items():
         assert hasattr(lib, name), f'{name} declared in dbw_hip.h but not exported'
@@ -62,10 +43,9 @@ def test_every_declared_symbol_is_exported_with_matching_signature():
 def test_bin_cursor_count_comes_from_the_library():
     """The host sizes the cursor array and rounds the record capacity of the texture bins with the library's DBW_BIN_SUBCURSORS
     (dbw_bin_subcursors), not with a constant of its own."""
-    import re
     from dbw_amd import ops
     lib = _lib.load()
-    declared = int(re.search(r'#define DBW_BIN_SUBCURSORS (\d+)', open(HEADER).read()).group(1))
+    declared = AH.defines('dbw_hip.h')['DBW_BIN_SUBCURSORS']
     assert lib.dbw_bin_subcursors() == declared == ops.BIN_SUBCURSORS == ops.bin_subcursors()
     for nbins in (1, 7, 640):
         cap = ops.texbin_capacity(49, 300, 400, 10, nbins)
@@ -96,7 +76,7 @@ def _parse_struct(name):
     """[(field, ctype)] of `typedef struct name { ... } name;` in the header: plain declarations only (scalars, pointers, small arrays)."""
     src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
     body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (name, name), src, flags=re.S).group(1)
-    base = dict(CTYPE, uint64_t=ctypes.c_uint64, int32_t=ctypes.c_int32)
+    base = dict(AH.CTYPE, uint64_t=ctypes.c_uint64, int32_t=ctypes.c_int32)
     fields = []
     for decl in body.split(';'):
         decl = ' '.join(decl.split())
@@ -145,7 +125,7 @@ def test_header_is_plain_c_and_a_c_host_links_against_the_library(tmp_path):
     if gcc is None:
         pytest.skip('no gcc')
     _lib.load()
-    names = sorted(parse_header())
+    names = sorted(AH.prototypes('dbw_hip.h'))
     src = tmp_path / 'host.c'
     src.write_text('#include <stdio.h>\n#include "dbw_hip.h"\n'
                    'int main(void) {\n'

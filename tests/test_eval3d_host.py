@@ -3,35 +3,20 @@
     dtu_eval.py:21-30,56-78 and against the REAL reference's cloud (tests/golden/dtu_tiny.npz), the distance formula bit-exact against torch;
   * eval3d.chamfer_distance on CPU tensors against the REAL reference's chamfer_distance (tests/golden/chamfer.npz): values and gradients;
   * the sequential greedy downsample (restated) against the reference's keep mask; the PLY / .mat readers; the TSV format;
-  * the C ABI of include/dbw_eval.h: prototypes == _lib.EVAL_SIGNATURES, symbols exported, validation before any launch."""
+  * the C ABI of include/dbw_eval.h: validation before any launch (prototypes, revision, symbols: tests/test_abi_families.py)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from dbw_amd import _lib, eval3d
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_nn_math.so')
-        csrc = os.path.join(ROOT, 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_nn_math.cpp'), os.path.join(csrc, 'nn_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('nn_math')
 
 
 def _p(a):
@@ -217,25 +202,6 @@ def test_tsv_matches_the_reference_bytes(golden_dir, tmp_path):
     g = np.load(os.path.join(golden_dir, 'dtu_tiny.npz'))
     eval3d.write_scores_tsv(str(tmp_path / 's.tsv'), float(g['acc']), float(g['comp']), float(g['avg']))
     assert (tmp_path / 's.tsv').read_text() == str(g['tsv'])
-
-
-HEADER = os.path.join(ROOT, 'include', 'dbw_eval.h')
-CTYPE = {'int': ctypes.c_int, 'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'dbw_stream_t': ctypes.c_void_p}
-
-
-def test_eval_header_matches_the_binding_and_the_library():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    protos = {}
-    for name, args in re.findall(r'\bint\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;', src, flags=re.S):
-        args = ' '.join(args.split())
-        protos[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]]
-                                                          for a in args.split(',')]
-    assert set(protos) == set(_lib.EVAL_SIGNATURES) | {'dbw_eval_abi_version'}
-    lib = _lib.load()
-    for name, types in _lib.EVAL_SIGNATURES.items():
-        assert protos[name] == types, name
-        assert getattr(lib, name).argtypes == types
-    assert lib.dbw_eval_abi_version() == _lib.EVAL_ABI_VERSION == int(re.search(r'#define DBW_EVAL_ABI_VERSION (\d+)', src).group(1)) == 1
 
 
 def test_eval_entry_points_validate_before_any_launch():

@@ -1,9 +1,7 @@
-"""CPU tests of the export's host side: the C boundary include/dbw_export.h against its ctypes binding and the library, argument validation
-before any launch, and the file writers of dbw_amd/export.py (PNG, GIF, PLY, textured OBJ with its atlas)."""
+"""CPU tests of the export's host side: argument validation of include/dbw_export.h before any launch (the boundary against its
+ctypes binding and the library: tests/test_abi_families.py), and the file writers of dbw_amd/export.py (PNG, GIF, PLY, textured OBJ with its atlas)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,51 +11,6 @@ from PIL import Image
 import oracle as O
 from dbw_amd import _lib, eval3d, export
 from dbw_amd.structures import PackedScene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'dbw_export.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'dbw_stream_t': ctypes.c_void_p}
-
-
-def _protos(ret, header=HEADER):
-    src = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b%s\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;' % ret, src, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]] for a in args.split(',')]
-    return out
-
-
-def test_export_header_is_plain_c99(tmp_path):
-    src = tmp_path / 'export.c'
-    src.write_text('#include "dbw_export.h"\nint main(void) { return DBW_EXPORT_ABI_VERSION == 1 && DBW_FRAME_HWC == 1 ? 0 : 1; }\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o',
-                        str(tmp_path / 'export.o')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_export_header_matches_the_binding_and_the_library():
-    ints = _protos('int')
-    assert set(ints) == set(_lib.EXPORT_SIGNATURES) | {'dbw_export_abi_version'} and not _protos('size_t')
-    lib = _lib.load()
-    for name, types in _lib.EXPORT_SIGNATURES.items():
-        assert ints[name] == types, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_int
-    src = open(HEADER).read()
-    assert lib.dbw_export_abi_version() == _lib.EXPORT_ABI_VERSION == int(re.search(r'#define DBW_EXPORT_ABI_VERSION (\d+)', src).group(1)) == 1
-    assert (_lib.FRAME_HWC, _lib.FRAME_EDGE_FIRST, _lib.FRAME_CLAMP_INPUT) == tuple(
-        int(re.search(r'#define DBW_FRAME_%s (\d+)' % n, src).group(1)) for n in ('HWC', 'EDGE_FIRST', 'CLAMP_INPUT'))
-    # the library exports exactly these names of the new boundary
-    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r' T (dbw_\w+)', syms))
-    assert set(ints) <= exported and {n for n in exported if 'export' in n or 'frames' in n} == set(ints)
-    # the other three boundaries are what they were
-    assert lib.dbw_abi_version() == _lib.ABI_VERSION == 7 and lib.dbw_viz_abi_version() == _lib.VIZ_ABI_VERSION == 1
-    assert lib.dbw_eval_abi_version() == _lib.EVAL_ABI_VERSION
-    others = set(_lib.SIGNATURES) | set(_lib.OTHER_SIGNATURES) | set(_lib.EVAL_SIGNATURES) | set(_lib.VIZ_SIGNATURES) | set(_lib.VIZ_OTHER_SIGNATURES)
-    assert not set(_lib.EXPORT_SIGNATURES) & others
-    hip = open(os.path.join(ROOT, 'include', 'dbw_hip.h')).read()
-    assert 'frames_u8' not in hip and 'dbw_export' not in hip
 
 
 def _frame_args(**over):

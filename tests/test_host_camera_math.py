@@ -3,30 +3,16 @@ compiles) built for the host with g++ (tests/host_camera_math.cpp): bit-exact cl
 oracle's transform_to_ndc + clip_faces on a scene that exercises every clipping case, and the hand-derived backward
 against autograd of the oracle.  The GPU test (tests/test_gpu_parity.py::test_project_clip_bit_exact) holds the kernel to the same."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 
 import oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_camera_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_camera_math.cpp'), os.path.join(csrc, 'camera_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('camera_math')
 
 
 def _p(t):

@@ -4,38 +4,24 @@
   * the keep-best rule against a ten-line restatement of icp.py:27-28,65-74 on a loss sequence that rises and falls;
   * the transform expression against its numpy restatement, bit for bit."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from dbw_amd import mesh
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_icp_math.so')
-        csrc = os.path.join(ROOT, 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_icp_math.cpp')] + [os.path.join(csrc, h) for h in ('icp_math.h', 'model_math.h', 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-        _LIB.host_icp_grad_MT.restype = ctypes.c_double
-        vp = ctypes.c_void_p
-        _LIB.host_icp_transform.argtypes = [vp, vp, ctypes.c_longlong, vp]
-        _LIB.host_icp_moments.argtypes = [vp, vp, vp, ctypes.c_longlong, vp]
-        _LIB.host_icp_step.argtypes = [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_int, vp, vp]
-        _LIB.host_icp_adam.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]
-    return _LIB
+    L = host_lib('icp_math')
+    L.host_icp_grad_MT.restype = ctypes.c_double
+    vp = ctypes.c_void_p
+    L.host_icp_transform.argtypes = [vp, vp, ctypes.c_longlong, vp]
+    L.host_icp_moments.argtypes = [vp, vp, vp, ctypes.c_longlong, vp]
+    L.host_icp_step.argtypes = [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_int, vp, vp]
+    L.host_icp_adam.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    return L
 
 
 def _p(a):

@@ -9,8 +9,6 @@ compile) built for the host with g++ (tests/host_light_math.cpp), against the to
     lie in between)."""
 import ctypes
 import math
-import os
-import subprocess
 
 import pytest
 import torch
@@ -18,24 +16,13 @@ import torch
 import lit_ref as LR
 import oracle as O
 from dbw_amd import ops
+from host_build import host_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
 KA, KD = [0.7, 0.7, 0.7], [0.4, 0.4, 0.4]
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_light_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_light_math.cpp'), os.path.join(csrc, 'light_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('light_math')
 
 
 def _p(t):

@@ -4,31 +4,19 @@ tv_grad from dbw.py:378-387 + loss.py:46, with the u-wrap), the decoupled compos
 the Adam update against torch.optim.Adam (optimizer.py:6-18)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import torch
 
 import oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_loss_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_loss_math.cpp'), os.path.join(csrc, 'loss_math.h'), os.path.join(csrc, 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-        _LIB.host_tv.restype = ctypes.c_double
-        _LIB.host_composite_mse.restype = ctypes.c_double
-    return _LIB
+    L = host_lib('loss_math')
+    L.host_tv.restype = ctypes.c_double
+    L.host_composite_mse.restype = ctypes.c_double
+    return L
 
 
 def _p(t):

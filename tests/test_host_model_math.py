@@ -5,30 +5,17 @@ superquadric surface points and their exponent gradients, the implicit superquad
 gradients, signed_pow / safe_pow, the 6D rotation and the posing chain with their hand-derived backward."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_model_math.so')
-        csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-        srcs = [os.path.join(HERE, 'host_model_math.cpp'), os.path.join(csrc, 'model_math.h'), os.path.join(csrc, 'raster_math.h'), os.path.join(csrc, 'rng_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-    return _LIB
+    return host_lib('model_math')
 
 
 def _p(t):

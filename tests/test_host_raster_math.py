@@ -4,32 +4,19 @@ their guards, conservative tile culling and the key/payload top-K list must repr
 The GPU parity tests (tests/test_gpu_parity.py) hold the kernels themselves to the same bar."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+from host_build import host_lib
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        out = os.path.join(HERE, '_build')
-        os.makedirs(out, exist_ok=True)
-        so = os.path.join(out, 'libhost_raster_math.so')
-        srcs = [os.path.join(HERE, 'host_raster_math.cpp'),
-                os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc', 'raster_math.h')]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', srcs[0], '-o', so])
-        _LIB = ctypes.CDLL(so)
-        _LIB.host_divcheck.restype = ctypes.c_longlong
-    return _LIB
+    L = host_lib('raster_math')
+    L.host_divcheck.restype = ctypes.c_longlong
+    return L
 
 
 def _p(t):

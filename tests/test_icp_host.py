@@ -1,39 +1,15 @@
 """CPU tests of the ICP-aligned evaluation (dbw_amd/eval3d.py, dbw_amd/metrics.py, include/dbw_icp.h), no GPU needed:
-  * the C ABI of include/dbw_icp.h: prototypes == _lib.ICP_SIGNATURES, symbols exported, validation before any launch;
+  * the C ABI of include/dbw_icp.h: validation before any launch (prototypes, revision, symbols: tests/test_abi_families.py);
   * gradient_icp on CPU tensors recovers the transform of the ellipsoid pair; fp32 and fp64 agree as measured when the input was chosen;
   * the refusals; normalize_mesh; the Metrics TSV bytes; MeshEvaluator on a sphere pair; ProxyEvaluator on two masks."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from dbw_amd import _lib, eval3d, mesh, metrics
 import icp_fixture as fx
-
-HEADER = os.path.join(ROOT, 'include', 'dbw_icp.h')
-CTYPE = {'int': ctypes.c_int, 'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'dbw_stream_t': ctypes.c_void_p}
-
-
-def test_icp_header_matches_the_binding_and_the_library():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    protos = {}
-    for name, args in re.findall(r'\bint\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;', src, flags=re.S):
-        args = ' '.join(args.split())
-        protos[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]]
-                                                          for a in args.split(',')]
-    assert set(protos) == set(_lib.ICP_SIGNATURES) | {'dbw_icp_abi_version'}
-    lib = _lib.load()
-    for name, types in _lib.ICP_SIGNATURES.items():
-        assert protos[name] == types, name
-        assert getattr(lib, name).argtypes == types
-    assert re.search(r'\bsize_t\s+dbw_icp_workspace_bytes\s*\(int N, int P1, int P2, int n_iter\)\s*;', src)
-    assert lib.dbw_icp_workspace_bytes.argtypes == [ctypes.c_int] * 4 and lib.dbw_icp_workspace_bytes.restype == ctypes.c_size_t
-    assert lib.dbw_icp_abi_version() == _lib.ICP_ABI_VERSION == int(re.search(r'#define DBW_ICP_ABI_VERSION (\d+)', src).group(1)) == 1
-    assert _lib.ICP_TRACE_PER_INSTANCE == int(re.search(r'#define DBW_ICP_TRACE_PER_INSTANCE (\d+)', src).group(1))
 
 
 def test_icp_entry_points_validate_before_any_launch():

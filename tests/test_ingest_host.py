@@ -1,9 +1,7 @@
-"""CPU tests of the image ingest's host side: the C boundary include/dbw_ingest.h against its ctypes binding and the library, its host
-function dbw_resample_table against the host build of the same header, and argument validation before any launch."""
+"""CPU tests of the image ingest's host side: the host function dbw_resample_table of include/dbw_ingest.h against the host build of
+csrc/resample_math.h, and argument validation before any launch (the boundary against its ctypes binding and the library:
+tests/test_abi_families.py)."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,58 +9,6 @@ import torch
 
 import resample_ref as RR
 from dbw_amd import _lib, ops
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'dbw_ingest.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'dbw_stream_t': ctypes.c_void_p}
-
-
-def _protos(ret, header=HEADER):
-    src = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b%s\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;' % ret, src, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]] for a in args.split(',')]
-    return out
-
-
-def test_ingest_header_is_plain_c99(tmp_path):
-    src = tmp_path / 'ingest.c'
-    src.write_text('#include "dbw_ingest.h"\nint main(void) { return DBW_INGEST_ABI_VERSION == 1 && DBW_RESAMPLE_FUSED == 2 ? 0 : 1; }\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o',
-                        str(tmp_path / 'ingest.o')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_ingest_header_matches_the_binding_and_the_library():
-    ints, sizes = _protos('int'), _protos('size_t')
-    assert set(ints) == set(_lib.INGEST_SIGNATURES) | {'dbw_ingest_abi_version'} and set(sizes) == set(_lib.INGEST_OTHER_SIGNATURES)
-    lib = _lib.load()
-    for name, types in _lib.INGEST_SIGNATURES.items():
-        assert ints[name] == types, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_int
-    for name, (restype, types) in _lib.INGEST_OTHER_SIGNATURES.items():
-        assert sizes[name] == types and restype == ctypes.c_size_t, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_size_t
-    src = open(HEADER).read()
-    assert lib.dbw_ingest_abi_version() == _lib.INGEST_ABI_VERSION == int(re.search(r'#define DBW_INGEST_ABI_VERSION (\d+)', src).group(1)) == 1
-    assert (_lib.RESAMPLE_AUTO, _lib.RESAMPLE_GENERAL, _lib.RESAMPLE_FUSED) == tuple(
-        int(re.search(r'#define DBW_RESAMPLE_%s (\d+)' % n, src).group(1)) for n in ('AUTO', 'GENERAL', 'FUSED'))
-    # the library exports exactly these names of the new boundary, and none of them reads like a name of the frame export's
-    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r' T (dbw_\w+)', syms))
-    mine = set(ints) | set(sizes)
-    assert mine <= exported and {n for n in exported if 'resample' in n or 'ingest' in n} == mine
-    assert not any('export' in n or 'frames' in n for n in mine)
-    # the other four boundaries are what they were
-    assert lib.dbw_abi_version() == _lib.ABI_VERSION == 7 and lib.dbw_viz_abi_version() == _lib.VIZ_ABI_VERSION == 1
-    assert lib.dbw_eval_abi_version() == _lib.EVAL_ABI_VERSION == 1 and lib.dbw_export_abi_version() == _lib.EXPORT_ABI_VERSION == 1
-    others = (set(_lib.SIGNATURES) | set(_lib.OTHER_SIGNATURES) | set(_lib.EVAL_SIGNATURES) | set(_lib.VIZ_SIGNATURES) | set(_lib.VIZ_OTHER_SIGNATURES)
-              | set(_lib.EXPORT_SIGNATURES))
-    assert not mine & others
-    for h in ('dbw_hip.h', 'dbw_viz.h', 'dbw_eval.h', 'dbw_export.h'):
-        text = open(os.path.join(ROOT, 'include', h)).read()
-        assert 'resample' not in text and 'dbw_ingest' not in text, h
 
 
 @pytest.mark.parametrize('in_size,out_size', [(1600, 400), (768, 768), (53, 13), (24, 50), (400, 3), (260, 65)])

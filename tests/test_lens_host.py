@@ -1,62 +1,15 @@
-"""CPU tests of the lens rectification's host side: the C boundary include/dbw_lens.h against its ctypes binding and the library, and
-argument validation before any launch."""
+"""CPU tests of the lens rectification's host side: argument validation of include/dbw_lens.h before any launch (the boundary against its
+ctypes binding and the library: tests/test_abi_families.py)."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 
 from dbw_amd import _lib, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'dbw_lens.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'dbw_stream_t': ctypes.c_void_p}
 
-
-def _protos(ret, header=HEADER):
-    src = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b%s\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;' % ret, src, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]] for a in args.split(',')]
-    return out
-
-
-def test_lens_header_is_plain_c99(tmp_path):
-    src = tmp_path / 'lens.c'
-    src.write_text('#include "dbw_lens.h"\nint main(void) { return DBW_LENS_ABI_VERSION == 1 && DBW_LENS_N_PARAMS == 12 ? 0 : 1; }\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o',
-                        str(tmp_path / 'lens.o')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_lens_header_matches_the_binding_and_the_library():
-    ints = _protos('int')
-    assert set(ints) == set(_lib.LENS_SIGNATURES) | {'dbw_lens_abi_version'} and not _protos('size_t')
-    lib = _lib.load()
-    for name, types in _lib.LENS_SIGNATURES.items():
-        assert ints[name] == types, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_int
-    src = open(HEADER).read()
-    assert lib.dbw_lens_abi_version() == _lib.LENS_ABI_VERSION == int(re.search(r'#define DBW_LENS_ABI_VERSION (\d+)', src).group(1)) == 1
-    assert _lib.LENS_N_PARAMS == int(re.search(r'#define DBW_LENS_N_PARAMS (\d+)', src).group(1)) == ops.lens_params((1, 1, 0, 0), (0,) * 6).numel()
-    # the library exports exactly these names of the new boundary, and none of them reads like a name of the ingest's or the frame export's
-    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r' T (dbw_\w+)', syms))
-    assert set(ints) <= exported and {n for n in exported if 'lens' in n or 'undistort' in n} == set(ints)
-    assert not any(w in n for n in ints for w in ('resample', 'ingest', 'export', 'frames'))
-    # the other five boundaries are what they were
-    assert lib.dbw_abi_version() == _lib.ABI_VERSION == 7 and lib.dbw_viz_abi_version() == _lib.VIZ_ABI_VERSION == 1
-    assert lib.dbw_eval_abi_version() == _lib.EVAL_ABI_VERSION == 1 and lib.dbw_export_abi_version() == _lib.EXPORT_ABI_VERSION == 1
-    assert lib.dbw_ingest_abi_version() == _lib.INGEST_ABI_VERSION == 1
-    others = (set(_lib.SIGNATURES) | set(_lib.OTHER_SIGNATURES) | set(_lib.EVAL_SIGNATURES) | set(_lib.VIZ_SIGNATURES) | set(_lib.VIZ_OTHER_SIGNATURES)
-              | set(_lib.EXPORT_SIGNATURES) | set(_lib.INGEST_SIGNATURES) | set(_lib.INGEST_OTHER_SIGNATURES))
-    assert not set(_lib.LENS_SIGNATURES) & others
-    for h in ('dbw_hip.h', 'dbw_viz.h', 'dbw_eval.h', 'dbw_export.h', 'dbw_ingest.h'):
-        text = open(os.path.join(ROOT, 'include', h)).read()
-        assert 'undistort' not in text and 'dbw_lens' not in text, h
+def test_lens_params_fill_the_count_of_the_header():
+    assert ops.lens_params((1, 1, 0, 0), (0,) * 6).numel() == _lib.LENS_N_PARAMS
 
 
 def _args(**over):

@@ -1,10 +1,8 @@
-"""CPU tests of the run record's host side (dbw_amd/runlog.py) and of the C boundary include/dbw_monitor.h against its ctypes binding and
-the library: the metric file byte for byte, the tick arithmetic and the resume position on a trainer without a GPU, the image logger's
+"""CPU tests of the run record's host side (dbw_amd/runlog.py) and of the C boundary include/dbw_monitor.h (against its ctypes
+binding and the library: tests/test_abi_families.py): the metric file byte for byte, the tick arithmetic and the resume position on a trainer without a GPU, the image logger's
 files and queue, argument validation before any launch."""
 import ctypes
 import os
-import re
-import subprocess
 import threading
 
 import numpy as np
@@ -17,53 +15,8 @@ import frame_ref as FR
 from dbw_amd import _lib, ops, runlog
 from dbw_amd.trainer import Trainer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'dbw_monitor.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
-         'dbw_stream_t': ctypes.c_void_p}
 
-
-def _protos(ret):
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b%s\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;' % ret, src, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]] for a in args.split(',')]
-    return out
-
-
-# ---- the C boundary ----------------------------------------------------------------------------------------------------------------------
-def test_monitor_header_is_plain_c99(tmp_path):
-    src = tmp_path / 'monitor.c'
-    src.write_text('#include "dbw_monitor.h"\nint main(void) { return DBW_MONITOR_ABI_VERSION == 1 && DBW_METER_MAX_VALUES == 16 ? 0 : 1; }\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o',
-                        str(tmp_path / 'monitor.o')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_monitor_header_matches_the_binding_and_the_library():
-    ints, sizes = _protos('int'), _protos('size_t')
-    assert set(ints) == set(_lib.MONITOR_SIGNATURES) | {'dbw_monitor_abi_version'} and set(sizes) == set(_lib.MONITOR_OTHER_SIGNATURES)
-    lib = _lib.load()
-    for name, types in _lib.MONITOR_SIGNATURES.items():
-        assert ints[name] == types, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_int
-    for name, (restype, types) in _lib.MONITOR_OTHER_SIGNATURES.items():
-        assert sizes[name] == types and getattr(lib, name).argtypes == types and getattr(lib, name).restype == restype
-    src = open(HEADER).read()
-    assert lib.dbw_monitor_abi_version() == _lib.MONITOR_ABI_VERSION == int(re.search(r'#define DBW_MONITOR_ABI_VERSION (\d+)', src).group(1)) == 1
-    assert _lib.METER_MAX_VALUES == int(re.search(r'#define DBW_METER_MAX_VALUES (\d+)', src).group(1))
-    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r' T (dbw_\w+)', syms))
-    mine = set(ints) | set(sizes)
-    assert mine <= exported and {n for n in exported if 'monitor' in n or 'meter' in n or 'scores' in n} == mine
-    others = (set(_lib.SIGNATURES) | set(_lib.OTHER_SIGNATURES) | set(_lib.EVAL_SIGNATURES) | set(_lib.VIZ_SIGNATURES) | set(_lib.EXPORT_SIGNATURES)
-              | set(_lib.INGEST_SIGNATURES) | set(_lib.LENS_SIGNATURES))
-    assert not mine & others
-    hip = open(os.path.join(ROOT, 'include', 'dbw_hip.h')).read()
-    assert 'dbw_monitor' not in hip and 'dbw_meter' not in hip and 'image_scores' not in hip
-
-
+# ---- the C boundary (its prototypes, revision and symbols: tests/test_abi_families.py) ------------------------------------------------
 def _score_args(**over):
     p = ctypes.c_void_p(256)
     a = dict(a=p, b=p, N=2, H=16, W=16, padding=0, workspace=p, ssim_map=None, out=p, stream=None)

@@ -1,9 +1,6 @@
-"""CPU tests of the lit visualisation renders' host side: the C boundary include/dbw_viz.h against its ctypes binding and the library,
-argument validation before any launch, the Renderer's light / shading keywords and refusals, and the view-trajectory helpers."""
+"""CPU tests of the lit visualisation renders' host side: argument validation of include/dbw_viz.h before any launch (the boundary
+against its ctypes binding and the library: tests/test_abi_families.py), the Renderer's light / shading keywords and refusals, and the view-trajectory helpers."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -14,45 +11,8 @@ from dbw_amd import _lib, ops
 from dbw_amd import renderer as RN
 from dbw_amd.renderer import Renderer
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'dbw_viz.h')
-CTYPE = {'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'dbw_stream_t': ctypes.c_void_p}
 LIGHT = {'name': 'directional', 'direction': [[1, 0.25, -1]], 'ambient_color': [[0.7, 0.7, 0.7]], 'diffuse_color': [[0.4, 0.4, 0.4]],
          'specular_color': [[0., 0., 0.]]}
-
-
-def _protos(ret):
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b%s\s+(dbw_\w+)\s*\(([^;{]*?)\)\s*;' % ret, src, flags=re.S):
-        args = ' '.join(args.split())
-        out[name] = [] if args in ('', 'void') else [ctypes.c_void_p if '*' in a else CTYPE[a.replace('const ', '').split()[0]] for a in args.split(',')]
-    return out
-
-
-def test_viz_header_is_plain_c99(tmp_path):
-    src = tmp_path / 'viz.c'
-    src.write_text('#include "dbw_viz.h"\nint main(void) { return DBW_VIZ_ABI_VERSION == 1 ? 0 : 1; }\n')
-    r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o',
-                        str(tmp_path / 'viz.o')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_viz_header_matches_the_binding_and_the_library():
-    ints, sizes = _protos('int'), _protos('size_t')
-    assert set(ints) == set(_lib.VIZ_SIGNATURES) | {'dbw_viz_abi_version'}
-    assert set(sizes) == set(_lib.VIZ_OTHER_SIGNATURES)
-    lib = _lib.load()
-    for name, types in _lib.VIZ_SIGNATURES.items():
-        assert ints[name] == types, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == ctypes.c_int
-    for name, (restype, types) in _lib.VIZ_OTHER_SIGNATURES.items():
-        assert sizes[name] == types and restype == ctypes.c_size_t, name
-        assert getattr(lib, name).argtypes == types and getattr(lib, name).restype == restype
-    src = open(HEADER).read()
-    assert lib.dbw_viz_abi_version() == _lib.VIZ_ABI_VERSION == int(re.search(r'#define DBW_VIZ_ABI_VERSION (\d+)', src).group(1)) == 1
-    # the other two boundaries are what they were
-    assert lib.dbw_abi_version() == _lib.ABI_VERSION == 7 and not set(_lib.VIZ_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EVAL_SIGNATURES))
 
 
 def _lit_args(**over):
