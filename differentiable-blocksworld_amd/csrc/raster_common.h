@@ -101,9 +101,10 @@ __device__ __forceinline__ FaceRec load_rec_nowait(const FaceRec *__restrict__ r
     u.v[1] = vp[1];
     return u.r;
 }
-template <int KMAX, bool PAY3>
+// (Q: the per-pixel list the kept pairs go to -- TopK, or a type with its init / sibling / insert interface: parse_math.h)
+template <int KMAX, bool PAY3, class Q = TopK<KMAX, PAY3>>
 __device__ __forceinline__ void eval_staged_chunk(const FaceRec *__restrict__ recs, int f_begin, int jl, int mcnt, bool in_img, f2 p, int K, float blur,
-                                                  int persp, int clipb, bool fastdiv, bool sign_only, TopK<KMAX, PAY3> &q, pay4 *home, int NT, int tid, bool no_insert = false, bool no_eval = false,
+                                                  int persp, int clipb, bool fastdiv, bool sign_only, Q &q, pay4 *home, int NT, int tid, bool no_insert = false, bool no_eval = false,
                                                   unsigned long long mask = ~0ull) {
     // (mask: the lanes of `jl` that hold faces of the chunk, in order)
     auto face = [&](const FaceRec &r, int j) {
@@ -153,11 +154,11 @@ __device__ __forceinline__ void eval_staged_chunk(const FaceRec *__restrict__ re
 // (PRE: a callable run once the tile's view and pixel are known and BEFORE the tile's own list is built -- the fused forward evaluates the
 // hard env layer of its pixel there, while nothing of the soft pass is live in registers yet)
 struct NoPre { __device__ __forceinline__ void operator()(int, int, int, bool) const {} };
-template <int KMAX, int TW, int TH, int GROUP = 2, bool PAY3 = false, class PRE = NoPre>
+template <int KMAX, int TW, int TH, int GROUP = 2, bool PAY3 = false, class PRE = NoPre, class Q = TopK<KMAX, PAY3>>
 __device__ __forceinline__ bool raster_tile(const FaceRec *__restrict__ recs, const float4 *__restrict__ bbox,
                                             const int *__restrict__ first_idx, const int *__restrict__ num_faces, int H, int W, int K,
                                             float blur, int persp, int clipb, long long total_blocks, const CoarseBins &cb, int dbg,
-                                            int &n, int &xi, int &yi, TopK<KMAX, PAY3> &q, pay4 *&home, bool *known_empty = nullptr, PRE pre = PRE()) {
+                                            int &n, int &xi, int &yi, Q &q, pay4 *&home, bool *known_empty = nullptr, PRE pre = PRE()) {
     static_assert(COARSE % TW == 0 && COARSE % TH == 0, "a tile must lie inside one coarse bin");
     // 8x8 tiles read the cell lists of cell_bin_kernel; walking the coarse bin (below) is their fallback -- a bin whose cell lists did
     // not fit the pool, or a caller without a binned workspace -- and gets by with the smallest staging area

@@ -152,10 +152,15 @@ VIZ_SIGNATURES = {
     'dbw_vertex_normals': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p],
     'dbw_render_lit_fwd': [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_i,
                            c_i, c_i, c_f, c_f, c_i, c_p, c_i, c_p, c_p, c_sz, c_p],
+    # scene parsing maps (csrc/scene_parse.hip), added under revision 1 of the header
+    'dbw_viz_parse_fwd': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p],
 }
 VIZ_OTHER_SIGNATURES = {
     'dbw_render_lit_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i, c_i]),
+    'dbw_viz_parse_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i]),
 }
+VIZ_MAX_LABELS = header_define('dbw_viz.h', 'DBW_VIZ_MAX_LABELS')
+VIZ_NO_LABEL = header_define('dbw_viz.h', 'DBW_VIZ_NO_LABEL')
 VIZ_ABI_VERSION = header_define('dbw_viz.h', 'DBW_VIZ_ABI_VERSION')
 
 # the 8-bit frame export: name -> argtypes, exactly the int-returning prototypes of include/dbw_export.h (checked by

@@ -550,6 +550,32 @@ class DifferentiableBlocksWorld(nn.Module):
         return torch.from_numpy(M.get_fancy_cmap()(values.numpy())).float().to(self.sq_eps.device)
 
     @torch.no_grad()
+    def parse_views(self, inp, filter_transparent=True, w_bkg=True):
+        """What the blocks world says is in the views of `inp` (its R, T; K on first use): -> parse.SceneParse with, per pixel, the label of
+        the part that is seen (0 sky, 1 ground, 2 + k block k in its ORIGINAL index, 255 nothing), its depth, and the word of all labels that
+        cover the pixel, seen or hidden -- the blocks' amodal masks -- plus per view and label the amodal and the visible area.  One hard
+        pass over sky, ground and blocks joined (w_bkg=False: without the sky dome), renderer.parse_packed.  A block that filter_transparent
+        or kill_blocks drops leaves its label unused.  An evaluation-time call like predict(w_edges=True): the scene is packed on the host
+        under sync_free too, and the per-step state of the last forward is left as it was."""
+        from .parse import LABEL_BLOCK0, LABEL_GROUND, LABEL_SKY, MAX_BLOCKS, SceneParse, default_palette
+        if self.n_blocks > MAX_BLOCKS:
+            raise NotImplementedError(f'{self.n_blocks} blocks: the coverage word has 64 bits, two of them for sky and ground')
+        self._ensure_cameras(inp)
+        with self._host_packed_rebuild():
+            scene = self.build_scene(filter_transparent=filter_transparent, w_bkg=w_bkg)
+        opac = self.get_opacities().cpu()
+        kept = opac > 0.5 if filter_transparent else (opac > 0.01 if self.kill_blocks else torch.ones_like(opac, dtype=torch.bool))
+        blocks = LABEL_BLOCK0 + kept.nonzero().flatten().to(torch.int32)
+        face_label = torch.cat([torch.full((self.bkg_n_faces if w_bkg else 0,), LABEL_SKY, dtype=torch.int32),
+                                torch.full((self.ground_n_faces,), LABEL_GROUND, dtype=torch.int32), blocks.repeat_interleave(self.BNF)])
+        if face_label.numel() != scene.faces.shape[0]:
+            raise RuntimeError(f'{face_label.numel()} labels for a scene of {scene.faces.shape[0]} faces: the kept blocks are not the packed ones')
+        label, depth, cover, counts = self.renderer.parse_packed(scene, face_label, inp['R'], inp['T'])
+        values = torch.linspace(0, 1, self.n_blocks + 1)[1:]
+        palette = default_palette(torch.from_numpy(M.get_fancy_cmap()(values.numpy())).float()[:, :3])
+        return SceneParse(label, depth, cover, counts, self.n_blocks, kept, palette)
+
+    @torch.no_grad()
     def get_arranged_block_txt(self):                                            # dbw.py:433-438
         maps = torch.sigmoid(self.textures).permute(0, 3, 1, 2)
         ncol, nrow = 5, len(maps) // 5
@@ -644,14 +670,15 @@ class DifferentiableBlocksWorld(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ qualitative evaluation (dbw.py:495-554)
     @torch.no_grad()
-    def qualitative_eval(self, loader, device, path=None, NV=240):
+    def qualitative_eval(self, loader, device, path=None, NV=240, parse=False):
         """The pictures, meshes and videos of a trained model, the file set of the reference (dbw.py:495-554), under `path`:
         textures/{bkg,ground,block_XX}.png; rotated_mesh.*; mesh_full.obj and mesh.obj (without the sky dome, reduced ground), each with its
         .mtl and .png; gt.ply (3000 points of loader.dataset.pc_gt under seed 123, where the dataset has one); and per input i (at most
         10): i_inp, i_rec, i_rec_col, i_rec_col_inp, i_rec_syn_nobkg, i_rec_syn_nobkg_edged .png and the two trajectories i_rec_traj.*,
         i_rec_traj_syn.* over R @ R_traj of get_circle_traj(N_views=NV).  Videos are mp4 where imageio imports, animated GIFs otherwise
         (export.save_video); rotated_mesh has NV views too (the reference's 240 is its NV).  Stops after the meshes when no block is
-        opaque.  `loader`: any iterable of (inp, labels); its batch_size, or the size of the first batch, numbers the inputs.  Every frame is
+        opaque.  parse=True adds <path>/parse/: the scene parsing maps of those inputs (parse_views, export.write_parse).
+        `loader`: any iterable of (inp, labels); its batch_size, or the size of the first batch, numbers the inputs.  Every frame is
         converted to 8 bits on the GPU (renderer.render_views_u8, ops.frames_u8).  The train / eval state is put back on exit.
         -> {'render': seconds in render + conversion + copy, 'encode': seconds in the file writers}."""
         import time
@@ -705,7 +732,7 @@ class DifferentiableBlocksWorld(nn.Module):
 
             renderer, renderer_light = self.renderer, self.renderer_light
             H, W = self.img_size
-            count, N = 0, 10
+            count, N, parses = 0, 10, []
             R_traj = get_circle_traj(N_views=NV)[0].to(device)
             n_zeros = int(np.log10(N - 1)) + 1
             BS = getattr(loader, 'batch_size', None)
@@ -736,7 +763,11 @@ class DifferentiableBlocksWorld(nn.Module):
                     timed('encode', export.save_video, frames, path / f'{i}_rec_traj.mp4')
                     frames = timed('render', render_views_u8, syn_blocks, R_v, T_v, renderer=renderer_light)
                     timed('encode', export.save_video, frames, path / f'{i}_rec_traj_syn.mp4')
+                if parse:
+                    parses.append(timed('render', self.parse_views, {**inp, 'R': R_src[:B], 'T': T_src[:B]}))
                 count += B
+            if parse:
+                timed('encode', export.write_parse, export.join_parses(parses), path / 'parse')
             return spent
         finally:
             self.train(was_training)

@@ -66,6 +66,45 @@ def save_video(frames_u8, path, fps=24):
     return save_gif(frames_u8, os.path.splitext(path)[0] + '.gif', fps=fps)
 
 
+def join_parses(parses):
+    """Several parse.SceneParse of the same model (one per batch of views) -> one over all their views, on the CPU."""
+    from .parse import SceneParse
+    parses = list(parses)
+    if not parses:
+        raise ValueError('no parse to join')
+    first = parses[0]
+    label, depth, cover, counts = [torch.cat([getattr(p, name).cpu() for p in parses], 0) for name in ('label', 'depth', 'cover', 'counts')]
+    return SceneParse(label, depth, cover, counts, first.n_blocks, first.kept, first.palette)
+
+
+def write_parse(parse, path):
+    """A parse.SceneParse -> the directory `path`: per view v label_%03d.png (the label map painted: parse.colors()), depth_%03d.npy
+    (H,W) float32 and cover_%03d.npy (H,W) int64; and block_visibility.tsv, a line of names and one line per block: `block`, `kept`, then
+    per view `amodal_v`, `visible_v` (pixels) and `occlusion_v` (1 - visible / amodal as '{:.5f}', 'nan' for a block the view does not
+    contain).  -> the list of the paths written."""
+    os.makedirs(str(path), exist_ok=True)
+    written = []
+    painted = parse.colors().cpu()
+    depth, cover = parse.depth.cpu().numpy(), parse.cover.cpu().numpy()
+    V = painted.shape[0]
+    for v in range(V):
+        written.append(save_png(painted[v], os.path.join(str(path), 'label_%03d.png' % v)))
+        for name, arr in (('depth', depth), ('cover', cover)):
+            written.append(os.path.join(str(path), '%s_%03d.npy' % (name, v)))
+            np.save(written[-1], arr[v])
+    amodal, visible = [t.cpu() for t in parse.areas()]
+    occ = parse.occlusion().cpu()
+    written.append(os.path.join(str(path), 'block_visibility.tsv'))
+    with open(written[-1], mode='w') as f:
+        f.write('\t'.join(['block', 'kept'] + [f'{name}_{v}' for v in range(V) for name in ('amodal', 'visible', 'occlusion')]) + '\n')
+        for k in range(parse.n_blocks):
+            cells = [str(k), str(int(parse.kept[k]))]
+            for v in range(V):
+                cells += [str(int(amodal[v, k])), str(int(visible[v, k])), '{:.5f}'.format(float(occ[v, k]))]
+            f.write('\t'.join(cells) + '\n')
+    return written
+
+
 def save_ply(path, points):
     """(n,3) points -> a binary little-endian PLY with float x, y, z (eval3d.read_ply_points reads it back).  -> path."""
     pts = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)

@@ -699,6 +699,44 @@ def render_scene_lit(verts, maps, faces_alpha, faces_i32, R, T, Kmat, face_uvs, 
     return img
 
 
+def parse_scene(verts, faces_i32, face_label, R, T, Kmat, cfg):
+    """Scene parsing maps of a packed scene for the len(R) views (include/dbw_viz.h: dbw_viz_parse_fwd), hard rasterisation at cfg.H x
+    cfg.W (cfg.K, cfg.sigma and cfg.blur are not looked at), no grad.  face_label: one label in [0, 64) per face of the scene.
+    -> label (B,H,W) uint8: label of the nearest face, 255 where there is none; depth (B,H,W) fp32: its view-space z, -1 where there is
+    none; cover (B,H,W) int64: bit l set where some face with label l covers the pixel, occluded or not; counts (B,64,2) int32: per view and
+    label [amodal area, visible area] in pixels.
+
+    Who checks the labels: a `face_label` on the CPU (a tensor or a sequence: the usual case, parse_views builds its table there) is handed to
+    the library as the host copy it validates before any launch, and uploaded; a tensor on the GPU is taken as it is -- its builder vouches
+    for it (the kernel folds a label into [0, 64), so a bad table gives wrong maps, never a wild access) -- and is never read back."""
+    lib = _viz_lib()
+    verts_c = _chk(verts.detach(), torch.float32, 'verts')
+    faces_c = _chk(faces_i32, torch.int32, 'faces')
+    dev = verts_c.device
+    B, F_ = R.shape[0], faces_c.shape[0]
+    host = None
+    if not (torch.is_tensor(face_label) and face_label.is_cuda):
+        host = torch.as_tensor(face_label).to(torch.int32).reshape(-1).contiguous()
+        lab = host.to(dev)
+    else:
+        lab = _chk(face_label, torch.int32, 'face_label').reshape(-1)
+    if lab.numel() != F_:
+        raise ValueError(f'face_label has {lab.numel()} entries for {F_} faces')
+    cl = project_clip(verts_c, faces_c, R, T, Kmat, cfg.eps, cfg.z_clip, cfg.persp)
+    fvc = cl['face_verts'].view(-1, 3, 3)
+    Ft = fvc.shape[0]
+    ws_bytes = lib.dbw_viz_parse_workspace_bytes(Ft, B, F_, cfg.H, cfg.W)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+    label = torch.empty(B, cfg.H, cfg.W, dtype=torch.uint8, device=dev)
+    depth = torch.empty(B, cfg.H, cfg.W, dtype=torch.float32, device=dev)
+    cover = torch.empty(B, cfg.H, cfg.W, dtype=torch.int64, device=dev)
+    counts = torch.empty(B, _lib.VIZ_MAX_LABELS, 2, dtype=torch.int32, device=dev)
+    _lib.call('dbw_viz_parse_fwd', _ptr(fvc), _ptr(cl['first_idx']), _ptr(cl['num_faces']), _ptr(cl['neighbor']), _ptr(cl['c2o']), 2 * F_, B, Ft,
+              cfg.H, cfg.W, F_, int(cfg.persp), _ptr(lab), _ptr(host), _ptr(label), _ptr(depth), _ptr(cover), _ptr(counts), _ptr(ws), ws_bytes,
+              _stream(verts_c))
+    return label, depth, cover, counts
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 8-bit frame export (include/dbw_export.h)
 # ---------------------------------------------------------------------------------------------------------------------

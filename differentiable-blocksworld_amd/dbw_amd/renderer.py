@@ -202,6 +202,19 @@ class Renderer(nn.Module):
         return ops.render_scene(scene.verts, scene.maps, faces_alpha, scene.faces, R, T, Kmat, scene.face_uvs, scene.face_map,
                                 scene.map_desc, self._bg, cfg)
 
+    @torch.no_grad()
+    def parse_packed(self, scene, face_label, R, T):
+        """Scene parsing maps of `scene` for the len(R) views at this renderer's image size, cameras and z_clip: -> (label, depth, cover,
+        counts) of ops.parse_scene.  face_label: one label in [0, 64) per face of the scene.  Hard rasterisation whatever the renderer's
+        sigma and faces_per_pixel are; lights and shading play no part."""
+        if self.cam_name != 'perspective' or self.cameras.K is None:
+            raise NotImplementedError('the HIP path needs perspective cameras with an explicit NDC K: call '
+                                      'update_cameras(K=...) first (dbw.py:204-208)')
+        Kmat = self.cameras.K[0].to(R.device).contiguous()
+        H, W = self.img_size
+        cfg = ops.RenderCfg(H, W, 1, 0.0, self.z_clip, self.perspective_correct, False, scene.faces.shape[0], EPS)
+        return ops.parse_scene(scene.verts, scene.faces, face_label, R.float().contiguous(), T.float().contiguous(), Kmat, cfg)
+
     def _render_lit(self, scene, R, T, Kmat, faces_alpha, viz_purpose):
         """Flat / Phong shading under this renderer's light, which follows the camera (renderer.py:87-89; `self.lights` itself is not
         touched).  viz_purpose: hard, one face per pixel, 4x4 super-samples resolved inside the kernel; else this renderer's own

@@ -6,7 +6,7 @@ Host-side scalars only; nothing here touches pixels.  The record of a run -- met
 runlog.RunRecorder's, which this loop calls when one is attached (`trainer.recorder`); without one the loop is what it was.  `evaluate`
 ends a run like the reference's trainer.py:241-272."""
 import time
-from collections import Counter
+from collections import Counter, OrderedDict
 
 import torch
 
@@ -192,23 +192,29 @@ class Trainer:
         return last
 
     # trainer.py:241-272
-    def evaluate(self, loader, run_dir, dtu=None, aligned=None):
+    def evaluate(self, loader, run_dir, dtu=None, aligned=None, parse=False, masks=None):
         """The end of a run: qualitative_eval into run_dir/quali_eval, quantitative_eval (hard inference) into run_dir/final_scores.tsv
         (a line of names, a line of values, '{:.5f}'), and -- dtu = dict(scale_mat=, scan_id=, dataset_dir=), further keywords of
         eval3d.evaluate_dtu allowed -- the official DTU scores of the blocks into run_dir; aligned = dict(points=, normals=), further
         keywords of eval3d.evaluate_aligned allowed -- the ICP-aligned Chamfer / normal scores against a ground-truth cloud in any frame
-        into run_dir/aligned_scores.tsv.  loader: an iterable of (inp, labels) that can be walked twice.  -> the scores (with the DTU dict
-        under 'dtu' and the aligned scores under 'aligned' where asked for)."""
+        into run_dir/aligned_scores.tsv.  parse=True: the scene parsing maps of the inputs into run_dir/quali_eval/parse
+        (model.parse_views, export.write_parse).  masks: ground-truth foreground masks of ALL views of the loader in its order, (V,H,W) or
+        (V,1,H,W), bool or 0 / 1, at the image size -- metrics.ProxyEvaluator scores the parse's foreground() (some block is what the
+        pixel shows) against them into run_dir/mask_scores.tsv, written like final_scores.tsv.  loader: an iterable of (inp, labels) that
+        can be walked twice (three times with masks).  -> the scores (with the DTU dict under 'dtu', the aligned scores under 'aligned'
+        and the mask scores under 'masks' where asked for)."""
         import os
         run_dir = str(run_dir)
         os.makedirs(os.path.join(run_dir, 'quali_eval'), exist_ok=True)
         device = self.views['imgs'].device
         self.model.eval()
-        self.model.qualitative_eval(loader, device, path=os.path.join(run_dir, 'quali_eval'))
+        self.model.qualitative_eval(loader, device, path=os.path.join(run_dir, 'quali_eval'), **({'parse': True} if parse else {}))
         scores = self.model.quantitative_eval(loader, device, hard_inference=True)
         with open(os.path.join(run_dir, 'final_scores.tsv'), mode='w') as f:
             f.write('\t'.join(scores.keys()) + '\n')
             f.write('\t'.join('{:.5f}'.format(float(v)) for v in scores.values()) + '\n')
+        if masks is not None:
+            scores = dict(scores, masks=self._mask_scores(loader, device, masks, run_dir))
         if dtu is not None:
             from .eval3d import evaluate_dtu
             scores = dict(scores, dtu=evaluate_dtu(self.model, eval_dir=run_dir, **dtu))
@@ -216,6 +222,30 @@ class Trainer:
             from .eval3d import evaluate_aligned
             scores = dict(scores, aligned=dict(evaluate_aligned(self.model, eval_dir=run_dir, **aligned)))
         return scores
+
+    def _mask_scores(self, loader, device, masks, run_dir):
+        """mask_iou of the parsed foreground against `masks` (evaluate's), view by view in the loader's order -> run_dir/mask_scores.tsv."""
+        import os
+        from .metrics import ProxyEvaluator
+        masks = torch.as_tensor(masks)
+        masks = masks[:, 0] if masks.dim() == 4 else masks
+        if masks.dim() != 3 or tuple(masks.shape[1:]) != tuple(self.model.img_size):
+            raise ValueError(f'masks are (V,H,W) or (V,1,H,W) at the image size {tuple(self.model.img_size)}, got {tuple(masks.shape)}')
+        ev, seen = ProxyEvaluator(), 0
+        for inp, _ in loader:
+            inp = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in inp.items()}
+            fg = self.model.parse_views(inp).foreground()
+            if seen + len(fg) > len(masks):
+                raise ValueError(f'{len(masks)} masks for more than {seen + len(fg) - 1} views')
+            ev.update(fg.float(), (masks[seen:seen + len(fg)].to(device) != 0).float())
+            seen += len(fg)
+        if seen != len(masks):
+            raise ValueError(f'{len(masks)} masks for {seen} views')
+        out = OrderedDict(zip(ev.names, ev.compute()))
+        with open(os.path.join(run_dir, 'mask_scores.tsv'), mode='w') as f:
+            f.write('\t'.join(out.keys()) + '\n')
+            f.write('\t'.join('{:.5f}'.format(float(v)) for v in out.values()) + '\n')
+        return out
 
     # trainer.py:201-209 / 84-107
     def state_dict(self):

@@ -12,8 +12,13 @@
 #define DBW_VIZ_H
 #include "dbw_hip.h"
 
-/* ABI revision of this header (dbw_viz_abi_version() returns the value the library was built with). */
+/* ABI revision of this header (dbw_viz_abi_version() returns the value the library was built with).  The scene parsing entry points
+ * (dbw_viz_parse_*) were ADDED under revision 1: nothing that existed changed its meaning or its layout, so the number stays. */
 #define DBW_VIZ_ABI_VERSION 1
+
+/* Scene parsing: labels are 0 .. DBW_VIZ_MAX_LABELS - 1 (one bit of the coverage word each); DBW_VIZ_NO_LABEL marks a pixel no face covers. */
+#define DBW_VIZ_MAX_LABELS 64
+#define DBW_VIZ_NO_LABEL 255
 
 #ifdef __cplusplus
 extern "C" {
@@ -55,6 +60,30 @@ int dbw_render_lit_fwd(const float *face_verts_c, const int32_t *first_idx, cons
                        const float *ambient3, const float *diffuse3, int N, int64_t F_total, int H, int W, int K, int F, float sigma,
                        float blur_radius, int perspective_correct, const float *background3, int ssaa, float *image, void *workspace,
                        size_t workspace_bytes, dbw_stream_t stream);
+
+/* Bytes of workspace dbw_viz_parse_fwd needs: the rasteriser's binned workspace at H x W and one label per clipped face.  0 for arguments
+ * the call would refuse. */
+size_t dbw_viz_parse_workspace_bytes(int64_t F_total, int N, int F, int H, int W);
+
+/* Scene parsing maps, one forward-only pass: which labelled part of the scene every pixel SEES, how far away it is, and every label that
+ * COVERS the pixel, occluded or not (amodal masks).  Hard rasterisation (sigma = 0, blur_radius = 0), no culling; the inside test, the depth
+ * and the order of the faces are the rasteriser's own ((pz, face index), dbw_rasterize_fwd with K = 1 and clipped barycentrics).
+ *   face_verts_c ... c2o, Fc_stride, N, F_total, H, W, F, perspective_correct: as in dbw_render_lit_fwd (c2o NULL: an unclipped table of
+ *     N * F faces); N, H, W > 0;
+ *   face_label (F) int32: one label in [0, DBW_VIZ_MAX_LABELS) per ORIGINAL face; clipped face f has the label of face c2o[f];
+ *   face_label_host: NULL, or a HOST copy of face_label.  The labels are validated on that copy, before any launch (an entry outside
+ *     [0, 64): DBW_ERR_INVALID); the device table is never read back.  With NULL the caller vouches for the table (ops.parse_scene always
+ *     passes the copy it built the device table from); an unchecked label is taken modulo 64 and nothing is accessed out of bounds;
+ *   label  (N,H,W) uint8 out: label of the nearest face, DBW_VIZ_NO_LABEL where no face passes;
+ *   depth  (N,H,W) fp32 out: view-space z of the nearest face -- what zbuf[..., 0] of dbw_rasterize_fwd holds -- or -1;
+ *   cover  (N,H,W) int64 out: bit l = some face with label l passes the inside test at the pixel (bit 63 is the sign bit);
+ *   counts (N,DBW_VIZ_MAX_LABELS,2) int32 out: per view and label [pixels covered (amodal area), pixels where it is the nearest (visible
+ *     area)].  Zeroed on `stream` by the call, summed with integer atomics: two calls are bit-equal;
+ *   workspace: 256-byte aligned, at least dbw_viz_parse_workspace_bytes(F_total, N, F, H, W) bytes. */
+int dbw_viz_parse_fwd(const float *face_verts_c, const int32_t *first_idx, const int32_t *num_faces, const int32_t *neighbor,
+                      const int32_t *c2o, int Fc_stride, int N, int64_t F_total, int H, int W, int F, int perspective_correct,
+                      const int32_t *face_label, const int32_t *face_label_host, uint8_t *label, float *depth, int64_t *cover,
+                      int32_t *counts, void *workspace, size_t workspace_bytes, dbw_stream_t stream);
 
 #ifdef __cplusplus
 }
