@@ -143,7 +143,13 @@ EVAL_SIGNATURES = {
     'dbw_dtu_lattice_counts': [c_p, c_i64, c_p, c_p],
     'dbw_dtu_lattice_points': [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p],
     'dbw_radius_downsample_round': [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_d, c_p, c_p, c_p],
+    # plane RANSAC (csrc/plane_fit.hip), added under revision 1 of the header
+    'dbw_eval_plane_fit': [c_p, c_i64, c_i, c_i, c_f, c_i64, c_p, c_p, c_f, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
 }
+EVAL_OTHER_SIGNATURES = {
+    'dbw_eval_plane_workspace_bytes': (c_sz, [c_i64, c_i]),
+}
+EVAL_PLANE_ORTHOGONAL, EVAL_PLANE_VERTICAL = 0, 1             # DBW_EVAL_PLANE_* of include/dbw_eval.h
 EVAL_ABI_VERSION = header_define('dbw_eval.h', 'DBW_EVAL_ABI_VERSION')
 
 # the lit visualisation renders: name -> argtypes, exactly the int-returning prototypes of include/dbw_viz.h (checked by
@@ -218,7 +224,7 @@ ICP_ABI_VERSION = header_define('dbw_icp.h', 'DBW_ICP_ABI_VERSION')
 # `what` completes "the loaded libdbw_hip.so has no ..." of family().
 Family = collections.namedtuple('Family', 'header macro version_fn signatures other_signatures what')
 FAMILIES = {
-    'eval': Family('dbw_eval.h', 'DBW_EVAL_ABI_VERSION', 'dbw_eval_abi_version', EVAL_SIGNATURES, {}, '3D evaluation entry points'),
+    'eval': Family('dbw_eval.h', 'DBW_EVAL_ABI_VERSION', 'dbw_eval_abi_version', EVAL_SIGNATURES, EVAL_OTHER_SIGNATURES, '3D evaluation entry points'),
     'viz': Family('dbw_viz.h', 'DBW_VIZ_ABI_VERSION', 'dbw_viz_abi_version', VIZ_SIGNATURES, VIZ_OTHER_SIGNATURES, 'lit render entry points'),
     'export': Family('dbw_export.h', 'DBW_EXPORT_ABI_VERSION', 'dbw_export_abi_version', EXPORT_SIGNATURES, {}, 'frame export entry point'),
     'ingest': Family('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION', 'dbw_ingest_abi_version', INGEST_SIGNATURES, INGEST_OTHER_SIGNATURES,
@@ -276,12 +282,14 @@ def load():
             continue
         getattr(lib, f.version_fn).restype = c_i
         for name, argtypes in f.signatures.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = c_i
+            if hasattr(lib, name):              # (a function added under a header's revision is absent from builds of older sources: family() says so)
+                fn = getattr(lib, name)
+                fn.argtypes = argtypes
+                fn.restype = c_i
         for name, (restype, argtypes) in f.other_signatures.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = argtypes, restype
+            if hasattr(lib, name):
+                fn = getattr(lib, name)
+                fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 
@@ -296,6 +304,12 @@ def family(name):
     got, want = getattr(lib, f.version_fn)(), header_define(f.header, f.macro)
     if got != want:
         raise RuntimeError(f'the library was built for {name} ABI {got}, include/{f.header} declares {want}: rebuild it')
+    # functions added under an unchanged revision: a library that holds some of the family's functions holds all of them
+    names = list(f.signatures) + list(f.other_signatures)
+    missing = [n for n in names if not hasattr(lib, n)]
+    if missing and len(missing) < len(names):
+        raise RuntimeError(f'the loaded libdbw_hip.so has the {name} family of include/{f.header} at revision {got} but not '
+                           f'{", ".join(missing)}: it was built from older sources, rebuild it')
     return lib
 
 

@@ -406,6 +406,7 @@ class CustomScene(_Scene):
 
         self.pc_gt = torch.zeros(1, 3)
         ply = path.parent / meta['ply_file_path'] if meta.get('ply_file_path') else path.parent / 'points.ply'
+        self.ply_file = ply if ply.exists() else None
         if ply.exists():
             from .eval3d import read_ply_points
             points = np.asarray(read_ply_points(ply), dtype=np.float64)
@@ -415,6 +416,17 @@ class CustomScene(_Scene):
                                   or (store.prepare is None) != (self.prepare is None)):
             raise ValueError('store: made for other files, another img_size or another lens treatment')
         self.store = store if store is not None else ImageStore(self.input_files, self.img_size, prepare=self.prepare)
+
+    def world_frame(self, device=None, T_range=(1, 1, 1), **kw):
+        """worldfit.estimate_world_frame on this capture's cloud and cameras (both in the normalised frame R, T live in) -> WorldFrame: the
+        R_world, T_world and S_world of model.mesh.  device: where the plane fit runs (a cuda device: the HIP kernel).  ValueError for a
+        capture without a cloud."""
+        from .worldfit import estimate_world_frame
+        if self.ply_file is None:
+            raise ValueError(f"'{self.tag}': no point cloud (ply_file_path of transforms.json, or points.ply next to it): the world frame is "
+                             'fitted to the cloud, there is no fit without one')
+        pts = self.pc_gt if device is None else self.pc_gt.to(device)
+        return estimate_world_frame(pts, self.cam2world, T_range=T_range, **kw)
 
     @staticmethod
     def _frame_file(folder, file_path):

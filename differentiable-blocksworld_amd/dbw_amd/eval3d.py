@@ -15,7 +15,11 @@ nearest neighbours, the DTU dense lattice and its radius downsample -- is HIP (c
     gradient_icp_torch(...)               the same loop in torch, any device and dtype: the CPU path and the yardstick of the GPU tests
     normalize_mesh(verts, faces, ...)     utils/mesh.py:25-44 for one mesh                             -> (verts, faces)
     evaluate_aligned(model, points, ...)  the ICP-aligned scores (metrics.MeshEvaluator) of a model's live blocks, aligned_scores.tsv
+    plane_ransac(points, ...)             robust plane fit: N points x H hypotheses in one call (dbw_eval_plane_fit) -> PlaneResult
+    plane_ransac_torch(...)               the same fit in torch, any device; dtype=torch.float64: the oracle of the tests
+    filter_ground(points, ...)            utils/ransac.py as dtu_3d_process.py:36-41 uses it           -> (points off the ground, (p0, p1, p2))
 """
+import collections
 import ctypes
 import math
 import os
@@ -709,3 +713,216 @@ def evaluate_aligned(model, points, normals=None, eval_dir=None, generator=None,
             f.write('\t'.join(scores.keys()) + '\n')
             f.write('\t'.join('{:.5f}'.format(float(v)) for v in scores.values()) + '\n')
     return scores
+
+
+# ------------------------------------------------------------------------------------------------ plane RANSAC
+PlaneResult = collections.namedtuple('PlaneResult', 'normal offset n_inliers best counts mask triples rounds')
+PlaneResult.__doc__ = """A plane fit, every field a tensor on the device of the points: normal (3,) and offset () fp64 (normal . p = offset on the
+plane; zeros when no hypothesis was admissible), n_inliers () int32 of the final plane, best () int32 (the winning hypothesis, -1: none),
+counts (H,) int32 or None (-1: degenerate or inadmissible), mask (N,) bool or None, triples (H,3) int32, rounds () int32 (refinement rounds
+done)."""
+PLANE_MODES = {'orthogonal': _lib.EVAL_PLANE_ORTHOGONAL, 'vertical': _lib.EVAL_PLANE_VERTICAL}
+PLANE_STREAM = 0x504C414E                # csrc/plane_math.h: PLANE_STREAM
+VERTICAL_THRESH = 0.001                  # ransac.py:32
+
+
+def plane_draw(seed, n_hyp, N):
+    """csrc/plane_math.h plane_draw for j = 0 .. n_hyp - 1 -> (n_hyp,3) int32 numpy: Philox4x32-10 with the counter (j, 0, 0, 'PLAN') and the
+    key (seed low, seed high), word k scaled to [0, N) by (word * N) >> 32."""
+    M32 = np.uint64(0xffffffff)
+    c = [np.arange(n_hyp, dtype=np.uint64), np.zeros(n_hyp, np.uint64), np.zeros(n_hyp, np.uint64), np.full(n_hyp, PLANE_STREAM, np.uint64)]
+    k0, k1 = np.uint64(int(seed) & 0xffffffff), np.uint64((int(seed) >> 32) & 0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & M32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+    return np.stack([(w * np.uint64(N)) >> np.uint64(32) for w in c[:3]], 1).astype(np.int32)
+
+
+def _plane_args(points, n_hyp, thresh, residual, up, max_tilt, cams, min_side, refine, triples):
+    if residual not in PLANE_MODES:
+        raise ValueError(f"plane_ransac: residual must be 'orthogonal' or 'vertical', got {residual!r}")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'plane_ransac: points (N,3) expected, got {tuple(points.shape)}')
+    N = points.shape[0]
+    if triples is not None:
+        triples = torch.as_tensor(triples).to(device=points.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        n_hyp = triples.shape[0]
+    n_hyp, refine = int(n_hyp), int(refine)
+    if not (1 <= n_hyp <= 4096 and 3 <= N < 2 ** 31 and 0 <= refine <= 8):
+        raise ValueError(f'plane_ransac: 1 <= n_hyp <= 4096, 3 <= N < 2^31 and 0 <= refine <= 8 expected, got n_hyp={n_hyp}, N={N}, refine={refine}')
+    mode = PLANE_MODES[residual]
+    if thresh is None:
+        if mode == _lib.EVAL_PLANE_VERTICAL:
+            thresh = VERTICAL_THRESH
+        else:                                # (one host read: give thresh to avoid it) 1 % of the bounding box's diagonal
+            thresh = 0.01 * float((points.max(0).values.double() - points.min(0).values.double()).norm())
+    thresh = float(np.float32(thresh))
+    if not (thresh > 0 and math.isfinite(thresh)):
+        raise ValueError(f'plane_ransac: thresh must be positive and finite, got {thresh}')
+    tau = thresh if mode == _lib.EVAL_PLANE_ORTHOGONAL else 0.0
+    thresh2 = float(np.float32(thresh) * np.float32(thresh)) if mode == _lib.EVAL_PLANE_ORTHOGONAL else thresh
+    if not thresh2 > 0:
+        raise ValueError(f'plane_ransac: thresh {thresh} squares to 0 in fp32')
+    cos_tilt, min_cams = 0.0, 0
+    if mode == _lib.EVAL_PLANE_VERTICAL:
+        up, cams, refine = None, None, 0
+    if up is not None:
+        up = torch.as_tensor(up).detach().to(device=points.device, dtype=torch.float32).reshape(3).contiguous()
+        cos_tilt = float(np.float32(math.cos(math.radians(float(max_tilt)))))
+    if cams is not None:
+        cams = torch.as_tensor(cams).detach().to(device=points.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+        if not 1 <= cams.shape[0] <= 65536:
+            raise ValueError(f'plane_ransac: 1 to 65536 camera centres expected, got {cams.shape[0]}')
+        min_cams = min(cams.shape[0], max(0, math.ceil(float(min_side) * cams.shape[0] - 1e-9)))
+    return n_hyp, mode, thresh2, tau, up, cos_tilt, cams, min_cams, refine, triples
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _plane_hypotheses(tri_pts, mode, up, cos_tilt, cams, tau, min_cams, dt):
+    """csrc/plane_math.h plane_from_triple and plane_admissible on (H,3,3) points in dtype dt, expression by expression -> (planes (H,4),
+    valid (H,) bool).  Computed on the CPU, where every torch op is one IEEE rounding: the fp32 planes are those of the kernel, bit for bit."""
+    a, b, c = tri_pts[:, 0], tri_pts[:, 1], tri_pts[:, 2]
+    e1, e2 = b - a, c - a
+    m = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    L2 = _dot3(m, m)
+    valid = (L2 < math.inf) & ~(L2 <= torch.tensor(1e-8, dtype=dt) * (_dot3(e1, e1) * _dot3(e2, e2)))
+    if mode == _lib.EVAL_PLANE_VERTICAL:
+        valid = valid & (m[:, 2] != 0)
+        n = m / m[:, 2:3]
+    else:
+        n = m / L2.sqrt()[:, None]
+        if up is not None:
+            n = torch.where((_dot3(n, up[None]) < 0)[:, None], -n, n)
+    d = _dot3(n, a)
+    if mode == _lib.EVAL_PLANE_ORTHOGONAL:
+        if up is not None:
+            valid = valid & (_dot3(n, up[None]) >= cos_tilt)
+        if cams is not None:
+            r = ((n[:, None, 0] * cams[None, :, 0] + n[:, None, 1] * cams[None, :, 1]) + n[:, None, 2] * cams[None, :, 2]) - d[:, None]
+            valid = valid & ((r > tau).sum(1) >= min_cams)
+    planes = torch.cat([n, d[:, None]], 1)
+    return torch.where(valid[:, None], planes, torch.zeros_like(planes)), valid
+
+
+def _plane_inliers(pl, x, y, z, thresh2):
+    r = ((pl[0] * x + pl[1] * y) + pl[2] * z) - pl[3]
+    return r * r < thresh2
+
+
+def plane_ransac_torch(points, n_hyp=512, thresh=None, residual='orthogonal', up=None, max_tilt=60.0, cams=None, min_side=0.9, refine=2, seed=0,
+                       triples=None, return_counts=False, return_mask=False, dtype=torch.float32, chunk_elems=1 << 24):
+    """plane_ransac in torch, on any device: the triples of csrc/plane_math.h's plane_draw, the hypotheses and their priors expression by
+    expression (on the CPU: H x a few numbers), the scoring in chunks of hypotheses that materialise a (chunk, N) residual matrix as the
+    reference's batches do, the refinement in fp64 with torch.linalg.eigh.  dtype=torch.float32 states the kernel's arithmetic: the same
+    counts and the same best hypothesis on the CPU (on a device torch's own kernels have been seen a point off at the threshold); dtype=torch.float64 does everything in fp64 and is the oracle of the tests.  Reads the best index to
+    the host."""
+    n_hyp, mode, thresh2, tau, up, cos_tilt, cams, min_cams, refine, triples = _plane_args(points, n_hyp, thresh, residual, up, max_tilt, cams,
+                                                                                          min_side, refine, triples)
+    dev, N = points.device, points.shape[0]
+    pts = points.detach().to(torch.float32)
+    if triples is None:
+        triples = torch.from_numpy(plane_draw(seed, n_hyp, N)).to(dev)
+    t64 = triples.to(torch.int64)
+    in_range = ((t64 >= 0) & (t64 < N)).all(1)
+    tri_pts = pts[t64.clamp(0, N - 1).reshape(-1)].reshape(n_hyp, 3, 3).cpu().to(dtype)
+    cpu = lambda t: None if t is None else t.cpu().to(dtype)                    # noqa: E731
+    th2 = torch.tensor(thresh2, dtype=dtype)
+    planes, valid = _plane_hypotheses(tri_pts, mode, cpu(up), torch.tensor(cos_tilt, dtype=dtype), cpu(cams), torch.tensor(tau, dtype=dtype),
+                                      min_cams, dtype)
+    planes, valid, th2 = planes.to(dev), valid.to(dev) & in_range, th2.to(dev)
+    x, y, z = (pts[:, k].to(dtype) for k in range(3))
+    counts = torch.empty(n_hyp, dtype=torch.int32, device=dev)
+    step = max(1, chunk_elems // N)
+    for a in range(0, n_hyp, step):
+        pl = planes[a:a + step]
+        r = ((pl[:, 0:1] * x[None] + pl[:, 1:2] * y[None]) + pl[:, 2:3] * z[None]) - pl[:, 3:4]
+        counts[a:a + step] = (r * r < th2).sum(1)
+    counts = torch.where(valid, counts, torch.full_like(counts, -1))
+    top = counts.max()
+    best = int(torch.where(counts == top, torch.arange(n_hyp, device=dev), n_hyp).min()) if int(top) >= 0 else -1
+    plane = torch.zeros(4, dtype=torch.float64, device=dev)
+    rounds = 0
+    if best >= 0:
+        plane = planes[best].to(torch.float64)
+        a0 = pts[t64[best, 0]].to(torch.float64)
+        for _ in range(refine):
+            inl = _plane_inliers(plane.to(dtype), x, y, z, th2)
+            q = pts[inl].to(torch.float64) - a0
+            if q.shape[0] < 3:
+                break
+            mean = q.sum(0) / q.shape[0]
+            cov = (q.T @ q) / q.shape[0] - mean[:, None] * mean[None]
+            v = torch.linalg.eigh(cov).eigenvectors[:, 0]
+            v = torch.where((v * plane[:3]).sum() < 0, -v, v)
+            plane = torch.cat([v, (v * (a0 + mean)).sum()[None]])
+            rounds += 1
+        mask = _plane_inliers(plane.to(dtype), x, y, z, th2)
+    else:
+        mask = torch.zeros(N, dtype=torch.bool, device=dev)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)              # noqa: E731
+    return PlaneResult(plane[:3], plane[3], mask.sum().to(torch.int32), i32(best), counts if return_counts else None,
+                       mask if return_mask else None, triples, i32(rounds))
+
+
+def plane_fit(points, n_hyp, mode, thresh2, seed=0, triples=None, up=None, cos_tilt=0.0, cams=None, tau=0.0, min_cams=0, refine=0,
+              with_counts=True, with_mask=True):
+    """dbw_eval_plane_fit on device tensors, arguments as in include/dbw_eval.h (points (N,3) fp32 contiguous; triples int32; up, cams fp32)
+    -> dict(plane (4,) fp64, info (4,) int32, counts (H,) int32 or None, triples (H,3) int32, mask (N,) uint8 or None).  Everything is
+    enqueued on the current stream; nothing is read by the host."""
+    dev, N = points.device, points.shape[0]
+    lib = _lib.family('eval')
+    nbytes = lib.dbw_eval_plane_workspace_bytes(N, int(n_hyp))
+    if nbytes == 0:
+        raise ValueError(f'plane_fit: sizes N={N}, H={n_hyp} are refused (1 <= H <= 4096, 3 <= N < 2^31)')
+    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    out = dict(plane=torch.empty(4, dtype=torch.float64, device=dev), info=torch.empty(4, dtype=torch.int32, device=dev),
+               counts=torch.empty(n_hyp, dtype=torch.int32, device=dev) if with_counts else None,
+               triples=torch.empty(n_hyp, 3, dtype=torch.int32, device=dev),
+               mask=torch.empty(N, dtype=torch.uint8, device=dev) if with_mask else None)
+    seed = int(seed) & 0xffffffffffffffff
+    seed = seed - (1 << 64) if seed >= 1 << 63 else seed                        # the 64 bits, as the int64_t of the prototype
+    with torch.cuda.device(dev):
+        _call('dbw_eval_plane_fit', _p(points), N, int(n_hyp), int(mode), float(thresh2), seed, _p(triples), _p(up), float(cos_tilt), _p(cams),
+              0 if cams is None else cams.shape[0], float(tau), int(min_cams), int(refine), _p(ws), _p(out['plane']), _p(out['info']),
+              _p(out['counts']), _p(out['triples']), _p(out['mask']), _stream(dev))
+    return out
+
+
+def plane_ransac(points, n_hyp=512, thresh=None, residual='orthogonal', up=None, max_tilt=60.0, cams=None, min_side=0.9, refine=2, seed=0,
+                 triples=None, return_counts=False, return_mask=False):
+    """Robust plane fit of a cloud (N,3): n_hyp planes through random triples of points (or through the rows of `triples` (H,3)), each scored
+    by its number of inliers among all N points, the best one (lowest index on ties) refined -> PlaneResult.
+
+    residual 'orthogonal': unit normal, a point is an inlier iff its distance is below `thresh` (None: 1 % of the bounding box's diagonal,
+    which costs one host read); `refine` rounds refit the plane to its inliers (smallest eigenvector of their covariance, fp64).  Priors:
+    with `up` (3,), the normal points to the side of up and its tilt against it is at most `max_tilt` degrees; with `cams` (M,3), at least
+    ceil(min_side * M) camera centres lie more than `thresh` above the plane.  residual 'vertical': the reference's regression
+    z = p0 + p1 x + p2 y through the triple (ransac.py), inlier iff the SQUARED residual is below `thresh` (None: 0.001); no priors, no
+    refinement; normal = (-p1, -p2, 1), offset = p0.
+
+    Device tensors run csrc/plane_fit.hip in one call with no host read (the result's fields are device tensors), CPU tensors
+    plane_ransac_torch.  The draw of the triples is a function of (seed, hypothesis index, N) alone, the same on both paths."""
+    if points.device.type == 'cpu':
+        return plane_ransac_torch(points, n_hyp, thresh, residual, up, max_tilt, cams, min_side, refine, seed, triples, return_counts, return_mask)
+    n_hyp, mode, thresh2, tau, up, cos_tilt, cams, min_cams, refine, triples = _plane_args(points, n_hyp, thresh, residual, up, max_tilt, cams,
+                                                                                          min_side, refine, triples)
+    pts = points.detach().to(torch.float32).contiguous()
+    o = plane_fit(pts, n_hyp, mode, thresh2, seed, triples, up, cos_tilt, cams, tau, min_cams, refine, with_counts=return_counts,
+                  with_mask=return_mask)
+    return PlaneResult(o['plane'][:3], o['plane'][3], o['info'][2], o['info'][0], o['counts'], None if o['mask'] is None else o['mask'].bool(),
+                       o['triples'], o['info'][3])
+
+
+def filter_ground(points, thresh=VERTICAL_THRESH, n_iter=100, seed=0, batch_size=10, triples=None):
+    """The ground filter of dtu_3d_process.py:36-41: Ransac() of utils/ransac.py fits z = p0 + p1 x + p2 y to the cloud (n_iter // batch_size
+    * batch_size hypotheses, each the plane through three points; the first hypothesis with the most inliers wins), and the points whose
+    squared residual is below `thresh` are dropped -> (points[~inlier], (p0, p1, p2) as a (3,) fp64 tensor).  The triples are this
+    package's counter-based draw, not torch.randint's, unless `triples` (H,3) gives them."""
+    n_hyp = int(n_iter) // int(batch_size) * int(batch_size)
+    res = plane_ransac(points, n_hyp=n_hyp, thresh=thresh, residual='vertical', refine=0, seed=seed, triples=triples, return_mask=True)
+    params = torch.stack([res.offset, -res.normal[0], -res.normal[1]])
+    return points[~res.mask], params

@@ -11,6 +11,9 @@ split, the image logs, model.pkl at every validation tick, model_<epoch>.pkl at 
 writes model.pkl at the end only.  training.resume: TAG (or --resume [TAG], default: this run's tag) continues the run of
 <runs-root>/<dataset>/<TAG>/model.pkl where it stopped; training.pretrained: TAG starts from that run's weights.
 
+model.mesh.R_world: auto (T_world: auto and S_world: auto beside it) on a custom scene with a point cloud: the three entries are estimated from
+the cloud and the cameras (worldfit.estimate_world_frame), printed and written to <run_dir>/world_frame.yml before the model is built.
+
 The perceptual term needs the weights of a VGG16 and of the LPIPS heads, which do not ship with the package: a config with
 perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so)."""
 import argparse
@@ -54,9 +57,52 @@ def prepare_config(args):
     return cfg
 
 
+WORLD_KEYS = ('R_world', 'T_world', 'S_world')
+
+
+def wants_world_frame(cfg):
+    """True where model.mesh says `R_world: auto` (T_world: auto and S_world: auto are accepted beside it, and only beside it)."""
+    mesh = cfg.get('model', {}).get('mesh') or {}
+    autos = [k for k in WORLD_KEYS if isinstance(mesh.get(k), str)]
+    bad = [k for k in autos if mesh[k] != 'auto']
+    if bad:
+        raise SystemExit(f"model.mesh.{bad[0]}: '{mesh[bad[0]]}' is neither numbers nor 'auto'")
+    if autos and 'R_world' not in autos:
+        raise SystemExit(f"model.mesh.{autos[0]}: auto goes with R_world: auto (the three are estimated together from the scene's point cloud)")
+    return bool(autos)
+
+
+def resolve_world_frame(cfg, scene, device, run_dir=None, resume=None):
+    """Replaces the `auto` entries of cfg['model']['mesh'] by numbers, in place: the three entries of the checkpoint `resume` (a path:
+    its model_kwargs carry them, a resumed run does not fit again), or the estimate of scene.world_frame, which is printed and written to
+    <run_dir>/world_frame.yml.  A scene without a cloud, and the scale_mat-normalised DTU / BlendedMVS scenes, are refused."""
+    if not wants_world_frame(cfg):
+        return None
+    mesh = cfg['model']['mesh']
+    if resume is not None:
+        kept = torch.load(resume, map_location='cpu', weights_only=False)['model_kwargs']['mesh']
+        mesh.update({k: kept[k] for k in WORLD_KEYS})
+        print(f"R_world: auto -> the world frame of {resume}: " + ', '.join(f'{k}={mesh[k]}' for k in WORLD_KEYS))
+        return None
+    if not hasattr(scene, 'world_frame'):
+        raise SystemExit(f"model.mesh.R_world: auto is for custom scenes: a '{scene.name}' scene is normalised by its scale_mat, and the "
+                         'R_world, T_world, S_world its config ships with hold')
+    try:
+        frame = scene.world_frame(device, T_range=mesh.get('T_range', (1, 1, 1)))
+    except ValueError as e:
+        raise SystemExit(f'model.mesh.R_world: auto: {e}') from e
+    mesh.update(frame.mesh_kwargs())
+    print(f'R_world: auto -> {frame}')
+    if run_dir is not None:
+        with open(os.path.join(run_dir, 'world_frame.yml'), 'w') as f:
+            f.write(frame.yaml())
+    return frame
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = prepare_config(args)
+    wants_world_frame(cfg)                      # (a malformed entry is refused before anything is read)
     from . import create_model
     from .dataset import create_train_val_test
     from .runlog import RunRecorder, resolve_start
@@ -73,6 +119,7 @@ def main(argv=None):
     seed = cfg['training'].get('seed', 4321)
     torch.manual_seed(seed)
     train, val, test = create_train_val_test(cfg, args.data_root, args.device)
+    resolve_world_frame(cfg, train, args.device, run_dir, start.get('resume'))
     model = create_model(cfg, train.img_size).to(args.device).train()
     if 'perceptual' in model.loss_weights:
         from .lpips_vgg import LPIPSVGG

@@ -45,6 +45,29 @@ int dbw_dtu_lattice_points(const double *tri, int64_t F, const int64_t *counts, 
 int dbw_radius_downsample_round(const double *points, const int64_t *cell_keys, const int64_t *rank, int64_t n, int64_t ny, int64_t nz,
                                 double radius, const int32_t *status_in, int32_t *status_out, dbw_stream_t stream);
 
+/* Plane RANSAC on a point cloud (csrc/plane_fit.hip, arithmetic csrc/plane_math.h; reference src/utils/ransac.py and the ground filter of
+ * src/dtu_3d_process.py:36-41), added under revision 1 of this header.  points (N,3) fp32; H hypotheses, each the plane through three
+ * points: the rows of triples (H,3) int32, or (NULL) those drawn by Philox4x32-10 from `seed` (its 64 bits; the type is int64_t for the
+ * sake of plain-C bindings) and the hypothesis index.  A plane is (n, d), the residual of p is ((n.x*p.x + n.y*p.y) + n.z*p.z) - d, p is an
+ * inlier iff residual^2 < thresh2.
+ *   mode DBW_EVAL_PLANE_ORTHOGONAL: n is the unit normal (turned to n.up >= 0 when up (3) is given), thresh2 = tau^2.  Priors: with up, a
+ *     hypothesis needs n.up >= cos_tilt; with cams (M,3), at least min_cams camera centres with residual > tau.
+ *   mode DBW_EVAL_PLANE_VERTICAL: the reference's regression z = p0 + p1 x + p2 y as the plane n = (-p1, -p2, 1), d = p0; thresh2 is the
+ *     reference's `thresh`.  up, cams and refine are not used.
+ * A triple with a repeated index, (nearly) collinear points or, in the vertical mode, a vertical triangle is degenerate.  The best
+ * hypothesis has the most inliers, the lowest index on ties.  refine (0..8) rounds, orthogonal mode only: the plane is refitted to its
+ * inliers among all N points (smallest eigenvector of their fp64 covariance), stopping early below 3 inliers.
+ * Outputs: plane (4) fp64 = n, d (zero if no hypothesis is admissible: the call still returns 0); info (4) int32 = best hypothesis or -1,
+ * its count, the inlier count of the final plane, refinement rounds done; counts (H) int32 or NULL, -1 for a degenerate or inadmissible
+ * hypothesis; triples_out (H,3) int32 or NULL; mask (N) uint8 or NULL, the inliers of the final plane (rounded to fp32).
+ * 1 <= H <= 4096, 3 <= N < 2^31, M <= 65536.  workspace: dbw_eval_plane_workspace_bytes(N, H) bytes (0: sizes refused), 16-byte aligned. */
+#define DBW_EVAL_PLANE_ORTHOGONAL 0
+#define DBW_EVAL_PLANE_VERTICAL 1
+size_t dbw_eval_plane_workspace_bytes(int64_t N, int H);
+int dbw_eval_plane_fit(const float *points, int64_t N, int H, int mode, float thresh2, int64_t seed, const int32_t *triples, const float *up,
+                       float cos_tilt, const float *cams, int M, float tau, int min_cams, int refine, void *workspace, double *plane,
+                       int32_t *info, int32_t *counts, int32_t *triples_out, uint8_t *mask, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
