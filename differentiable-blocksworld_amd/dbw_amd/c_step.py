@@ -6,7 +6,7 @@ the model once (pointers into the flat parameter / gradient buffers, the constan
 training phase) and then makes one call per iteration; the library enqueues ~16 launches on two streams (csrc/train_step.hip).
 
 Same mathematics as NativeStep (which is checked against the autograd iteration, which is checked against the oracle):
-tests/test_gpu_model.py::test_c_step_equals_native_step holds them to each other for every fuse mask.  Scope = NativeStep's: the decoupled
+tests/test_gpu_c_step.py::test_c_step_equals_native_step holds them to each other for every fuse mask.  Scope = NativeStep's: the decoupled
 training render with MSE + parsimony + TV + overlap on a sync-free model; anything else -> `supported()` is False."""
 import ctypes
 import os
@@ -15,7 +15,7 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, phase
 from .dbw import OVERLAP_N_BLOCKS, OVERLAP_N_POINTS, OVERLAP_TEMPERATURE
 
 _p = ops._ptr
@@ -26,8 +26,9 @@ _OFF = {'alpha': 0, 'alpha_full': 1, 'keep': 2, 'losses': 3, 'arena_begin': 4, '
 
 
 def side_stream(dev, priority=True):
-    """ONE side stream per process, device and priority (torch hands streams out of a pool round-robin and HIP multiplexes them onto a few
-    hardware queues: see native_step.py)."""
+    """ONE side stream per process, device and priority, for NativeStep, CStep and the data-parallel driver alike: torch hands streams out
+    of a pool round-robin and HIP multiplexes them onto a few hardware queues -- the fourth / fifth NativeStep of a process used to get a
+    stream that shares its queue with the main stream, and its steps took 2.1 ms instead of 1.2 (tools/diag/degrade.py)."""
     key = (dev.index, bool(priority))
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev, priority=-1 if priority else 0)
@@ -83,7 +84,6 @@ class CStep:
         self._pid = os.getpid()
         self._cur = None
         self._target, self._target_key = None, None
-        self._env_key = None
         self._inp = _lib.StepInputs()
         self._clean_plan = None             # handle of the plan whose arena a caller cleared itself (arena_cleaned_by_caller)
         self._calls = 0                     # default counter of the step's random numbers (callers with a step count of their own pass it)
@@ -91,18 +91,13 @@ class CStep:
 
     # ---- what the plan covers -----------------------------------------------------------------------------------------------------------
     def supported(self):
-        m, w = self.m, self.m.loss_weights
-        r = m.renderer
+        m = self.m
         # (the perceptual term: a network of the caller's evaluated between two phases of the step -- needs the env layer inside the fg pass)
-        perceptual_ok = 'perceptual' not in w or (m.perceptual_fn is not None and (self.fuse & 18) == 18)
-        # (clip_inside = False, the sigmoid opacity, travels as a negative sigma that dbw_train_step_create refuses: the autograd path has it)
-        ok = (m.decouple_rendering and m.sync_free and 'rgb' in w and perceptual_ok and r.detach_bary and r.faces_per_pixel > 1
-              and r.clip_inside and getattr(m.renderer_fine, 'clip_inside', True) and getattr(m, 'default_criteria', True)
-              and r.cam_name == 'perspective' and m.blocks_n_faces < (1 << 20) and m.n_blocks + 2 < (1 << 11) and m.n_blocks <= 64
-              and ops.FUSED_FORWARD and ops.FUSED_BACKWARD and ops.TILED_FRAGMENTS and ops.UV_FRAGMENTS and ops.HARD_UV_FRAGMENTS
-              and ops.COARSE_BINS and ops.TEXTURE_BINS)
-        lib = _lib.load()
-        return bool(ok and hasattr(lib, 'dbw_train_step_run'))
+        perceptual_ok = 'perceptual' not in m.loss_weights or (m.perceptual_fn is not None and (self.fuse & 18) == 18)
+        # (clip_inside = False, the sigmoid opacity, would travel as a negative sigma that dbw_train_step_create refuses: the shared predicate)
+        ok = (m.sync_free and perceptual_ok and m.n_blocks <= 64 and ops.HARD_UV_FRAGMENTS and ops.COARSE_BINS and ops.TEXTURE_BINS
+              and phase.fast_path_refusal(m) is None)
+        return bool(ok and hasattr(_lib.load(), 'dbw_train_step_run'))
 
     def _plan_handle(self):
         return self._cur[0]
@@ -123,10 +118,8 @@ class CStep:
 
     def _plan_for(self, inp, B, defer=False):
         m = self.m
-        coarse = m.is_live('coarse_learning')
-        decim = int(m.decim_factor) if m.is_live('decimate_txt') else 1
-        decim_blocks = decim if coarse else 1
-        renderer = m.renderer if coarse else m.renderer_fine
+        ph = self._phase = phase.phase_of(m, defer=defer)
+        renderer = m.renderer_fine if ph.fine_renderer else m.renderer
         dev = inp['imgs'].device
         Kt = renderer.cameras.K
         seq = self.backward_order
@@ -139,7 +132,7 @@ class CStep:
             both = m.world_size == 1
         # ONE plan (and one workspace) per phase / configuration, whatever the batch size: a plan runs any B up to its max_views, so a
         # ragged last mini-batch or a smaller shard reuses the plan of the full batch; only a LARGER batch replaces it
-        key = (coarse, decim, decim_blocks, m.world_size, self.fuse, int(seq), int(bool(both)), Kt.data_ptr(), m.R_world.data_ptr(),
+        key = (ph, m.world_size, self.fuse, int(seq), int(bool(both)), Kt.data_ptr(), m.R_world.data_ptr(),
                m.R_world._version, m.T_world._version, float(m.S_world),
                self.params.flat.data_ptr(), tuple(sorted(m.loss_weights.items())), float(m.opacity_noise or 0.0), bool(m.kill_blocks),
                int(self.serial_setup_max_views), bool(self.sync_events), bool(defer))
@@ -156,9 +149,6 @@ class CStep:
             if self._clean_plan == have[0]:
                 self._clean_plan = None
             del self._plans[key]
-        w = m.loss_weights
-        rs = 1.0 / m.world_size
-        fine = not coarse
         S_w, R_w, T_w = m._world_consts()
         TS, u_, nb = m.txt_size, m.txt_bkg_upscale, m.n_blocks
         keep = []                                   # tensors the plan points into
@@ -168,41 +158,35 @@ class CStep:
         d.n_blocks, d.block_nv, d.block_nf = nb, m._block_nv, m.BNF
         d.n_sky_verts, d.n_ground_verts = m._bkg_verts.shape[0], m._ground_base.shape[0]
         d.n_sky_faces, d.n_ground_faces = m._n_bkg_faces, m._n_ground_faces
-        d.txt_size, d.env_txt_size, d.decim_env, d.decim_blocks, d.coarse = TS, TS * u_, decim, decim_blocks, int(coarse)
+        d.txt_size, d.env_txt_size, d.decim_env, d.decim_blocks, d.coarse = TS, TS * u_, ph.decim_env, ph.decim_blocks, int(ph.coarse)
         cfg = renderer._cfg(nb * m.BNF)
         d.sigma, d.blur_radius = float(cfg.sigma), float(cfg.blur)
         d.z_clip, d.cam_eps, d.perspective_correct = float(cfg.z_clip or 0.0), float(cfg.eps), int(cfg.persp)
         for i in range(3):
             d.bg_fg[i], d.bg_env[i] = float(renderer.background_color[i]), float(m.renderer_env.background_color[i])
         d.S_world, d.ratio_block_scene, d.scale_min = float(S_w), float(m.ratio_block_scene), float(m.scale_min)
-        d.opacity_noise = float(m.opacity_noise) if (m.opacity_noise and coarse) else 0.0
-        masked = fine or m.kill_blocks
-        d.mask_threshold = (0.5 if fine else 0.01) if masked else -1.0
-        tv_f = 1.0 if coarse else 0.1
+        d.opacity_noise, d.mask_threshold = ph.noise_scale, ph.mask_threshold
         # (deferred texture gradients: the TV gradient is added on every rank BEHIND the all-reduce -- full weight in the kernels, the reported
         # value scaled instead, include/dbw_hip.h: tv_value_scale)
-        tv = float(w['tv']) * tv_f * (1.0 if defer else rs) if 'tv' in w else 0.0
-        d.tv_value_scale = rs if defer else 1.0
-        d.w_rgb = float(w['rgb'])
-        d.w_parsimony = float(w['parsimony']) * rs if ('parsimony' in w and coarse) else 0.0
-        d.w_tv_bkg, d.w_tv_blocks, d.w_tv_ground = tv, tv, tv * tv_f
-        d.w_overlap = float(w['overlap']) * rs if ('overlap' in w and coarse) else 0.0
+        d.tv_value_scale = ph.tv_value_scale
+        d.w_rgb, d.w_parsimony, d.w_overlap = ph.w_rgb, ph.w_parsimony or 0.0, ph.w_overlap or 0.0
+        d.w_tv_bkg, d.w_tv_blocks, d.w_tv_ground = (row[3] for row in ph.texture_rows())
         d.overlap_points, d.overlap_temperature, d.overlap_n_blocks = OVERLAP_N_POINTS, OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS
         # constant tables
         Kmat = Kt[0].to(dev).contiguous()
         nbv = m._bkg_verts.shape[0]
         env_verts = torch.empty(nbv + m._ground_base.shape[0], 3, device=dev)
-        env_verts[:nbv] = ((m._bkg_verts * S_w) @ R_w + T_w)
-        desc_e = m._env_map_desc if decim == 1 else m._env_map_desc_dec
-        desc_f = m._block_map_desc_all if decim_blocks == 1 else m._block_map_desc_dec
+        env_verts[:nbv] = m.sky_world_verts()
+        desc_e, desc_f = phase.env_map_desc(m, ph), phase.block_map_desc(m, ph)
         keep += [R_w, T_w, Kmat, env_verts]
         d.R_world, d.T_world, d.Kmat = _p(R_w), _p(T_w), _p(Kmat)
         d.ground_base, d.env_verts = _p(m._ground_base), _p(env_verts)
         d.env_faces, d.env_face_uvs, d.env_face_map, d.env_map_desc = _p(m._env_faces), _p(m._env_face_uvs), _p(m._env_face_map), _p(desc_e)
         d.trig, d.block_faces, d.block_face_uvs = _p(m._trig), _p(m._block_faces_all), _p(m._block_face_uvs_all)
         d.block_face_map, d.block_map_desc = _p(m._block_face_map_all), _p(desc_f)
-        if decim_blocks == 1:
-            d.block_bin_base, d.block_bin_info, d.n_bins = _p(m._block_bin_base), _p(m._block_bin_info), nb * m._bins_per_block
+        texbins = phase.block_texbins(m, ph, nb)
+        if texbins is not None:
+            d.block_bin_base, d.block_bin_info, d.n_bins = _p(texbins[0]), _p(texbins[1]), texbins[2]
         # parameters and gradients (views of the flat buffers)
         g = {n: m.get_parameter(n).grad for n, _, _ in self.params.names}
         for f, n in (('sq_eps', 'sq_eps'), ('S', 'S'), ('R6', 'R_6d'), ('T', 'T'), ('alpha_logit', 'alpha_logit'), ('R6_ground', 'R_6d_ground'),
@@ -396,7 +380,7 @@ class CStep:
                 _lib.call('dbw_train_step_run', handle, ctypes.byref(a), cur.cuda_stream, side)
                 with torch.enable_grad():
                     leaf = rec.requires_grad_(True)
-                    perceptual = m._perceptual_term(inp['imgs'], leaf, m.is_live('coarse_learning'), inp.get('view_ids'))
+                    perceptual = m._perceptual_term(inp['imgs'], leaf, self._phase.coarse_epoch, inp.get('view_ids'))
                     g_rec, = torch.autograd.grad(perceptual, leaf)
                 perceptual, g_rec = perceptual.detach(), g_rec.contiguous()
                 a.phase, a.rec_out, a.grad_rec = 2, 0, g_rec.data_ptr()

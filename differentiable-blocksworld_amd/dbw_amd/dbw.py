@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import mesh as M
-from . import ops
+from . import ops, phase
 from .renderer import DIRECTION_LIGHT, Renderer
 from .structures import PackedScene
 
@@ -291,24 +291,27 @@ class DifferentiableBlocksWorld(nn.Module):
     def _world_consts(self):
         return float(self.S_world), self.R_world[0].contiguous(), self.T_world[0].contiguous()
 
+    def sky_world_verts(self):
+        """The sky dome's vertices in world coordinates.  Constant geometry (no parameter involved): cached until the world transform
+        changes (load_state_dict copies into the R_world / T_world buffers in place -> their version counters move; S_world is a plain
+        attribute) or the model moves.  The training steps copy it in front of the ground's vertices (a new tensor: a new sky)."""
+        key = (float(self.S_world), self.R_world._version, self.T_world._version, self.R_world.data_ptr(), self._bkg_verts.device)
+        if getattr(self, '_bkg_world_key', None) != key:
+            S_w, R_w, T_w = self._world_consts()
+            self._bkg_world = ((self._bkg_verts * S_w) @ R_w + T_w).detach()
+            self._bkg_world_key = key
+        return self._bkg_world
+
     def build_env_scene(self):
         """join(build_bkg(world_coord=True), build_ground(world_coord=True))  (dbw.py:214,267-295) as a PackedScene."""
         S_w, R_w, T_w = self._world_consts()
-        # constant geometry (no parameter involved): cached until the world transform changes (load_state_dict copies into the
-        # R_world / T_world buffers in place -> their version counters move; S_world is a plain attribute) or the model moves
-        key = (float(S_w), self.R_world._version, self.T_world._version, self.R_world.data_ptr(), self._bkg_verts.device)
-        if getattr(self, '_bkg_world_key', None) != key:
-            self._bkg_world = ((self._bkg_verts * S_w) @ R_w + T_w).detach()
-            self._bkg_world_key = key
-        bkg_v = self._bkg_world
+        ph = phase.phase_of(self, self.training)
         ground_v = ops.posed_mesh(self.R_6d_ground, self.T_ground, self._ground_base, S_w, R_w, T_w)
-        decim = self.decim_factor if (self.training and self.is_live('decimate_txt')) else 1
-        bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, decim)
-        g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, decim)
-        verts = torch.cat([bkg_v, ground_v], 0)
+        bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, ph.decim_env)
+        g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, ph.decim_env)
+        verts = torch.cat([self.sky_world_verts(), ground_v], 0)
         maps = torch.cat([bkg_maps.reshape(-1), g_maps.reshape(-1)])
-        desc = self._env_map_desc if decim == 1 else self._env_map_desc_dec
-        scene = PackedScene(verts, self._env_faces, self._env_face_uvs, self._env_face_map, desc, maps)
+        scene = PackedScene(verts, self._env_faces, self._env_face_uvs, self._env_face_map, phase.env_map_desc(self, ph), maps)
         scene.const_faces = self._n_bkg_faces       # the sky dome is a buffer (dbw.py:74-76): no gradient flows to its vertices
         return scene
 
@@ -325,17 +328,14 @@ class DifferentiableBlocksWorld(nn.Module):
     def build_blocks_scene(self, filter_transparent=False):
         """build_blocks(filter_transparent, as_scene=True) (dbw.py:297-346) as a PackedScene, or None if no block is left.
         Sets self._alpha (live blocks), self._alpha_full, self._blocks_maps like the reference."""
-        coarse = self.training and self.is_live('coarse_learning')
-        noise, noise_scale = None, 0.0
-        if self.opacity_noise and coarse:
+        ph = phase.phase_of(self, self.training, filter_transparent)
+        noise = None
+        if ph.noise_scale:
             noise = self._noise_override if self._noise_override is not None else self._shared_randn_like(self.alpha_logit)
-            noise_scale = float(self.opacity_noise)
-        masked = filter_transparent or self.kill_blocks
-        thresh = (0.5 if filter_transparent else 0.01) if masked else -1.0
         # sigmoid(alpha_logit + noise), the transparency mask on the noise-free opacity and alpha * mask: one launch
-        self._alpha, self._alpha_full, mask_i32 = ops.block_alpha(self.alpha_logit, noise, noise_scale, thresh)
+        self._alpha, self._alpha_full, mask_i32 = ops.block_alpha(self.alpha_logit, noise, ph.noise_scale, ph.mask_threshold)
         keep, nb = None, self.n_blocks
-        if masked:
+        if ph.masked:
             if self.sync_free:
                 keep = mask_i32
             else:
@@ -343,8 +343,7 @@ class DifferentiableBlocksWorld(nn.Module):
                 if nb < self.n_blocks:
                     keep = mask_i32
                     self._alpha = self._alpha[mask_i32.bool()]
-        decim = self.decim_factor if (coarse and self.is_live('decimate_txt')) else 1
-        maps_all, self._blocks_maps = ops.texture_prep(self.textures, decim)
+        maps_all, self._blocks_maps = ops.texture_prep(self.textures, ph.decim_blocks)
         self._keep_mask = keep
         if nb == 0:
             return None
@@ -354,14 +353,10 @@ class DifferentiableBlocksWorld(nn.Module):
         maps = maps_all if (keep is None or self.sync_free) else maps_all[keep.bool()]
         F_ = nb * self.BNF
         # (a view of the full table: its row 0 announces all n_blocks rows, which stay readable behind the nb rows in use)
-        desc = (self._block_map_desc_all if decim == 1 else self._block_map_desc_dec)[:nb]
-        self._blocks_decimated = decim > 1
-        nbins = nb * self._bins_per_block
-        # full-resolution maps: texel gradients go through the texture-space bins (coarse phase 8.6 -> 4.2 ms/step, fine phase
-        # 3.1 -> 2.8 ms/step on the bench config); decimated maps use the in-tile LDS hash
-        texbins = None if decim > 1 else (self._block_bin_base[:nb], self._block_bin_info[:nbins], nbins)
+        desc = phase.block_map_desc(self, ph)[:nb]
+        self._blocks_decimated = ph.blocks_decimated
         return PackedScene(verts.reshape(-1, 3), self._block_faces_all[:F_], self._block_face_uvs_all[:F_],
-                           self._block_face_map_all[:F_], desc, maps.reshape(-1), texbins)
+                           self._block_face_map_all[:F_], desc, maps.reshape(-1), phase.block_texbins(self, ph, nb))
 
     def blocks_mesh(self, filter_transparent=True):
         """-> (verts (V,3) fp32, faces (F,3) int64): the posed blocks in world coordinates, live ones only, joined into one mesh in block
@@ -390,13 +385,13 @@ class DifferentiableBlocksWorld(nn.Module):
         if reduce_ground:
             base = (base * torch.tensor([3 / self.z_far, 1, 3 / self.z_far], device=base.device)).contiguous()
         ground_v = ops.posed_mesh(self.R_6d_ground, self.T_ground, base, S_w, R_w, T_w)
-        decim = self.decim_factor if (self.training and self.is_live('decimate_txt')) else 1
-        g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, decim)
-        desc = self._env_map_desc if decim == 1 else self._env_map_desc_dec
+        ph = phase.phase_of(self, self.training)
+        g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, ph.decim_env)
+        desc = phase.env_map_desc(self, ph)
         nf, nv = self._n_bkg_faces, self._bkg_verts.shape[0]
         if w_bkg:
-            bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, decim)
-            scene = PackedScene(torch.cat([((self._bkg_verts * S_w) @ R_w + T_w).detach(), ground_v], 0), self._env_faces, self._env_face_uvs,
+            bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, ph.decim_env)
+            scene = PackedScene(torch.cat([self.sky_world_verts(), ground_v], 0), self._env_faces, self._env_face_uvs,
                                 self._env_face_map, desc, torch.cat([bkg_maps.reshape(-1), g_maps.reshape(-1)]))
             scene.const_faces = nf
             return scene
@@ -609,16 +604,12 @@ class DifferentiableBlocksWorld(nn.Module):
         then fg pass + decoupled composite + MSE in one kernel -- no fg image, no composite kernel, no image-sized gradient round
         trips.  Returns None when the configuration needs the general path (non-decoupled, perceptual term, no block left, layered
         fallbacks switched off)."""
-        w = self.loss_weights
-        if (not self.decouple_rendering or 'rgb' not in w or 'perceptual' in w or not self.default_criteria
-                or not (ops.FUSED_FORWARD and ops.FUSED_BACKWARD and ops.TILED_FRAGMENTS and ops.UV_FRAGMENTS)):
+        if 'perceptual' in self.loss_weights:
             return None
         self._ensure_cameras(inp)
-        fine = not self.is_live('coarse_learning')
+        fine = phase.phase_of(self, self.training).fine_renderer
         renderer = self.renderer_fine if fine else self.renderer
-        if not renderer.detach_bary or renderer.faces_per_pixel < 2 or renderer.cam_name != 'perspective' or renderer.cameras.K is None:
-            return None
-        if not renderer.clip_inside:          # the sigmoid opacity (renderer.py:257-258): generic shading kernels only, the loss epilogue is exp-only
+        if phase.fast_path_refusal(self, renderer) is not None:
             return None
         blocks = self.build_blocks_scene(filter_transparent=fine)
         if blocks is None or blocks.faces.shape[0] >= (1 << 20) or blocks.map_desc.shape[0] >= (1 << 11):
@@ -631,7 +622,7 @@ class DifferentiableBlocksWorld(nn.Module):
         cfg_f = renderer._cfg(blocks.faces.shape[0], lds_aggregate=self._blocks_decimated, texbins=blocks.texbins)
         imgs = inp['imgs']
         count = imgs.numel() if getattr(self, '_global_count', None) is None else self._global_count
-        rgb = ops.render_decoupled_mse(env, blocks, alpha, imgs, float(w['rgb']) / float(count), R, T, Kmat, cfg_e, cfg_f,
+        rgb = ops.render_decoupled_mse(env, blocks, alpha, imgs, float(self.loss_weights['rgb']) / float(count), R, T, Kmat, cfg_e, cfg_f,
                                        self.renderer_env._bg, renderer._bg)
         return self.compute_losses(imgs, None, layers=None, rgb_value=rgb)
 
@@ -789,27 +780,21 @@ class DifferentiableBlocksWorld(nn.Module):
             value = self.perceptual_fn(imgs, rec, view_ids=view_ids)
         else:
             value = self.perceptual_fn(imgs, rec)
-        return self.loss_weights['perceptual'] * (1 if coarse else 0.1) * share * value
+        return self.loss_weights['perceptual'] * phase.late_factor(coarse) * share * value
 
     def compute_losses(self, imgs, rec, layers=None, rgb_value=None):
         w = self.loss_weights
         dev = imgs.device
-        coarse = self.is_live('coarse_learning')
-        ws = self.world_size
-        # view-independent regularisers: every rank computes them identically; scaled by 1/world_size so that the
-        # sum all-reduce of gradients counts them once
-        rs = 1.0 / ws
+        # (the epoch's loss factors in eval mode too; view-independent regularisers: every rank computes them identically, scaled by
+        # 1 / world_size so that the sum all-reduce of gradients counts them once)
+        ph = phase.phase_of(self, self.training)
+        coarse, rs, ws = ph.coarse_epoch, ph.rs, self.world_size
         if (layers is not None or rgb_value is not None) and 'rgb' in w and self.default_criteria:
-            # training path: composite + MSE and the regularisers as ONE autograd node (ops.fused_losses); factors of
-            # dbw.py:373-405: parsimony and overlap only act in the coarse phase, tv is scaled by 0.1 afterwards (and the
-            # ground map once more)
+            # training path: composite + MSE and the regularisers as ONE autograd node (ops.fused_losses), the phase's weights
+            # folded into the kernels' scales
             count = imgs.numel() if getattr(self, '_global_count', None) is None else self._global_count
-            tv_f = 1 if coarse else 0.1
-            cfg = {'rgb': float(w['rgb']), 'count': float(count),
-                   'parsimony': float(w['parsimony']) * rs if ('parsimony' in w and coarse) else None,
-                   'tv': float(w['tv']) * tv_f * rs if 'tv' in w else None, 'tv_ground_factor': tv_f,
-                   'overlap': float(w['overlap']) * rs if ('overlap' in w and coarse) else None,
-                   'overlap_consts': (float(self.ratio_block_scene), float(self.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS)}
+            cfg = {'rgb': ph.w_rgb, 'count': float(count), 'parsimony': ph.w_parsimony, 'tv': ph.w_tv, 'tv_ground_factor': ph.tv_factor,
+                   'overlap': ph.w_overlap, 'overlap_consts': (float(self.ratio_block_scene), float(self.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS)}
             u = None
             if cfg['overlap']:
                 u = self._overlap_u_override
@@ -845,7 +830,7 @@ class DifferentiableBlocksWorld(nn.Module):
             alpha = self._alpha_full if coarse else (self._alpha_full > 0.5).float()
             losses['parsimony'] = w['parsimony'] * factor * rs * safe_pow(alpha, 0.5).mean()
         if 'tv' in losses:
-            factor = 1 if coarse else 0.1
+            factor = ph.tv_factor
             if self.tv_type == 'l2sq':
                 tv = ops.tv_l2sq(self._bkg_maps) + ops.tv_l2sq(self._blocks_maps, wrap_x=True) + ops.tv_l2sq(self._ground_maps) * factor
             else:       # dbw.py:378-387 with tv_norm_funcs['l1' | 'l2'], in torch on the prepared maps

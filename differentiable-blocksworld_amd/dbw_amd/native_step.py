@@ -16,18 +16,18 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, phase
+from .c_step import side_stream
 from .dbw import OVERLAP_N_BLOCKS, OVERLAP_N_POINTS, OVERLAP_TEMPERATURE
 
 _p = ops._ptr
-_SIDE_STREAMS = {}
 
 
 class NativeStep:
     def __init__(self, model, params):
         self.m, self.params = model, params
         self.grad = {n: model.get_parameter(n).grad for n, _, _ in params.names}       # views of the flat gradient buffer
-        self._env_verts = None
+        self._env_verts, self._env_sky = None, None
         self._target, self._target_key = None, None
         self._side, self.overlap_regularisers, self.side_priority = None, True, True
         self.regularisers_behind_fg = True
@@ -50,14 +50,8 @@ class NativeStep:
         return self._target
 
     def supported(self):
-        m, w = self.m, self.m.loss_weights
-        r = self.m.renderer
-        # (clip_inside = False -- the sigmoid opacity -- is implemented by the generic shading / backward kernels of the autograd path only: the
-        # specialised uv kernels and the loss epilogue are exp-only, sigma >= 0)
-        return (m.decouple_rendering and m.sync_free and 'rgb' in w and 'perceptual' not in w and r.detach_bary and r.faces_per_pixel > 1
-                and r.clip_inside and getattr(m.renderer_fine, 'clip_inside', True) and getattr(m, 'default_criteria', True)
-                and r.cam_name == 'perspective' and m.blocks_n_faces < (1 << 20) and m.n_blocks + 2 < (1 << 11)
-                and ops.FUSED_FORWARD and ops.FUSED_BACKWARD and ops.TILED_FRAGMENTS and ops.UV_FRAGMENTS)
+        m = self.m
+        return bool(m.sync_free and 'perceptual' not in m.loss_weights and phase.fast_path_refusal(m) is None)
 
     def __call__(self, inp, global_count=None, zero_grad=None):
         """Forward + backward of one iteration on this rank's views.  The caller has opened the zero arena (ops.ARENA.begin_step) and
@@ -75,11 +69,8 @@ class NativeStep:
         dev = imgs.device
         m._ensure_cameras(inp)
         B = imgs.shape[0]
-        coarse = m.is_live('coarse_learning')              # (training mode)
-        fine = not coarse
-        decim = int(m.decim_factor) if m.is_live('decimate_txt') else 1
-        decim_blocks = decim if coarse else 1              # dbw.py:329-334: blocks are only decimated in the coarse phase
-        rs = 1.0 / m.world_size
+        ph = phase.phase_of(m)                                 # (training mode)
+        fine, decim, decim_blocks = ph.fine_renderer, ph.decim_env, ph.decim_blocks
         S_w, R_w, T_w = m._world_consts()
         nb, nv, TS, u_ = m.n_blocks, m._block_nv, m.txt_size, m.txt_bkg_upscale
         renderer = m.renderer_fine if fine else m.renderer
@@ -91,14 +82,8 @@ class NativeStep:
         if self.overlap_regularisers:
             if self._side is None:
                 # high priority: its small kernels overtake the big render kernels of the main stream instead of queueing behind them, and
-                # the fg backward finishes before the (lighter) env backward it shares the GPU with, so that the LONGER tail hides.
-                # ONE side stream per process, device and priority: torch hands streams out of a pool round-robin and HIP multiplexes
-                # them onto a few hardware queues -- the fourth / fifth NativeStep of a process used to get a stream that shares its
-                # queue with the main stream, and its steps took 2.1 ms instead of 1.2 (tools/diag/degrade.py)
-                key = (dev.index, bool(self.side_priority))
-                if key not in _SIDE_STREAMS:
-                    _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev, priority=-1 if self.side_priority else 0)
-                self._side = _SIDE_STREAMS[key]
+                # the fg backward finishes before the (lighter) env backward it shares the GPU with, so that the LONGER tail hides
+                self._side = side_stream(dev, self.side_priority)
             side = self._side
             side.wait_stream(cur)                          # the previous step's Adam, the zero arena
         st_main, st_side = cur.cuda_stream, side.cuda_stream
@@ -107,11 +92,11 @@ class NativeStep:
         st = st_main
         nbv = m._bkg_verts.shape[0]
         ngv = m._ground_base.shape[0]
-        key = (float(S_w), m.R_world._version, m.T_world._version, m.R_world.data_ptr())
-        if self._env_verts is None or self._env_key != key:          # the sky dome is constant: written once
+        sky = m.sky_world_verts()
+        if self._env_sky is not sky:                                  # the sky dome is constant: written once per cached tensor of the model's
             self._env_verts = torch.empty(nbv + ngv, 3, device=dev)
-            self._env_verts[:nbv] = ((m._bkg_verts * S_w) @ R_w + T_w)
-            self._env_key = key
+            self._env_verts[:nbv] = sky
+            self._env_sky = sky
         env_verts = self._env_verts
         _lib.call('dbw_posed_mesh_fwd', _p(m._ground_base), ngv, _p(m.R_6d_ground), _p(m.T_ground), float(S_w), _p(R_w), _p(T_w),
                   env_verts.data_ptr() + nbv * 12, st)
@@ -120,7 +105,7 @@ class NativeStep:
         env_maps = torch.empty(2 * ce, device=dev)                    # [sky | ground]
         blk_maps = torch.empty(nb * (TS // decim_blocks) ** 2 * 3, device=dev)
         cfg_e = m.renderer_env._cfg(Fe, lds_aggregate=True, const_faces=m._n_bkg_faces)   # the sky dome's vertices are constants
-        desc_e = m._env_map_desc if decim == 1 else m._env_map_desc_dec
+        desc_e = phase.env_map_desc(m, ph)
         cl_e = ops.project_clip(env_verts, m._env_faces, R, T, Kmat, cfg_e.eps, cfg_e.z_clip, cfg_e.persp)
         lay_e = ops.hard_layout(cfg_e, None, desc_e)                  # 3: hard uv-fragments
         # image-shaped buffers of the step (env image, the two gradient images) live in the 8x8-tile planar layout of the fragments
@@ -133,12 +118,9 @@ class NativeStep:
         # the env pass on the main stream waits for them; then zero the gradients and the opacities (dbw.py:297-311) ----
         torch.cuda.set_stream(side)
         st = st_side
-        tv_f = 1.0 if coarse else 0.1
-        tv = float(w['tv']) * tv_f * rs if 'tv' in w else 0.0
         sets = []                                                      # the three texture tensors: one launch per pass over them
-        for tex, d, out, wrap, sc, name in ((m.texture_bkg, decim, env_maps[:ce], 0, tv, 'texture_bkg'),
-                                            (m.textures, decim_blocks, blk_maps, 1, tv, 'textures'),
-                                            (m.texture_ground, decim, env_maps[ce:], 0, tv * tv_f, 'texture_ground')):
+        for (name, d, wrap, sc), out in zip(ph.texture_rows(), (env_maps[:ce], blk_maps, env_maps[ce:])):
+            tex = getattr(m, name)
             n, h, ww, _ = tex.shape
             sig = torch.empty_like(tex) if d > 1 else out.view(tex.shape)
             sets.append(dict(texture=_p(tex), n=n, h=h, w=ww, decim=d, maps=_p(out), sig=_p(sig) if d > 1 else 0, wrap_x=wrap, tv_scale=sc,
@@ -154,16 +136,13 @@ class NativeStep:
         if zero_grad is not None:
             zero_grad()
         vals = torch.zeros(8, device=dev)                  # 0 rgb (filled on demand), 1 parsimony, 2 tv, 3 overlap; outlives the step
-        noise, noise_scale = None, 0.0
-        if m.opacity_noise and coarse:
+        noise = None
+        if ph.noise_scale:
             noise = m._noise_override if m._noise_override is not None else m._shared_randn_like(m.alpha_logit)
-            noise_scale = float(m.opacity_noise)
-        masked = fine or m.kill_blocks
-        thresh = (0.5 if fine else 0.01) if masked else -1.0
         alpha, alpha_full = torch.empty(nb, device=dev), torch.empty(nb, device=dev)
         keep = torch.empty(nb, dtype=torch.int32, device=dev)
-        _lib.call('dbw_block_alpha_fwd', _p(m.alpha_logit), _p(noise), noise_scale, thresh, nb, _p(alpha), _p(alpha_full), _p(keep), st)
-        keep_p = _p(keep) if masked else 0
+        _lib.call('dbw_block_alpha_fwd', _p(m.alpha_logit), _p(noise), ph.noise_scale, ph.mask_threshold, nb, _p(alpha), _p(alpha_full), _p(keep), st)
+        keep_p = _p(keep) if ph.masked else 0
 
         # ---- main: the env pass ----
         torch.cuda.set_stream(cur)
@@ -179,9 +158,8 @@ class NativeStep:
         # (dbw.py:373-405) -- they only need the parameters, opacities and maps prepared above ----
         torch.cuda.set_stream(side)
         st = st_side
-        desc_f = m._block_map_desc_all if decim_blocks == 1 else m._block_map_desc_dec
-        texbins = None if decim_blocks > 1 else (m._block_bin_base, m._block_bin_info, nb * m._bins_per_block)
-        cfg_f = renderer._cfg(Ff, lds_aggregate=decim_blocks > 1, texbins=texbins)
+        desc_f = phase.block_map_desc(m, ph)
+        cfg_f = renderer._cfg(Ff, lds_aggregate=ph.blocks_decimated, texbins=phase.block_texbins(m, ph, nb))
         blk_verts = torch.empty(nb * nv, 3, device=dev)
         _lib.call('dbw_sq_blocks_fwd', _p(m.sq_eps), _p(m.S), _p(m.R_6d), _p(m.T), _p(m._trig), keep_p, 0, nb, nv, float(m.ratio_block_scene),
                   float(m.scale_min), float(S_w), _p(R_w), _p(T_w), _p(blk_verts), st)
@@ -194,7 +172,7 @@ class NativeStep:
             fg_ready = torch.cuda.Event()                              # behind it (they run next to the fg forward)
             fg_ready.record(side)
         count = float(imgs.numel() if global_count is None else global_count)
-        scale = float(w['rgb']) / count
+        scale = ph.w_rgb / count
 
         def fg_pass():
             # ---- main: the fg pass, ending in the composite + MSE ----
@@ -216,18 +194,18 @@ class NativeStep:
             if cfg_f.texbins is not None:          # (full-resolution maps: the record sub-ranges of this step's backward, from the last step's demand)
                 cfg_f.bin_demand.prepare(cfg_f.texbins[2], ops.texbin_capacity(B, cfg_f.H, cfg_f.W, cfg_f.K, cfg_f.texbins[2]), dev)
             g_alpha_full = ops.ARENA.zeros(nb, torch.float32, dev)                                  # d / d alpha_full (parsimony, overlap)
-            if 'parsimony' in w and coarse:
-                _lib.call('dbw_sqrt_mean', _p(alpha_full), nb, 1e-6, float(w['parsimony']) * rs, vals.data_ptr() + 4, _p(g_alpha_full), st)
-            if 'tv' in w:
+            if ph.w_parsimony is not None:
+                _lib.call('dbw_sqrt_mean', _p(alpha_full), nb, 1e-6, ph.w_parsimony, vals.data_ptr() + 4, _p(g_alpha_full), st)
+            if ph.w_tv is not None:
                 for t in sets:
                     t['_g_sig'] = torch.empty_like(t['_sig'])
                     t['sig'], t['grad_sig_out'], t['grad_sig'] = _p(t['_sig']), _p(t['_g_sig']), _p(t['_g_sig'])
                 launch('dbw_tv_l2sq_sets', (0, 1, 2), vals.data_ptr() + 8, st)
-            if 'overlap' in w and coarse:
+            if ph.w_overlap is not None:
                 u = m._overlap_u_override if m._overlap_u_override is not None else torch.rand(nb, OVERLAP_N_POINTS, 3, device=dev)
                 ws = ops.ARENA.zeros(nb * 18, torch.float32, dev)
                 _lib.call('dbw_overlap_loss', _p(u), u.shape[1], _p(m.sq_eps), _p(m.S), _p(m.R_6d), _p(m.T), _p(alpha_full), nb,
-                          float(m.ratio_block_scene), float(m.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS, float(w['overlap']) * rs,
+                          float(m.ratio_block_scene), float(m.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS, ph.w_overlap,
                           vals.data_ptr() + 12, _p(g['sq_eps']), _p(g['S']), _p(g['R_6d']), _p(g['T']), _p(g_alpha_full), _p(ws), st)
 
             torch.cuda.set_stream(cur)
@@ -283,7 +261,7 @@ class NativeStep:
             kernel_done = torch.cuda.Event()
             seq = self.sequential_backward
             if seq is None:
-                seq = m.world_size > 1 or decim_blocks == 1
+                seq = m.world_size > 1 or not ph.blocks_decimated
             both = False
             if cfg_f.texbins is not None:
                 # full-resolution maps: the texel gradients of the blocks leave the fg kernel as binned records and only reach

@@ -586,3 +586,69 @@ def test_arena_cleaned_by_the_caller_counts_for_the_plan_it_cleaned_only():
     for k in want0:
         assert abs(got0[k] - want0[k]) <= 2e-6 * max(abs(want0[k]), 1e-3), (k, got0[k], want0[k])
     assert float((step.params.grad - g0).abs().max()) <= 1e-5 * float(g0.abs().max())
+
+
+def _small(epoch):
+    """2 views of 32 x 48, 3 blocks, 16^2 textures, 4 faces per pixel (the smoke run's shapes: every pass still has real fragments)."""
+    return _model(epoch, nb=3, ts=16, fpp=4, H=32, W=48), _inputs(2, 32, 48)
+
+
+_f32 = lambda x: ctypes.c_float(x).value
+# the reference's rules (src/model/dbw.py:297-334, 361-408) for _cfg() on one rank, as literals; the fine phase's TV weights are the
+# doubles 0.1 * 0.1 * 1.0 and that * 0.1, rounded to float once, at the descriptor
+_PLAN = {0: dict(coarse=1, decim_env=8, decim_blocks=8, opacity_noise=1.0, mask_threshold=0.01, w_rgb=1.0, w_parsimony=0.01, w_tv_bkg=0.1,
+                 w_tv_blocks=0.1, w_tv_ground=0.1, w_overlap=1.0, tv_value_scale=1.0, bins=False),
+         800: dict(coarse=1, decim_env=1, decim_blocks=1, opacity_noise=1.0, mask_threshold=0.01, w_rgb=1.0, w_parsimony=0.01, w_tv_bkg=0.1,
+                   w_tv_blocks=0.1, w_tv_ground=0.1, w_overlap=1.0, tv_value_scale=1.0, bins=True),
+         1600: dict(coarse=0, decim_env=1, decim_blocks=1, opacity_noise=0.0, mask_threshold=0.5, w_rgb=1.0, w_parsimony=0.0,
+                    w_tv_bkg=0.010000000000000002, w_tv_blocks=0.010000000000000002, w_tv_ground=0.0010000000000000002, w_overlap=0.0,
+                    tv_value_scale=1.0, bins=True)}
+
+
+@pytest.mark.parametrize('epoch', [0, 800, 1600])
+def test_plan_descriptor_carries_the_constants_of_its_phase(epoch):
+    """The scalar fields of the dbw_step_desc a plan was created from (dbw_amd/phase.py -> CStep._plan_for), bit for bit: loss values and
+    gradients are unordered float sums, the descriptor is what can be compared exactly."""
+    model, inp = _small(epoch)
+    step = ShardedTrainStep(model, lr=5e-3, lr_texture=5e-2, seed=99)
+    step(inp)
+    torch.cuda.synchronize()
+    assert step.cstep._cur is not None, 'the C step did not run'
+    d = step.cstep._cur[2][-1]
+    want = dict(_PLAN[epoch])
+    n_bins = 3 * model._bins_per_block if want.pop('bins') else 0
+    assert d.n_bins == n_bins and (epoch == 0 or n_bins > 0)
+    for name, value in want.items():
+        got = getattr(d, name)
+        assert got == (value if isinstance(value, int) else _f32(value)), (name, got, value)
+
+
+def test_native_step_and_c_step_of_one_process_share_one_side_stream():
+    from dbw_amd import c_step, native_step
+    steps = []
+    for c in (False, True):
+        model, inp = _small(0)
+        steps.append(ShardedTrainStep(model, lr=5e-3, lr_texture=5e-2, seed=99, use_c_step=c))
+        steps[-1](inp)
+    torch.cuda.synchronize()
+    native, cs = steps[0].native, steps[1].cstep
+    assert steps[0].cstep is None and cs._cur is not None
+    side = c_step.side_stream(torch.device(DEV), True)
+    assert native._side is side and c_step.side_stream(torch.device(DEV), cs.side_priority) is side      # (parallel.py's look-up for the C step)
+    assert [k for k in c_step._SIDE_STREAMS if k[0] == 0 and k[1]] == [(0, True)] and not hasattr(native_step, '_SIDE_STREAMS')
+
+
+def test_native_step_and_c_step_copy_the_sky_dome_from_the_model_s_one_cache():
+    model, inp = _small(0)
+    native = ShardedTrainStep(model, lr=0.0, lr_texture=0.0, seed=99, use_c_step=False)
+    native(inp)
+    sky = model._bkg_world
+    cs = ShardedTrainStep(model, lr=0.0, lr_texture=0.0, seed=99)
+    cs(inp)
+    torch.cuda.synchronize()
+    assert cs.cstep._cur is not None and model._bkg_world is sky and model.sky_world_verts() is sky
+    n = cs.cstep._cur[2][-1].n_sky_verts
+    assert n == sky.shape[0] == model._bkg_verts.shape[0]
+    env_c = next(t for t in cs.cstep._cur[2][:-1] if t.shape == native.native._env_verts.shape)      # (the plan's keep-alive list)
+    assert torch.equal(native.native._env_verts[:n], sky) and torch.equal(env_c[:n], sky)
+    assert env_c.data_ptr() == cs.cstep._cur[2][-1].env_verts
