@@ -2,6 +2,9 @@
 (include/dbw_hip.h); the Python host binds it with ctypes.  Flags matter for parity:
   -ffp-contract=off        one rounding per fp32 op, bit-exact with the CPU oracle's rasteriser arithmetic
   -munsafe-fp-atomics      hardware global/LDS float atomics instead of CAS loops
+  -fno-slp-vectorize       (NO_SLP sources only) a v_pk_{add,mul,fma}_f32 costs a SIMD 1.5-1.7 plain fp32 instructions at 4-5 waves,
+                           and a stream that mixes the two runs at the packed rate (tools/ubench/pk_rate.hip, profiles/r09_pk_rate.txt):
+                           the forward render kernels are bound by VALU issue and run faster on single-element instructions.  Same bits.
 IEEE fp32 divide/sqrt is hipcc's default (-fhip-fp32-correctly-rounded-divide-sqrt)."""
 import os
 import subprocess
@@ -15,6 +18,11 @@ SOURCES = ['util.hip', 'raster.hip', 'project_clip.hip', 'shade_blend.hip', 'ren
 OUT = os.path.join(HERE, 'dbw_amd', 'libdbw_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-munsafe-fp-atomics',
          '-fno-gpu-flush-denormals-to-zero', '-Wall', '-Wno-unused-function']
+NO_SLP = ('render_fused.hip',)         # the fused forward render kernels (profiles/r09_experiments.md: what each source gains and costs)
+
+
+def flags_for(source):
+    return FLAGS + (['-fno-slp-vectorize'] if source in NO_SLP else [])
 
 
 def needs_build():
@@ -36,7 +44,7 @@ def build(force=False, verbose=False, extra_flags=()):
     for s in SOURCES:
         o = os.path.join(HERE, 'build', s.replace('.hip', '.o'))
         objs.append(o)
-        cmd = [hipcc] + FLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, s), '-o', o]
+        cmd = [hipcc] + flags_for(s) + list(extra_flags) + ['-c', os.path.join(CSRC, s), '-o', o]
         if verbose:
             print(' '.join(cmd))
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

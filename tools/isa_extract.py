@@ -4,6 +4,7 @@ usage: tools/isa_extract.py render_fused.hip 'render_fwd_kernelILi10ELi8ELi8ELi2
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-munsafe-fp-atomics', '-fno-gpu-flush-denormals-to-zero']
+NO_SLP = ('render_fused.hip',)        # as build.py
 
 
 def kinds(lines):
@@ -27,7 +28,7 @@ def main():
     defs = [a for a in sys.argv[3:] if a.startswith('-D')]
     dump = sys.argv[sys.argv.index('--dump') + 1] if '--dump' in sys.argv else None
     out = '/tmp/_isa_%s.s' % os.path.basename(src)
-    subprocess.check_call(['/opt/rocm/bin/hipcc'] + FLAGS + defs + ['-S', '--cuda-device-only', '-o', out, os.path.join(ROOT, 'differentiable-blocksworld_amd', 'csrc', src)],
+    subprocess.check_call(['/opt/rocm/bin/hipcc'] + FLAGS + (['-fno-slp-vectorize'] if os.path.basename(src) in NO_SLP else []) + defs + ['-S', '--cuda-device-only', '-o', out, os.path.join(ROOT, 'differentiable-blocksworld_amd', 'csrc', src)],
                           stderr=subprocess.DEVNULL)
     L = open(out).read().split('\n')
     start = next(i for i, l in enumerate(L) if l.endswith(':') is False and re.match(r'^_Z\S*' + re.escape(sub) + r'\S*:', l))

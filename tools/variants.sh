@@ -10,7 +10,8 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-
 while [ $# -ge 2 ]; do
   name=$1; defs=$2; shift 2
   ( objs=""; for f in util raster project_clip shade_blend render_fused texture model_ops train_step lpips_head; do
-      rm -f /tmp/var_${name}_$f.o; /opt/rocm/bin/hipcc $FLAGS $defs -c $CS/$f.hip -o /tmp/var_${name}_$f.o & objs="$objs /tmp/var_${name}_$f.o"; done; wait
+      case $f in render_fused) X=-fno-slp-vectorize;; *) X=;; esac      # (build.py's NO_SLP)
+      rm -f /tmp/var_${name}_$f.o; /opt/rocm/bin/hipcc $FLAGS $X $defs -c $CS/$f.hip -o /tmp/var_${name}_$f.o & objs="$objs /tmp/var_${name}_$f.o"; done; wait
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs -o tools/variants/$name.so; echo built $name ) &
 done
 wait
