@@ -202,9 +202,12 @@ MONITOR_SIGNATURES = {
     'dbw_image_scores': [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     'dbw_meter_add': [c_p, c_p, c_i, c_d, c_i64, c_p],
     'dbw_meter_reset': [c_p, c_i, c_p],
+    # SSIM as a loss term (csrc/ssim_term.hip), added under revision 1 of the header
+    'dbw_monitor_ssim_term': [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
 }
 MONITOR_OTHER_SIGNATURES = {
     'dbw_image_scores_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
+    'dbw_monitor_ssim_term_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
 }
 METER_MAX_VALUES = 16                                         # DBW_METER_MAX_VALUES of include/dbw_monitor.h
 MONITOR_ABI_VERSION = header_define('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION')

@@ -10,7 +10,8 @@ src/trainer.py:137-147 drives, with every per-iteration computation executed by 
 Only O(K)-scalar glue (opacity sigmoid/noise, parsimony over K numbers, loss weighting) stays in torch.
 
 The perceptual term needs the third-party `lpips` package + VGG weights (absent here): it is a pluggable callable
-(`perceptual_fn`), excluded from the HIP path as SURVEY.md 8(a) A10 prescribes."""
+(`perceptual_fn`), excluded from the HIP path as SURVEY.md 8(a) A10 prescribes.  `perceptual_name: ssim` installs the reference's other
+registered criterion instead, SSIMLoss, as a built-in term (metrics.SSIMTerm, csrc/ssim_term.hip)."""
 import warnings
 from copy import deepcopy
 
@@ -54,9 +55,9 @@ class DifferentiableBlocksWorld(nn.Module):
         self._init_blocks(**kwargs.get('mesh', {}))
         self._init_renderer(self.img_size, **kwargs.get('renderer', {}))
         self._init_rend_optim(**kwargs.get('rend_optim', {}))
+        self.perceptual_fn = None
         self._init_loss(**kwargs.get('loss', {}))
         self.cur_epoch = 0
-        self.perceptual_fn = None
         self.world_size, self.rank = 1, 0     # view-sharded data parallel (parallel.py)
         self._noise_override = None
         self._overlap_u_override = None
@@ -201,7 +202,8 @@ class DifferentiableBlocksWorld(nn.Module):
                    'parsimony': kwargs.pop('parsimony_weight', 0), 'scale': kwargs.pop('scale_weight', 0),
                    'tv': kwargs.pop('tv_weight', 0), 'overlap': kwargs.pop('overlap_weight', 0)}
         name = kwargs.pop('name', 'mse')
-        kwargs.pop('perceptual_name', 'lpips')
+        # loss.py:22, dbw.py:155,163: 'lpips' (a third-party network: set_perceptual) or 'ssim', the built-in term (metrics.SSIMTerm)
+        self.perceptual_name = kwargs.pop('perceptual_name', 'lpips')
         tv_type = kwargs.pop('tv_type', 'l2sq')
         assert len(kwargs) == 0, kwargs
         # loss.py:11-24,43-47: the image criteria of the registry that are criteria on an RGB image pair (mse / l2, l1, huber = SmoothL1)
@@ -217,9 +219,14 @@ class DifferentiableBlocksWorld(nn.Module):
         self.default_criteria = name in ('mse', 'l2') and tv_type == 'l2sq'
         self.loss_weights = {k: v for k, v in weights.items() if v > 0}
         self.loss_names = [f'loss_{n}' for n in list(self.loss_weights.keys()) + ['total']]
+        if self.perceptual_name == 'ssim' and 'perceptual' in self.loss_weights:
+            from .metrics import SSIMTerm
+            self.perceptual_fn = SSIMTerm()
 
     def set_perceptual(self, fn):
-        """fn(imgs, rec) -> scalar, e.g. lpips.LPIPS(net='vgg') with normalize=True (loss.py:32-40)."""
+        """fn(imgs, rec) -> scalar, e.g. lpips.LPIPS(net='vgg') with normalize=True (loss.py:32-40).  Replaces the built-in term that
+        perceptual_name: ssim installed."""
+        self._modules.pop('perceptual_fn', None)        # (a module installed before: a plain callable may take its place)
         self.perceptual_fn = fn
 
     # ------------------------------------------------------------------------------------------------ bookkeeping
@@ -629,12 +636,12 @@ class DifferentiableBlocksWorld(nn.Module):
     # ------------------------------------------------------------------------------------------------ evaluation (dbw.py:464-493)
     @torch.no_grad()
     def quantitative_eval(self, loader, device, hard_inference=True):
-        """PSNR / SSIM (/ LPIPS when a perceptual network was supplied with set_perceptual) of the reconstruction over `loader`
+        """PSNR / SSIM (/ LPIPS when a perceptual network was supplied with set_perceptual; never the built-in SSIM term) of the reconstruction over `loader`
         (batches of (inp, labels) like the reference's datasets).  hard_inference: exact anti-aliased render of the joined scene
         (4x resolution, sigma 0, one face per pixel, 4x4 average pooling; renderer.py:56-60,178-183), else the soft decoupled
         prediction.  -> OrderedDict like the reference's; LPIPS is NaN when no network is installed."""
         from collections import OrderedDict
-        from .metrics import AverageMeter, mse2psnr, ssim
+        from .metrics import AverageMeter, SSIMTerm, mse2psnr, ssim
         was_training = self.training
         self.eval()
         opacities = self.get_opacities()
@@ -654,7 +661,9 @@ class DifferentiableBlocksWorld(nn.Module):
             meters['L_rec'].update(sum(losses[k] for k in ('rgb', 'perceptual') if k in losses), N=N)
             meters['PSNR'].update(mse2psnr(F.mse_loss(imgs, rec)), N=N)
             meters['SSIM'].update(ssim(imgs, rec, padding=False).mean(), N=N)
-            meters['LPIPS'].update(self.perceptual_fn(imgs, rec) if self.perceptual_fn is not None else float('nan'), N=N)
+            # (the built-in SSIM term is no LPIPS: the column stays NaN, the term is part of L_rec and L_tot)
+            lpips_fn = None if isinstance(self.perceptual_fn, SSIMTerm) else self.perceptual_fn
+            meters['LPIPS'].update(lpips_fn(imgs, rec) if lpips_fn is not None else float('nan'), N=N)
         self.train(was_training)
         return OrderedDict([('n_blocks', n_blocks)] + [(k, m.avg) for k, m in meters.items()]
                            + [(f'alpha{k}', a.item()) for k, a in enumerate(opacities)])
@@ -769,7 +778,7 @@ class DifferentiableBlocksWorld(nn.Module):
         the constant half of its work per training view (lpips_vgg.LPIPSVGG.cache_targets); never needed for the value."""
         if self.perceptual_fn is None:
             raise RuntimeError('perceptual_weight > 0 needs model.set_perceptual(fn): lpips is a third-party network '
-                               'outside the HIP path (SURVEY.md 8a A10)')
+                               "outside the HIP path (SURVEY.md 8a A10); loss.perceptual_name: 'ssim' installs the built-in SSIM term")
         # the perceptual criterion is a mean over the views it is given: under view-sharded data parallelism the gradients of all ranks
         # are SUMMED, so a rank's term is weighted by its share of the global batch (like the MSE, which is normalised by the
         # global element count) -- the sum over ranks is then the reference's mean over the whole batch

@@ -73,6 +73,18 @@ def ssim(img1, img2, window_size=11, padding=False):
     return ssim_map(img1, img2, window_size, padding=padding).flatten(1).mean(1)
 
 
+class SSIMTerm(torch.nn.Module):
+    """The reference's SSIMLoss (loss.py:124-156, padding=True) as the perceptual term of the loss (`perceptual_name: ssim`):
+    criterion(imgs, rec) -> mean over the batch, the channels and the pixels of 1 - SSIM, a scalar (ops.ssim_term: one HIP kernel for value
+    and gradient on the GPU).  The reference's forward returns one value per image, with which its total loss is a vector for more than one
+    view; the mean over the batch equals it for one view and is what LPIPSLoss makes of its per-image values.  No parameters, no weights to
+    load, no target cache."""
+
+    def forward(self, imgs, rec):
+        from .ops import ssim_term
+        return ssim_term(imgs, rec)
+
+
 CHAMFER_FACTOR = 10            # utils/metrics.py:14: the usual factor Chamfer is reported with (OccNet, DVR)
 
 

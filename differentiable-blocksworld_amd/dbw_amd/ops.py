@@ -831,6 +831,54 @@ def image_scores(a, b, padding=False, return_map=False):
     return res + (m,) if return_map else res
 
 
+def ssim_term_value_grad(imgs, rec, with_grad=True):
+    """dbw_monitor_ssim_term as it stands: imgs, rec (N,3,H,W) fp32 contiguous on the GPU, N > 0 -> (value (1,) fp64 = mean(1 - SSIM) with
+    zero padding, d value / d rec (N,3,H,W) fp32 -- None without with_grad).  Two launches on the current stream, no host read."""
+    lib = _monitor_lib()
+    a_c, b_c = _chk(imgs, torch.float32, 'imgs'), _chk(rec, torch.float32, 'rec')
+    if a_c.dim() != 4 or a_c.shape[1] != 3 or a_c.shape != b_c.shape or a_c.shape[0] == 0:
+        raise ValueError(f'imgs, rec: two (N,3,H,W) tensors, N > 0, got {tuple(a_c.shape)} and {tuple(b_c.shape)}')
+    N, _, H, W = a_c.shape
+    dev = a_c.device
+    value = torch.empty(1, dtype=torch.float64, device=dev)
+    grad = torch.empty_like(b_c) if with_grad else None
+    ws = torch.empty(lib.dbw_monitor_ssim_term_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
+    _lib.call('dbw_monitor_ssim_term', _ptr(a_c), _ptr(b_c), N, H, W, _ptr(ws), _ptr(grad), _ptr(value), _stream(a_c))
+    return value, grad
+
+
+class _SsimTerm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, imgs, rec):
+        value, grad = ssim_term_value_grad(imgs, rec.detach(), with_grad=ctx.needs_input_grad[1])
+        ctx.save_for_backward(grad)
+        return value[0].to(rec.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return None, grad * g
+
+
+def _ssim_term_kernel_ok(imgs, rec):
+    return (imgs.is_cuda and rec.is_cuda and imgs.dtype == rec.dtype == torch.float32 and imgs.is_contiguous() and rec.is_contiguous()
+            and not imgs.requires_grad and imgs.dim() == 4 and imgs.shape == rec.shape and imgs.shape[1] == 3 and imgs.numel() > 0)
+
+
+def ssim_term(imgs, rec):
+    """The SSIM term of the loss: mean over n, c, y, x of 1 - SSIM(imgs, rec), (N,3,H,W) in [0, 1], 11 taps, sigma 1.5, zero padding (the
+    reference's SSIMLoss(padding=True), averaged over the batch) -> scalar on the device of the inputs, differentiable in rec.
+    fp32 contiguous GPU tensors: one dbw_monitor_ssim_term, which leaves the gradient beside the value where rec requires one; the backward
+    scales it by the incoming scalar.  imgs gets no gradient there.  Anything the kernel does not take (CPU tensors, another dtype, strides,
+    imgs that requires a gradient, an empty batch) goes through metrics.ssim_map(padding=True) and autograd."""
+    if not _ssim_term_kernel_ok(imgs, rec):
+        from .metrics import ssim_map as _ssim_map
+        if imgs.dim() != 4 or imgs.shape != rec.shape:
+            raise ValueError(f'imgs, rec: two (N,C,H,W) tensors, got {tuple(imgs.shape)} and {tuple(rec.shape)}')
+        return (1 - _ssim_map(imgs, rec, padding=True)).mean()
+    return _SsimTerm.apply(imgs, rec)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # image ingest (include/dbw_ingest.h)
 # ---------------------------------------------------------------------------------------------------------------------

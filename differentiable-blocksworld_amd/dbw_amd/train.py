@@ -1,5 +1,5 @@
-"""python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N] [--lpips-vgg F --lpips-lin F | --no-perceptual]
-                          [--resume [TAG]] [--no-record]
+"""python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
+                          [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -15,7 +15,9 @@ model.mesh.R_world: auto (T_world: auto and S_world: auto beside it) on a custom
 the cloud and the cameras (worldfit.estimate_world_frame), printed and written to <run_dir>/world_frame.yml before the model is built.
 
 The perceptual term needs the weights of a VGG16 and of the LPIPS heads, which do not ship with the package: a config with
-perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so)."""
+perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so).  With
+model.loss.perceptual_name: ssim -- or --perceptual ssim, which overrides the config's key -- the term is the built-in SSIM term
+(metrics.SSIMTerm) and needs no file; giving the LPIPS weight files beside it is refused as a contradiction."""
 import argparse
 import os
 import sys
@@ -33,6 +35,8 @@ def parse_args(argv=None):
     ap.add_argument('--epochs', type=int, default=None, help='override training.n_epoches')
     ap.add_argument('--lpips-vgg', default=None, help="state dict of torchvision's vgg16().features (torch.save)")
     ap.add_argument('--lpips-lin', default=None, help="state dict with lpips' lin{k}.model.1.weight tensors (torch.save)")
+    ap.add_argument('--perceptual', choices=('lpips', 'ssim'), default=None,
+                    help="the perceptual term, overriding model.loss.perceptual_name: 'ssim' is built in and needs no weight files")
     ap.add_argument('--no-perceptual', action='store_true', help='train without the perceptual term')
     ap.add_argument('--resume', nargs='?', const=True, default=None, metavar='TAG', help="continue the run TAG of this dataset (default: --tag's own run)")
     ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
@@ -41,17 +45,25 @@ def parse_args(argv=None):
 
 
 def prepare_config(args):
-    """The config of a run, with the perceptual term settled: kept (both weight files given), dropped (--no-perceptual) or refused."""
+    """The config of a run, with the perceptual term settled: kept (the built-in SSIM term, or LPIPS with both weight files given), dropped
+    (--no-perceptual) or refused."""
     from .dataset import load_config
     cfg = load_config(args.config, args.default)
     loss = cfg.get('model', {}).get('loss', {})
+    if getattr(args, 'perceptual', None) is not None:
+        loss['perceptual_name'] = args.perceptual
     if (loss.get('perceptual_weight') or 0) > 0:
         if args.no_perceptual:
             print(f"--no-perceptual: perceptual_weight {loss['perceptual_weight']} -> 0, the run optimises the other terms only")
             loss['perceptual_weight'] = 0
+        elif loss.get('perceptual_name', 'lpips') == 'ssim':
+            if args.lpips_vgg or args.lpips_lin:
+                raise SystemExit(f'{args.config}: perceptual_name = ssim is the built-in SSIM term and loads no weights: --lpips-vgg / --lpips-lin '
+                                 'contradict it (drop them, or give --perceptual lpips)')
         elif not (args.lpips_vgg and args.lpips_lin):
             raise SystemExit(f"{args.config}: perceptual_weight = {loss['perceptual_weight']} needs the LPIPS network's weights, which do not "
-                             'ship with this package: give --lpips-vgg and --lpips-lin, or --no-perceptual to train without the term')
+                             'ship with this package: give --lpips-vgg and --lpips-lin, or --no-perceptual to train without the term, or '
+                             '--perceptual ssim for the built-in SSIM term')
     if args.epochs is not None:
         cfg.setdefault('training', {})['n_epoches'] = args.epochs
     return cfg
@@ -121,7 +133,7 @@ def main(argv=None):
     train, val, test = create_train_val_test(cfg, args.data_root, args.device)
     resolve_world_frame(cfg, train, args.device, run_dir, start.get('resume'))
     model = create_model(cfg, train.img_size).to(args.device).train()
-    if 'perceptual' in model.loss_weights:
+    if 'perceptual' in model.loss_weights and model.perceptual_name != 'ssim':     # (ssim: the model installed its built-in term)
         from .lpips_vgg import LPIPSVGG
         net = LPIPSVGG()
         net.load_weights(torch.load(args.lpips_vgg, map_location='cpu'), torch.load(args.lpips_lin, map_location='cpu'))

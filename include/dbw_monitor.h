@@ -44,6 +44,26 @@ size_t dbw_image_scores_workspace_bytes(int N, int H, int W, int padding);
 int dbw_image_scores(const float *a, const float *b, int N, int H, int W, int padding, void *workspace, float *ssim_map, double *out,
                      dbw_stream_t stream);
 
+/* SSIM as a loss term (csrc/ssim_term.hip), added under revision 1 of this header.
+ * Bytes of `workspace` that dbw_monitor_ssim_term needs for these sizes (one fp64 per workgroup); 0 for sizes it refuses and for N = 0. */
+size_t dbw_monitor_ssim_term_workspace_bytes(int N, int H, int W);
+
+/* target, rec (N,3,H,W) fp32 in [0, 1] ->
+ *   value[0] = mean over the M = N*3*H*W elements of (1 - SSIM(target, rec)), fp64, on the device;
+ *   grad, when not NULL: (N,3,H,W) fp32, d value / d rec.  NULL: the value only, the same bits.
+ * SSIM is that of dbw_image_scores with padding = 1 (zero padding, the weights not renormalised: F.conv2d(padding=5)), the same compensated
+ * filters in the same order: value[0] is 1 - (the sum of out[n][1] over n) / M up to the last bits of the fp64 additions.  With
+ * m = (mu1, mu2, Eaa, Ebb, Eab) the filtered statistics of a window and S = n1 n2 / (d1 d2) its SSIM,
+ *   A = dS/dmu2,  B = dS/dEbb = -S / d2,  C = dS/dEab = 2 n1 / (d1 d2)            (maps, zero outside the image)
+ *   grad_q = -(1/M) [blur(A)_q + 2 rec_q blur(B)_q + target_q blur(C)_q]
+ * with blur the same zero-padded filter (csrc/score_math.h: ssim_deriv, ssim_grad_pixel).  One kernel -- a workgroup per 16 x 32 tile of
+ * one channel, the statistics and the three maps held in LDS -- and one that adds the workgroups' fp64 partial values in a fixed order:
+ * no atomics, two calls on the same inputs give the same bits.  Rows whose W is a multiple of 4 and whose images are 16-byte aligned are
+ * read as 16-byte loads; any other shape element by element, same results.  workspace: dbw_monitor_ssim_term_workspace_bytes(...) bytes,
+ * 8-byte aligned, as value is.  N = 0: nothing is launched, value stays as it is.  H * W < 2^31. */
+int dbw_monitor_ssim_term(const float *target, const float *rec, int N, int H, int W, void *workspace, float *grad, double *value,
+                          dbw_stream_t stream);
+
 /* table: n + 2 doubles on the device; vals: HOST array of n <= DBW_METER_MAX_VALUES DEVICE pointers, each to one fp32.  One kernel:
  *   table[i] += (double)*vals[i] * weight  (i < n),   table[n] += weight,
  *   table[n + 1] = step if it is negative and any *vals[i] is not finite (the first such step stays). */
