@@ -46,6 +46,14 @@ DBW_HD void lens_source(const LensParams &L, int i, int j, float *u, float *v) {
     *v = yd * L.fy + L.cy - 0.5f;
 }
 
+// Whether output pixel (i, j) reads inside the source frame: 0 <= u <= W - 1 and 0 <= v <= H - 1 of lens_source, not clamped (false for
+// a NaN).  The validity mask of a frame rectified without a crop (dbw_lens_valid_u8).
+DBW_HD bool lens_valid(const LensParams &L, int i, int j, int H, int W) {
+    float u, v;
+    lens_source(L, i, j, &u, &v);
+    return u >= 0.0f && u <= (float)(W - 1) && v >= 0.0f && v <= (float)(H - 1);
+}
+
 // One axis of a sample: the coordinate clamped to [0, size - 1], the lower corner (at most size - 2) and the weight of the upper one.
 DBW_HD int lens_split(float t, int size, float *w) {
     t = t > 0.0f ? t : 0.0f;                                  // (false for a NaN: 0)

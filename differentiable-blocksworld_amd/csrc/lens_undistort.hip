@@ -97,6 +97,14 @@ __global__ void __launch_bounds__(64 * LENS_ROWS) lens_undistort_kernel(LensArgs
     }
 }
 
+// The validity map of the rectified frame (dbw_lens_valid_u8): one byte per output pixel, once per scene -- a lane per pixel, rows of
+// consecutive bytes per wave.
+__global__ void __launch_bounds__(256) lens_valid_kernel(int H, int W, LensParams L, uint8_t *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long long)H * W) return;
+    out[p] = lens_valid(L, (int)(p / W), (int)(p % W), H, W) ? 255 : 0;
+}
+
 bool finite_all(const float *v, int n) {
     for (int k = 0; k < n; ++k)
         if (!(v[k] - v[k] == 0.0f)) return false;
@@ -123,4 +131,13 @@ extern "C" int dbw_images_undistort_u8(const uint8_t *src, int N, int H, int W, 
     const dim3 grid((unsigned)((A.quads + 63) / 64), (unsigned)((H + LENS_ROWS - 1) / LENS_ROWS), (unsigned)(groups < 65535 ? groups : 65535));
     hipLaunchKernelGGL(lens_undistort_kernel, grid, dim3(64, LENS_ROWS), 0, (hipStream_t)stream, A, src, out);
     return dbw_check_launch("lens_undistort_kernel");
+}
+
+extern "C" int dbw_lens_valid_u8(int H, int W, const float *lens, uint8_t *out, dbw_stream_t stream) {
+    DBW_REQUIRE(lens && out, "null pointer");
+    DBW_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1LL << 29), "bad size");
+    DBW_REQUIRE(finite_all(lens, LENS_N_PARAMS), "lens: a value that is not finite");
+    const long long blocks = ((long long)H * W + 255) / 256;
+    hipLaunchKernelGGL(lens_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, H, W, lens_params(lens), out);
+    return dbw_check_launch("lens_valid_kernel");
 }

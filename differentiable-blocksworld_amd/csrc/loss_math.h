@@ -55,6 +55,29 @@ DBW_HD float composite_mse_pixel(const float fc[3], float mask, const float ec[3
     return composite_mse_pixel(fc, mask, ec, target, has_target, two_scale, rec, gf, ge, gmask, none, false);
 }
 
+// the same composite under a validity weight m in [0, 1] of the pixel (masked_loss.hip): returns m * (the pixel's sum of squared
+// differences), and the gradients of  two_scale / 2 * m * sum_c (rec_c - target_c)^2 + <extra, rec>  through the composite -- per
+// channel d/d rec_c = (two_scale * m) * (rec_c - target_c) + extra_c, with two_scale = 2 * (weight / count) * (the upstream scalar) and
+// extra the perceptual term's d/d rec (has_extra as above).  m == 0: the target is not looked at in any way that reaches a result
+// (0 * d is +-0, and d is finite for finite images), the gradients are those of extra alone.
+DBW_HD float masked_composite_pixel(const float fc[3], float mask, const float ec[3], const float target[3], float m, float two_scale,
+                                    float rec[3], float gf[3], float ge[3], float &gmask, const float extra[3], bool has_extra) {
+    const float wm = two_scale * m;
+    float part = 0.f;
+    gmask = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        rec[c] = fc[c] * mask + (1.f - mask) * ec[c];
+        const float d = rec[c] - target[c];
+        part += d * d;
+        const float gr = has_extra ? wm * d + extra[c] : wm * d;
+        gf[c] = gr * mask;
+        ge[c] = gr * (1.f - mask);
+        gmask += gr * (fc[c] - ec[c]);
+    }
+    return m * part;
+}
+
 // torch.optim.Adam (no weight decay, no amsgrad; optimizer.py:6-18) for one element: step_size = lr / (1 - beta1^t),
 // bc2_sqrt = sqrt(1 - beta2^t)
 DBW_HD void adam_update(float &p, float g, float &m, float &v, float step_size, float beta1, float beta2, float eps, float bc2_sqrt) {

@@ -192,6 +192,8 @@ INGEST_ABI_VERSION = header_define('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION')
 # the lens rectification: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by tests/test_abi_families.py).
 LENS_SIGNATURES = {
     'dbw_images_undistort_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    # the validity map of a rectified frame, added under revision 1 of the header
+    'dbw_lens_valid_u8': [c_i, c_i, c_p, c_p, c_p],
 }
 LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h
 LENS_ABI_VERSION = header_define('dbw_lens.h', 'DBW_LENS_ABI_VERSION')
@@ -204,10 +206,15 @@ MONITOR_SIGNATURES = {
     'dbw_meter_reset': [c_p, c_i, c_p],
     # SSIM as a loss term (csrc/ssim_term.hip), added under revision 1 of the header
     'dbw_monitor_ssim_term': [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    # the image terms under a validity mask (csrc/masked_loss.hip), added under revision 1 of the header
+    'dbw_monitor_masked_composite': [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    'dbw_monitor_masked_ssim_term': [c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p],
 }
 MONITOR_OTHER_SIGNATURES = {
     'dbw_image_scores_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
     'dbw_monitor_ssim_term_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'dbw_monitor_masked_composite_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'dbw_monitor_masked_ssim_term_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
 }
 METER_MAX_VALUES = 16                                         # DBW_METER_MAX_VALUES of include/dbw_monitor.h
 MONITOR_ABI_VERSION = header_define('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION')

@@ -65,6 +65,17 @@ def get_files_from(dir_path, valid_extensions=IMG_EXTENSIONS, recursive=True, so
     return sorted(files) if sort else files
 
 
+def decode_mask(path, size):
+    """One mask file -> (H,W) uint8, 255 where Image.open(f).convert('L') is not zero and 0 elsewhere; size (H,W): the frame's, which the
+    mask must have."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.array(im.convert('L'))
+    if a.shape != tuple(size):
+        raise ValueError(f'{path}: a mask of {a.shape}, its frame is {tuple(size)}')
+    return np.where(a != 0, 255, 0).astype(np.uint8)
+
+
 def decode_rgb(path):
     """One image file -> (H,W,3) uint8, as Image.open(f).convert('RGB') reads it (dtu.py:63)."""
     from PIL import Image
@@ -76,10 +87,22 @@ class ImageStore:
     """The decoded frames of one scene directory, resident on one device: (N,3,H,W) fp32 targets of one img_size, filled file by file the
     first time a view is asked for, and optionally the raw (N,Hraw,Wraw,3) uint8 stack.  The three splits of a scene share one store.
     prepare: a callable from the uploaded (n,Hraw,Wraw,3) uint8 chunk on the device to a chunk of the same kind, applied before the
-    resize (a custom scene's lens rectification); the raw stack keeps what came off disk."""
+    resize (a custom scene's lens rectification); the raw stack keeps what came off disk.
+    Validity masks: mask_files -- one entry per frame, a file or None (all valid) -- and / or valid -- one (Hraw,Wraw) uint8
+    map of 0 / 255 for every frame, or a callable from the device to it (a lens map: ops.lens_valid_u8) -- make the store keep
+    masks (N,1,h,w) fp32 of 0 / 1 beside the targets.  A decoded mask (decode_mask: 0 / 255) is expanded to 3 channels, goes through
+    mask_prepare (default: prepare, the frames' own warp), is ANDed with valid and resized by the kernel that resizes the frames
+    (ops.resample_u8, out='u8'); a training pixel is valid where that byte is 255, that is where its whole footprint is valid.  The
+    existing kernels do the warp and the resize: three identical channels on a once-per-scene pass are accepted for that."""
 
-    def __init__(self, files, img_size, chunk=16, prepare=None):
+    def __init__(self, files, img_size, chunk=16, prepare=None, mask_files=None, mask_prepare=None, valid=None):
         self.files, self.img_size, self.chunk, self.prepare = list(files), tuple(img_size), chunk, prepare
+        self.mask_files = None if mask_files is None else list(mask_files)
+        if self.mask_files is not None and len(self.mask_files) != len(self.files):
+            raise ValueError(f'{len(self.mask_files)} masks for {len(self.files)} frames')
+        self.mask_prepare = prepare if mask_prepare is None else mask_prepare
+        self.valid, self.has_masks = valid, mask_files is not None or valid is not None
+        self.masks = None
         self.device = self.imgs = self.raw = None
         self.have, self.have_raw = np.zeros(len(self.files), bool), np.zeros(len(self.files), bool)
 
@@ -97,6 +120,14 @@ class ImageStore:
             if self.device is None:
                 self.device, self.raw_size = device, first.shape[:2]
                 self.imgs = torch.empty(len(self.files), 3, *self.img_size, dtype=torch.float32, device=device)
+                if self.has_masks:
+                    self.masks = torch.empty(len(self.files), 1, *self.img_size, dtype=torch.float32, device=device)
+                    if callable(self.valid):
+                        self.valid = self.valid(device)
+                    if self.valid is not None:
+                        self.valid = torch.as_tensor(self.valid, dtype=torch.uint8).to(device)
+                        if tuple(self.valid.shape) != tuple(self.raw_size):
+                            raise ValueError(f'valid: {tuple(self.valid.shape)}, the frames are {tuple(self.raw_size)}')
             if keep_raw and self.raw is None:
                 self.raw = torch.empty(len(self.files), *self.raw_size, 3, dtype=torch.uint8, device=device)
             slot = b % 2                                         # two staging buffers: the next chunk is decoded while this one is copied
@@ -118,6 +149,8 @@ class ImageStore:
                 events[slot].record(torch.cuda.current_stream(device))
             idx = torch.as_tensor(part, device=device)
             self.imgs[idx] = ops.resample_u8(raw if self.prepare is None else self.prepare(raw), self.img_size, out='f32')
+            if self.has_masks:
+                self.masks[idx] = self._masks_of(part, device)
             if self.raw is not None:
                 self.raw[idx] = raw
                 self.have_raw[part] = True
@@ -125,13 +158,33 @@ class ImageStore:
         idx = torch.as_tensor(ids, dtype=torch.long, device=device)
         return self.imgs[idx], (self.raw[idx] if keep_raw else None)
 
+    def _masks_of(self, part, device):
+        """(n,1,h,w) fp32 masks of the frames `part` (file indices), made on the device as the class docstring says."""
+        H, W = self.raw_size
+        m = torch.full((len(part), H, W, 3), 255, dtype=torch.uint8)
+        if self.mask_files is not None:
+            for j, i in enumerate(part):
+                if self.mask_files[i] is not None:
+                    m[j] = torch.from_numpy(decode_mask(self.mask_files[i], (H, W)))[:, :, None]
+        m = m.to(device)
+        if self.mask_prepare is not None:
+            m = self.mask_prepare(m)
+        if self.valid is not None:
+            m = m & self.valid[None, :, :, None]
+        small = ops.resample_u8(m.contiguous(), self.img_size, out='u8')
+        return (small[..., 0] == 255).to(torch.float32)[:, None]
+
+    def get_masks(self, ids):
+        """masks (V,1,h,w) of the file indices `ids`, after get() has made them."""
+        return self.masks[torch.as_tensor([int(i) for i in ids], dtype=torch.long, device=self.device)]
+
 
 # ---- scenes -------------------------------------------------------------------------------------------------------------------------------------
 class _Scene:
     """What the two dataset kinds share (dtu.py / bmvs.py): files, cameras, view ids, resident views and loaders."""
     name, folder, raw_img_size, n_channels = None, None, None, 3
 
-    def __init__(self, root, tag, img_size, split, view_ids=None, store=None):
+    def __init__(self, root, tag, img_size, split, view_ids=None, store=None, masks=False):
         self.split, self.tag = split, tag
         self.data_path = Path(root) / self.folder / tag / 'image'
         self.input_files = get_files_from(self.data_path, IMG_EXTENSIONS, recursive=True, sort=True)
@@ -141,9 +194,16 @@ class _Scene:
         cams = load_idr_cameras(self.data_path.parent / 'cameras.npz', self.raw_img_size, n_views=N)
         self.K, self.R, self.T, self.scale_mat = cams['K'], cams['R'], cams['T'], cams['scale_mat']
         self.pc_gt = torch.zeros(1, 3)
-        if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size):
-            raise ValueError('store: made for other files or another img_size')
-        self.store = store if store is not None else ImageStore(self.input_files, self.img_size)
+        # masks=True: the IDR layout's <tag>/mask/* beside image/, in sorted order, one per image
+        self.mask_files = None
+        if masks:
+            self.mask_files = get_files_from(self.data_path.parent / 'mask', IMG_EXTENSIONS, recursive=True, sort=True)
+            if len(self.mask_files) != N:
+                raise ValueError(f"{self.data_path.parent / 'mask'}: {len(self.mask_files)} masks for {N} images")
+        if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size
+                                  or store.has_masks != bool(masks)):
+            raise ValueError('store: made for other files, another img_size or other masks')
+        self.store = store if store is not None else ImageStore(self.input_files, self.img_size, mask_files=self.mask_files)
 
     def _split_ids(self, N, view_ids):
         return view_ids
@@ -157,10 +217,12 @@ class _Scene:
 
     def views(self, device, keep_raw=False, chunk=None):
         """{'imgs' (V,3,H,W) fp32, 'K' (V,4,4), 'R' (V,3,3), 'T' (V,3)} of this split, in its order, resident on `device`; with keep_raw
-        also 'raw' (V,Hraw,Wraw,3) uint8."""
+        also 'raw' (V,Hraw,Wraw,3) uint8; for a scene with validity masks also 'masks' (V,1,H,W) fp32 of 0 / 1."""
         ids = self.ids()
         imgs, raw = self.store.get(device, ids, keep_raw=keep_raw, chunk=chunk)
         out = {'imgs': imgs, 'K': self.K[ids].to(device), 'R': self.R[ids].to(device), 'T': self.T[ids].to(device)}
+        if self.store.has_masks:
+            out['masks'] = self.store.get_masks(ids)
         if keep_raw:
             out['raw'] = raw
         return out
@@ -196,8 +258,8 @@ class DTUScene(_Scene):
     (a (1,3) zero tensor where the scan's file is absent), scale_mat: the matrix back to the DTU frame."""
     name, folder, raw_img_size = 'dtu', 'DTU', (1200, 1600)
 
-    def __init__(self, root, tag, img_size, split, view_ids=None, store=None):
-        super().__init__(root, tag, img_size, split, view_ids=view_ids, store=store)
+    def __init__(self, root, tag, img_size, split, view_ids=None, store=None, masks=False):
+        super().__init__(root, tag, img_size, split, view_ids=view_ids, store=store, masks=masks)
         ply = self.data_path.parent.parent / 'Points' / 'stl' / 'stl{}_total.ply'.format(tag.replace('scan', '').zfill(3))
         if ply.exists():
             from .eval3d import read_ply_points
@@ -311,10 +373,14 @@ class CustomScene(_Scene):
     src/dataset/nerfstudio.py:35-77 without the `nerfstudio` package, and rectifies the frames on the device (ops.undistort_u8, zoomed so
     that every pixel is valid: lens_zoom) where the reference trains a pinhole renderer on the distorted ones; undistort=False is the
     reference's behaviour.  The train split holds ceil(0.9 N) frames spread evenly, test the others (shuffled under the seed len(tag)),
-    val none.  scale_mat: the normalised frame back to the file's; pc_gt: the points of `ply_file_path` or points.ply, normalised."""
+    val none.  scale_mat: the normalised frame back to the file's; pc_gt: the points of `ply_file_path` or points.ply, normalised.
+    masks=True reads each frame's `mask_path` (relative to the json, as Nerfstudio's exporters write it; a frame without one is all
+    valid) into views()['masks']; lens='mask' rectifies at zoom 1 and masks what reads outside the source frame (ops.lens_valid_u8)
+    instead of cropping it away with lens_zoom ('crop'), and never raises lens_zoom's ValueError."""
     name, folder = 'custom', 'custom'
 
-    def __init__(self, root, tag, split, downscale_factor=1, img_size=None, undistort=True, normalize='poses', view_ids=None, store=None):
+    def __init__(self, root, tag, split, downscale_factor=1, img_size=None, undistort=True, normalize='poses', view_ids=None, store=None,
+                 masks=False, lens='crop'):
         import json
         self.split, self.tag = split, tag
         self.data_path = Path(root) / self.folder / tag
@@ -369,10 +435,18 @@ class CustomScene(_Scene):
         else:
             self.view_ids = []
 
+        if lens not in ('crop', 'mask'):
+            raise ValueError(f"lens: 'crop' or 'mask', got {lens!r}")
         rectify = bool(undistort) and any(c != 0 for c in self.dist)
-        self.zoom = lens_zoom(h, w, self.intr, self.dist) if rectify else 1.0
+        lens_mask = rectify and lens == 'mask'
+        self.zoom = lens_zoom(h, w, self.intr, self.dist) if (rectify and not lens_mask) else 1.0
         intr, dist, zoom = self.intr, self.dist, self.zoom
         self.prepare = (lambda raw: ops.undistort_u8(raw, intr, dist, zoom)) if rectify else None
+        self.mask_files = None
+        if masks:
+            self.mask_files = [self._frame_file(path.parent, f['mask_path']) if f.get('mask_path') else None for f in frames]
+        valid = (lambda device: ops.lens_valid_u8(h, w, intr, dist, 1.0, device=device)) if lens_mask else None
+        has_masks = self.mask_files is not None or valid is not None
 
         c2w = np.stack([np.asarray(f['transform_matrix'], dtype=np.float64)[:4, :4] for f in frames])
         if c2w.shape[1] == 3:
@@ -413,9 +487,10 @@ class CustomScene(_Scene):
             self.pc_gt = torch.from_numpy(points @ F[:3, :3].T + F[:3, 3]).float()
 
         if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size
-                                  or (store.prepare is None) != (self.prepare is None)):
-            raise ValueError('store: made for other files, another img_size or another lens treatment')
-        self.store = store if store is not None else ImageStore(self.input_files, self.img_size, prepare=self.prepare)
+                                  or (store.prepare is None) != (self.prepare is None) or store.has_masks != has_masks):
+            raise ValueError('store: made for other files, another img_size, another lens treatment or other masks')
+        self.store = store if store is not None else ImageStore(self.input_files, self.img_size, prepare=self.prepare,
+                                                                mask_files=self.mask_files, valid=valid)
 
     def world_frame(self, device=None, T_range=(1, 1, 1), **kw):
         """worldfit.estimate_world_frame on this capture's cloud and cameras (both in the normalised frame R, T live in) -> WorldFrame: the

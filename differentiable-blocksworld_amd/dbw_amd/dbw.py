@@ -598,6 +598,15 @@ class DifferentiableBlocksWorld(nn.Module):
             self.build_env_scene()
             self.build_blocks_scene(filter_transparent=not self.is_live('coarse_learning'))
             return self.compute_losses(inp['imgs'], None, layers=None)
+        if 'masks' in inp:
+            # validity masks: the fused epilogue stands aside, the layers are rendered and both image terms take the masks
+            refusal = self._mask_refusal()
+            if refusal is not None:
+                raise NotImplementedError(f'a batch with masks: {refusal}')
+            masks = inp['masks']
+            msum = inp['mask_sum'] if 'mask_sum' in inp else float(masks.sum(dtype=torch.float64))      # (one host read without it)
+            fg, env = self.render_layers(inp)
+            return self.compute_losses(inp['imgs'], None, layers=(fg, env), masks=masks, mask_count=3.0 * float(msum))
         if not self.decouple_rendering:                                # one joined scene, one soft pass; losses through the general path
             return self.compute_losses(inp['imgs'], self.render_joined(inp)[:, :3])
         fused = self._forward_fused(inp) if self.fused_loss_epilogue else None
@@ -605,6 +614,16 @@ class DifferentiableBlocksWorld(nn.Module):
             return fused
         fg, env = self.render_layers(inp)
         return self.compute_losses(inp['imgs'], None, layers=(fg, env))
+
+    def _mask_refusal(self):
+        """-> why this model cannot take a batch with validity masks, or None."""
+        if not self.decouple_rendering:
+            return 'decouple_rendering is off: the masked reconstruction term is the decoupled composite'
+        if 'rgb' not in self.loss_weights or not self.default_criteria:
+            return f'criteria {self.criterion_name} / {self.tv_type}: the masked kernels have mse and l2sq, with an rgb term'
+        if self.world_size > 1:
+            return 'data-parallel training needs a global valid count, which is not implemented'
+        return None
 
     def _forward_fused(self, inp):
         """The training iteration with the reconstruction loss as the epilogue of the fg pass (ops.render_decoupled_mse): env pass,
@@ -773,9 +792,11 @@ class DifferentiableBlocksWorld(nn.Module):
             self.train(was_training)
 
     # ------------------------------------------------------------------------------------------------ losses (dbw.py:361-408)
-    def _perceptual_term(self, imgs, rec, coarse, view_ids=None):
+    def _perceptual_term(self, imgs, rec, coarse, view_ids=None, masks=None, count=None):
         """view_ids: the batch's `view_ids` entry, if the caller's loader provides one (trainer.py does) -- handed to a criterion that keeps
-        the constant half of its work per training view (lpips_vgg.LPIPSVGG.cache_targets); never needed for the value."""
+        the constant half of its work per training view (lpips_vgg.LPIPSVGG.cache_targets); never needed for the value.
+        masks, count: a criterion that declares takes_masks = True (metrics.SSIMTerm) receives them; any other is called on
+        imgs * masks and rec * masks, its own normalisation left alone (a target cache was built from imgs * masks: trainer.py)."""
         if self.perceptual_fn is None:
             raise RuntimeError('perceptual_weight > 0 needs model.set_perceptual(fn): lpips is a third-party network '
                                "outside the HIP path (SURVEY.md 8a A10); loss.perceptual_name: 'ssim' installs the built-in SSIM term")
@@ -785,19 +806,52 @@ class DifferentiableBlocksWorld(nn.Module):
         share = 1.0
         if self.world_size > 1 and getattr(self, '_global_count', None):
             share = imgs.numel() / float(self._global_count)
+        if masks is not None and getattr(self.perceptual_fn, 'takes_masks', False):
+            value = self.perceptual_fn(imgs, rec, masks=masks, count=count)
+            return self.loss_weights['perceptual'] * phase.late_factor(coarse) * share * value
+        if masks is not None:
+            imgs, rec = imgs * masks, rec * masks
         if view_ids is not None and getattr(self.perceptual_fn, 'target_cache', None) is not None:
             value = self.perceptual_fn(imgs, rec, view_ids=view_ids)
         else:
             value = self.perceptual_fn(imgs, rec)
         return self.loss_weights['perceptual'] * phase.late_factor(coarse) * share * value
 
-    def compute_losses(self, imgs, rec, layers=None, rgb_value=None):
+    def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None):
+        """masks (B,1,H,W) weights in [0, 1] with mask_count = 3 * their sum (a host number; computed with one host read when None): the
+        two image terms under the validity mask -- layers must be given --, the regularisers unchanged."""
         w = self.loss_weights
         dev = imgs.device
         # (the epoch's loss factors in eval mode too; view-independent regularisers: every rank computes them identically, scaled by
         # 1 / world_size so that the sum all-reduce of gradients counts them once, SURVEY.md 8e)
         ph = phase.phase_of(self, self.training)
         coarse, rs, ws = ph.coarse_epoch, ph.rs, self.world_size
+        if masks is not None:
+            refusal = self._mask_refusal() or (None if layers is not None else 'compute_losses needs the rendered layers')
+            if refusal is not None:
+                raise NotImplementedError(f'a batch with masks: {refusal}')
+            count = ops.mask_count(masks) if mask_count is None else float(mask_count)
+            # composite + masked MSE as one node with two outputs (its backward: one launch fed by the gradients of both), the regularisers
+            # through the regularisers-only form of ops.fused_losses, the perceptual term on the node's rec
+            rgb, rec = ops.composite_mse_masked(layers[0], layers[1], imgs, masks, ph.w_rgb, count)
+            cfg = {'rgb': None, 'count': count, 'parsimony': ph.w_parsimony, 'tv': ph.w_tv, 'tv_ground_factor': ph.tv_factor,
+                   'overlap': ph.w_overlap, 'overlap_consts': (float(self.ratio_block_scene), float(self.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS)}
+            u = None
+            if cfg['overlap']:
+                u = self._overlap_u_override
+                if u is None:
+                    u = torch.rand(self.n_blocks, OVERLAP_N_POINTS, 3, device=dev)
+            vals = ops.fused_losses(None, None, imgs, self._alpha_full, self._bkg_maps, self._blocks_maps, self._ground_maps,
+                                    self.sq_eps, self.S, self.R_6d, self.T, u, cfg)
+            losses = {k: vals[_FUSED_SLOT[k]] for k in w if k in _FUSED_SLOT}
+            losses['rgb'] = rgb
+            total = vals.sum() + rgb
+            if 'perceptual' in w:
+                losses['perceptual'] = self._perceptual_term(imgs, rec, coarse, getattr(self, '_view_ids', None), masks=masks, count=count)
+                total = total + losses['perceptual']
+            losses = {k: losses[k] for k in w}
+            losses['total'] = total
+            return losses
         if (layers is not None or rgb_value is not None) and 'rgb' in w and self.default_criteria:
             # training path: composite + MSE and the regularisers as ONE autograd node (ops.fused_losses), the phase's weights
             # folded into the kernels' scales

@@ -78,11 +78,13 @@ class SSIMTerm(torch.nn.Module):
     criterion(imgs, rec) -> mean over the batch, the channels and the pixels of 1 - SSIM, a scalar (ops.ssim_term: one HIP kernel for value
     and gradient on the GPU).  The reference's forward returns one value per image, with which its total loss is a vector for more than one
     view; the mean over the batch equals it for one view and is what LPIPSLoss makes of its per-image values.  No parameters, no weights to
-    load, no target cache."""
+    load, no target cache.  takes_masks: a batch with validity masks hands them over (masks (N,1,H,W) weights, count = 3 * their sum as a
+    host number) and the term is ops.ssim_term's masked form, instead of being called on images multiplied by the masks."""
+    takes_masks = True
 
-    def forward(self, imgs, rec):
+    def forward(self, imgs, rec, masks=None, count=None):
         from .ops import ssim_term
-        return ssim_term(imgs, rec)
+        return ssim_term(imgs, rec) if masks is None else ssim_term(imgs, rec, masks=masks, count=count)
 
 
 CHAMFER_FACTOR = 10            # utils/metrics.py:14: the usual factor Chamfer is reported with (OccNet, DVR)

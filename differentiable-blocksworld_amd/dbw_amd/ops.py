@@ -865,12 +865,66 @@ def _ssim_term_kernel_ok(imgs, rec):
             and not imgs.requires_grad and imgs.dim() == 4 and imgs.shape == rec.shape and imgs.shape[1] == 3 and imgs.numel() > 0)
 
 
-def ssim_term(imgs, rec):
+def mask_count(masks):
+    """count = 3 * sum(masks) as a python float: ONE host read (a synchronisation); a training loop passes the number instead."""
+    return 3.0 * float(masks.sum(dtype=torch.float64))
+
+
+def masked_ssim_term_value_grad(imgs, rec, masks, count, with_grad=True):
+    """dbw_monitor_masked_ssim_term as it stands: imgs, rec (N,3,H,W), masks (N,1,H,W) fp32 contiguous on the GPU, N > 0, count a host
+    number -> (value (1,) fp64 = sum masks (1 - SSIM(masks imgs, masks rec)) / count, d value / d rec (N,3,H,W) fp32 -- None without
+    with_grad).  Two launches on the current stream, no host read."""
+    lib = _monitor_lib()
+    a_c, b_c, m_c = _chk(imgs, torch.float32, 'imgs'), _chk(rec, torch.float32, 'rec'), _chk(masks, torch.float32, 'masks')
+    if a_c.dim() != 4 or a_c.shape[1] != 3 or a_c.shape != b_c.shape or a_c.shape[0] == 0:
+        raise ValueError(f'imgs, rec: two (N,3,H,W) tensors, N > 0, got {tuple(a_c.shape)} and {tuple(b_c.shape)}')
+    N, _, H, W = a_c.shape
+    if tuple(m_c.shape) != (N, 1, H, W):
+        raise ValueError(f'masks: {(N, 1, H, W)}, got {tuple(m_c.shape)}')
+    dev = a_c.device
+    value = torch.empty(1, dtype=torch.float64, device=dev)
+    grad = torch.empty_like(b_c) if with_grad else None
+    ws = torch.empty(lib.dbw_monitor_masked_ssim_term_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
+    _lib.call('dbw_monitor_masked_ssim_term', _ptr(a_c), _ptr(b_c), _ptr(m_c), N, H, W, float(count), _ptr(ws), _ptr(grad), _ptr(value),
+              _stream(a_c))
+    return value, grad
+
+
+class _MaskedSsimTerm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, imgs, rec, masks, count):
+        value, grad = masked_ssim_term_value_grad(imgs, rec.detach(), masks, count, with_grad=ctx.needs_input_grad[1])
+        ctx.save_for_backward(grad)
+        return value[0].to(rec.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return None, grad * g, None, None
+
+
+def ssim_term(imgs, rec, masks=None, count=None):
     """The SSIM term of the loss: mean over n, c, y, x of 1 - SSIM(imgs, rec), (N,3,H,W) in [0, 1], 11 taps, sigma 1.5, zero padding (the
     reference's SSIMLoss(padding=True), averaged over the batch) -> scalar on the device of the inputs, differentiable in rec.
     fp32 contiguous GPU tensors: one dbw_monitor_ssim_term, which leaves the gradient beside the value where rec requires one; the backward
     scales it by the incoming scalar.  imgs gets no gradient there.  Anything the kernel does not take (CPU tensors, another dtype, strides,
-    imgs that requires a gradient, an empty batch) goes through metrics.ssim_map(padding=True) and autograd."""
+    imgs that requires a gradient, an empty batch) goes through metrics.ssim_map(padding=True) and autograd.
+    masks (N,1,H,W) weights in [0, 1]: the term under a validity mask,
+        s = ssim_map(imgs * masks, rec * masks, padding=True);  ((1 - s) * masks).sum() / count,   count = 3 * masks.sum(),
+    0 for count == 0 -- one dbw_monitor_masked_ssim_term under the same conditions (masks fp32 contiguous, no gradient), the formula in
+    torch otherwise.  count=None costs one masks.sum() host read (mask_count); a training loop passes the number."""
+    if masks is not None:
+        if count is None:
+            count = mask_count(masks)
+        count = float(count)
+        if (_ssim_term_kernel_ok(imgs, rec) and masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
+                and not masks.requires_grad and tuple(masks.shape) == (imgs.shape[0], 1) + tuple(imgs.shape[2:])):
+            return _MaskedSsimTerm.apply(imgs, rec, masks, count)
+        from .metrics import ssim_map as _ssim_map
+        if imgs.dim() != 4 or imgs.shape != rec.shape or masks.dim() != 4:
+            raise ValueError(f'imgs, rec: two (N,C,H,W) tensors, masks (N,1,H,W); got {tuple(imgs.shape)}, {tuple(rec.shape)}, {tuple(masks.shape)}')
+        total = ((1 - _ssim_map(imgs * masks, rec * masks, padding=True)) * masks).sum()
+        return total / count if count > 0 else total * 0.0
     if not _ssim_term_kernel_ok(imgs, rec):
         from .metrics import ssim_map as _ssim_map
         if imgs.dim() != 4 or imgs.shape != rec.shape:
@@ -965,6 +1019,21 @@ def undistort_u8(raw_u8, intr, dist, zoom=1.0):
     out = torch.empty_like(src)
     if N > 0:
         _lib.call('dbw_images_undistort_u8', _ptr(src), N, H, W, lens.data_ptr(), _ptr(out), _stream(src))
+    return out
+
+
+def lens_valid_u8(H, W, intr, dist, zoom=1.0, device='cuda'):
+    """dbw_lens_valid_u8: the (H,W) uint8 validity map of the frames undistort_u8 makes with the same arguments, on `device` -- 255 where
+    the output pixel reads inside the source frame (not clamped), 0 elsewhere.  One map per scene."""
+    _lib.family('lens')
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f'a frame of {(H, W)}')
+    lens = lens_params(intr, dist, zoom)
+    out = torch.empty(H, W, dtype=torch.uint8, device=device)
+    if not out.is_cuda:
+        raise RuntimeError('lens_valid_u8 runs on the GPU (there is no CPU fallback)')
+    _lib.call('dbw_lens_valid_u8', H, W, lens.data_ptr(), _ptr(out), _stream(out))
     return out
 
 
@@ -1105,6 +1174,76 @@ def composite_mse(fg, env, imgs, count=None):
     `count` = number of elements of the GLOBAL batch (view-sharded data parallel), default this batch."""
     count = float(imgs.numel() if count is None else count)
     return _CompositeMSE.apply(fg, env, imgs, count)
+
+
+class _CompositeMSEMasked(torch.autograd.Function):
+    """(weight * sum masks (rec - imgs)^2 / count, rec) of the decoupled composite as ONE node with two outputs: the forward is
+    dbw_monitor_masked_composite (rec and the fp64 value, fixed-order reduction), the backward ONE launch of it fed by both incoming
+    gradients -- the scalar's, read from device memory, and the gradient other terms send to rec (the perceptual term)."""
+
+    @staticmethod
+    def forward(ctx, fg, env, imgs, masks, scale):
+        value, rec, saved = masked_composite_fwd(fg.detach(), env.detach(), imgs, masks, scale)
+        ctx.set_materialize_grads(False)             # an output nobody used arrives as None, not as an image of zeros to read
+        ctx.save_for_backward(*saved)
+        ctx.scale = scale
+        return value[0].to(torch.float32), rec
+
+    @staticmethod
+    def backward(ctx, g_value, g_rec):
+        fg, env, imgs, masks = ctx.saved_tensors
+        up = (g_value.detach().to(torch.float32).reshape(1).contiguous() if g_value is not None
+              else torch.zeros(1, dtype=torch.float32, device=fg.device))
+        g_fg, g_env = masked_composite_bwd(fg, env, imgs, masks, ctx.scale, up, None if g_rec is None else g_rec.detach())
+        return g_fg, g_env, None, None, None
+
+
+def masked_composite_fwd(fg, env, imgs, masks, scale):
+    """The forward of dbw_monitor_masked_composite as it stands: fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) fp32 on the GPU,
+    scale = weight / count a host number -> (value (1,) fp64 = scale * sum masks (rec - imgs)^2, rec (N,3,H,W), the four inputs as the
+    kernel read them).  Two launches on the current stream, no host read."""
+    lib = _monitor_lib()
+    fg_c, env_c = _chk(fg, torch.float32, 'fg'), _chk(env, torch.float32, 'env')
+    imgs_c, masks_c = _chk(imgs, torch.float32, 'imgs'), _chk(masks, torch.float32, 'masks')
+    if fg_c.dim() != 4:
+        raise ValueError(f'fg: (N,4,H,W), got {tuple(fg_c.shape)}')
+    N, _, H, W = fg_c.shape
+    if tuple(fg_c.shape) != (N, 4, H, W) or fg_c.shape != env_c.shape or tuple(imgs_c.shape) != (N, 3, H, W) or tuple(masks_c.shape) != (N, 1, H, W):
+        raise ValueError(f'fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W); got {tuple(fg_c.shape)}, {tuple(env_c.shape)}, '
+                         f'{tuple(imgs_c.shape)}, {tuple(masks_c.shape)}')
+    dev = fg_c.device
+    rec = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+    value = torch.zeros(1, dtype=torch.float64, device=dev)
+    if N > 0:
+        ws = torch.empty(lib.dbw_monitor_masked_composite_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
+        _lib.call('dbw_monitor_masked_composite', _ptr(fg_c), _ptr(env_c), _ptr(imgs_c), _ptr(masks_c), N, H, W, float(scale), _ptr(ws), _ptr(rec),
+                  _ptr(value), 0, 0, 0, 0, _stream(fg_c))
+    return value, rec, (fg_c, env_c, imgs_c, masks_c)
+
+
+def masked_composite_bwd(fg, env, imgs, masks, scale, upstream, grad_rec=None):
+    """The backward of dbw_monitor_masked_composite as it stands, ONE launch: upstream (1,) fp32 on the GPU -- the gradient with respect
+    to the value --, grad_rec (N,3,H,W) or None -- the gradient with respect to rec -- -> (grad_fg, grad_env) (N,4,H,W)."""
+    _monitor_lib()
+    fg, env, imgs, masks = (_chk(t, torch.float32, n) for t, n in ((fg, 'fg'), (env, 'env'), (imgs, 'imgs'), (masks, 'masks')))
+    N, _, H, W = fg.shape
+    up = _chk(upstream, torch.float32, 'upstream')
+    g_rec = None if grad_rec is None else _chk(grad_rec, torch.float32, 'grad_rec')
+    if up.numel() != 1 or (g_rec is not None and tuple(g_rec.shape) != (N, 3, H, W)):
+        raise ValueError('upstream: one fp32, grad_rec: (N,3,H,W)')
+    g_fg, g_env = torch.empty_like(fg), torch.empty_like(env)
+    if N > 0:
+        _lib.call('dbw_monitor_masked_composite', _ptr(fg), _ptr(env), _ptr(imgs), _ptr(masks), N, H, W, float(scale), 0, 0, 0, _ptr(up),
+                  _ptr(g_rec), _ptr(g_fg), _ptr(g_env), _stream(fg))
+    return g_fg, g_env
+
+
+def composite_mse_masked(fg, env, imgs, masks, weight, count):
+    """fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) weights in [0, 1], count = 3 * sum(masks) of the GLOBAL batch as a host number
+    -> (weight * sum masks (rec - imgs)^2 / count: a scalar, 0 for count == 0; rec (N,3,H,W): the composite).  Both outputs are
+    differentiable in fg and env; one HIP launch computes the gradients of whatever was built on the two."""
+    count = float(count)
+    return _CompositeMSEMasked.apply(fg, env, imgs, masks, float(weight) / count if count > 0 else 0.0)
 
 
 def composite(fg, env):

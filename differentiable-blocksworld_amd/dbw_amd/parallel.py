@@ -126,16 +126,23 @@ class ShardedTrainStep:
         CALL: a step the C plan voided (a cross-stream wait gave up, c_step.py: RuntimeWarning; never in a healthy process) moved no
         parameter and no moment but still counts, on every rank alike -- the host learns of it a run later and cannot know how many runs
         it had enqueued in between, and a bias correction that is one step ahead is harmless where replicas that disagree are not."""
+        # a batch with validity masks takes the autograd iteration: neither the C step nor the native step holds the masked terms
+        masked = 'masks' in inp
+        if masked and self.world_size > 1:
+            raise NotImplementedError('a batch with masks under data parallelism: the masked terms are normalised by the valid count of the '
+                                      'GLOBAL batch, which the ranks do not exchange yet')
         self.model._global_count = self._global_count(inp['imgs'], global_count)
         dirty = None
-        if self.cstep is not None and self.model.training and inp['imgs'].shape[0] > 0 and self._fused_adam() and self.cstep.supported():
+        if (self.cstep is not None and self.model.training and inp['imgs'].shape[0] > 0 and self._fused_adam() and self.cstep.supported()
+                and not masked):
             return self._c_iteration(inp)
         # gradients accumulate into the preallocated flat buffer, so nothing carved out of the zero arena outlives the
         # iteration: all zero-initialised scratch of the step comes from one buffer cleared by one launch
         ops.ARENA.enabled = True
         try:
             ops.ARENA.begin_step(self.params.flat.device)
-            native = self.native is not None and self.model.training and inp['imgs'].shape[0] > 0 and self.native.supported()
+            native = (self.native is not None and self.model.training and inp['imgs'].shape[0] > 0 and self.native.supported()
+                      and not masked)
             if native:
                 with torch.no_grad():         # (zeroes the gradient buffer itself: on its side stream, off the critical path)
                     losses = self.native(inp, self.model._global_count, zero_grad=self.params.zero_grad)

@@ -67,7 +67,8 @@ class MultiStepLR:
 class Trainer:
     """cfg: the reference's YAML dict (`model`, `training.{batch_size, optimizer, scheduler, n_epoches, seed}`).
     views: dict of tensors {'imgs' (V,3,H,W), 'R' (V,3,3), 'T' (V,3), 'K' (V,4,4)} resident on the device (the reference's
-    DataLoader yields the same dict batch by batch, trainer.py:118,141)."""
+    DataLoader yields the same dict batch by batch, trainer.py:118,141); every key is batched alike, so the 'masks' (V,1,H,W) of a scene with
+    validity masks (dataset.py) ride along, and each batch then carries 'mask_sum', the sum of its masks as a host number."""
 
     def __init__(self, cfg, model, views, process_group=None, sync_free=True, cache_perceptual_targets=True):
         tr = cfg['training']
@@ -104,13 +105,27 @@ class Trainer:
         # it (lpips_vgg.LPIPSVGG.cache_targets) computes it once for this rank's views, if that fits in a quarter of the free memory, and
         # every batch then carries the local indices of its views.  A third of the criterion's FLOPs; the values do not change.
         self.view_ids = False
+        # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
+        # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
+        self.mask_sums = None
+        if 'masks' in self.local:
+            self.mask_sums = self.local['masks'].to(torch.float64).flatten(1).sum(1).cpu()
         fn = getattr(model, 'perceptual_fn', None)
         if (cache_perceptual_targets and 'perceptual' in getattr(model, 'loss_weights', {}) and hasattr(fn, 'cache_targets') and self.local['imgs'].is_cuda
                 and self.local['imgs'].shape[0] > 0):
             need = fn.target_bytes(*self.local['imgs'].shape[2:], n_views=self.local['imgs'].shape[0])
             if need <= torch.cuda.mem_get_info(self.local['imgs'].device)[0] // 4:
-                fn.cache_targets(self.local['imgs'])
+                fn.cache_targets(self._perceptual_targets())
                 self.view_ids = True
+
+    def _perceptual_targets(self):
+        """What a caching criterion keeps the features of: this rank's images, times their masks where the views have them (the model calls
+        such a criterion on imgs * masks).  The product is made once and kept: the criterion recognises its cache by the tensor."""
+        if 'masks' not in self.local:
+            return self.local['imgs']
+        if getattr(self, '_masked_targets', None) is None:
+            self._masked_targets = self.local['imgs'] * self.local['masks']
+        return self._masked_targets
 
     # trainer.py:137-147
     def run_single_batch_train(self, inp, global_count=None):
@@ -141,8 +156,9 @@ class Trainer:
             # the criterion is shared by whoever holds the model: if its cache is not (or no longer) the one of THESE views -- new weights,
             # another Trainer on other views -- the ids would index foreign features; built again (a forward pass over the views, once)
             fn = self.model.perceptual_fn
-            if not (hasattr(fn, 'cache_matches') and fn.cache_matches(self.local['imgs'])):
-                fn.cache_targets(self.local['imgs'])
+            targets = self._perceptual_targets()
+            if not (hasattr(fn, 'cache_matches') and fn.cache_matches(targets)):
+                fn.cache_targets(targets)
         last = None
         t_start, n_img = time.time(), 0
         # Uneven shards (49 views over 8 ranks: 7,6,...,6; batch 4 -> two steps everywhere, the second of sizes 3,2,...,2): all ranks
@@ -154,6 +170,8 @@ class Trainer:
             batch = {k: v[idx] for k, v in self.local.items()}
             if self.view_ids:
                 batch['view_ids'] = idx
+            if self.mask_sums is not None:
+                batch['mask_sum'] = float(self.mask_sums[ids].sum())
             last, _ = self.run_single_batch_train(batch, self.global_count(b))
             n_img += idx.numel()
             if rec is not None:

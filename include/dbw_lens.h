@@ -36,6 +36,12 @@ int dbw_lens_abi_version(void);
  * any W give the same bytes. */
 int dbw_images_undistort_u8(const uint8_t *src, int N, int H, int W, const float *lens, uint8_t *out, dbw_stream_t stream);
 
+/* The validity map of a rectified frame, added under revision 1 of this header.  out (H,W) uint8 on the DEVICE: 255 where output pixel
+ * (i, j) reads inside the source frame -- 0 <= u <= W - 1 and 0 <= v <= H - 1 for the (u, v) above, NOT clamped --, 0 elsewhere and for
+ * a NaN coordinate.  lens: the HOST array of dbw_images_undistort_u8.  One map serves every frame of a scene: with it as a mask of the
+ * loss the frames need no zoom that crops the border away.  H >= 1, W >= 1. */
+int dbw_lens_valid_u8(int H, int W, const float *lens, uint8_t *out, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

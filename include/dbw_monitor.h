@@ -64,6 +64,40 @@ size_t dbw_monitor_ssim_term_workspace_bytes(int N, int H, int W);
 int dbw_monitor_ssim_term(const float *target, const float *rec, int N, int H, int W, void *workspace, float *grad, double *value,
                           dbw_stream_t stream);
 
+/* The two image terms of the loss under a validity mask (csrc/masked_loss.hip), added under revision 1 of this header.
+ * masks (N,1,H,W) fp32 weights in [0, 1], 1 = the pixel counts; count = 3 * sum(masks) over the batch is a HOST number.
+ *
+ * Bytes of `workspace` that the forward of dbw_monitor_masked_composite needs (one fp64 per workgroup); 0 for sizes it refuses, N = 0. */
+size_t dbw_monitor_masked_composite_workspace_bytes(int N, int H, int W);
+
+/* fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) fp32; scale = w_rgb / count (0 for count = 0), from the host.
+ * rec = fg_rgb * fg_a + (1 - fg_a) * env_rgb, the composite of dbw_composite_mse.
+ * Forward (grad_fg == grad_env == NULL): writes rec (N,3,H,W) and value[0] = scale * sum of masks * (rec - imgs)^2 as one fp64 on the
+ *   device, through per-workgroup fp64 partials in `workspace` added in a fixed order by a second launch: no atomics, two calls give the
+ *   same bits.  upstream and grad_rec must be NULL.
+ * Backward (grad_fg, grad_env (N,4,H,W) given; rec, value NULL; workspace unused): ONE launch.  upstream: one fp32 on the device, the
+ *   gradient g of the loss with respect to value; grad_rec: (N,3,H,W) or NULL, the gradient with respect to rec that other terms (the
+ *   perceptual one) send.  Per pixel and channel d/d rec = (2 scale g) masks (rec - imgs) + grad_rec, taken through the composite:
+ *   grad_fg = [d * fg_a (3 channels), sum_c d_c (fg_c - env_c)], grad_env = [d * (1 - fg_a), 0]  (csrc/loss_math.h: masked_composite_pixel).
+ * Rows whose W is a multiple of 4 and whose pointers are all 16-byte aligned move as 16-byte loads and stores; any other shape element by
+ * element, same results.  value: 8-byte aligned, as workspace is.  N = 0: nothing is launched.  H * W < 2^31. */
+int dbw_monitor_masked_composite(const float *fg, const float *env, const float *imgs, const float *masks, int N, int H, int W, double scale,
+                                 void *workspace, float *rec, double *value, const float *upstream, const float *grad_rec, float *grad_fg,
+                                 float *grad_env, dbw_stream_t stream);
+
+/* Bytes of `workspace` that dbw_monitor_masked_ssim_term needs (one fp64 per workgroup); 0 for sizes it refuses and for N = 0. */
+size_t dbw_monitor_masked_ssim_term_workspace_bytes(int N, int H, int W);
+
+/* dbw_monitor_ssim_term under the mask: with a~ = masks * target and b~ = masks * rec,
+ *   value[0] = sum over n, c, p of masks_p * (1 - SSIM_p(a~, b~)) / count      (0 for count = 0)
+ *   grad, when not NULL: d value / d rec = masks_q * (-1 / count) [blur(masks A)_q + 2 b~_q blur(masks B)_q + a~_q blur(masks C)_q].
+ * The invalid region reads as zero, like the outside of the frame, and a window centred in it is not counted: neither value nor gradient
+ * depends on what target and rec hold where masks = 0 (finite values), and the gradient is exactly 0 there.  The same kernel structure,
+ * filters and order as dbw_monitor_ssim_term; the mask is read from memory, not kept in LDS.  With masks of ones and count = 3 N H W the
+ * gradient is dbw_monitor_ssim_term's bit for bit, the value too.  count >= 0 and finite. */
+int dbw_monitor_masked_ssim_term(const float *target, const float *rec, const float *masks, int N, int H, int W, double count, void *workspace,
+                                 float *grad, double *value, dbw_stream_t stream);
+
 /* table: n + 2 doubles on the device; vals: HOST array of n <= DBW_METER_MAX_VALUES DEVICE pointers, each to one fp32.  One kernel:
  *   table[i] += (double)*vals[i] * weight  (i < n),   table[n] += weight,
  *   table[n + 1] = step if it is negative and any *vals[i] is not finite (the first such step stays). */
