@@ -120,6 +120,21 @@ DBW_HD f3 vertex_bwd(const float *verts, int vi, const Cam &c, float eps, f3 g) 
     return o;
 }
 
+// d(ndc vertex)/d(view-space vertex): what vertex_bwd holds before it rotates back to the world -- the part of the gradient that belongs
+// to the camera of the view (pose_math.h: g_T += gview, g_R[r][c] += X_r * gview_c).  Same operations in the same order as vertex_bwd.
+DBW_HD f3 vertex_bwd_view(const float *verts, int vi, const Cam &c, float eps, f3 g) {
+    const Proj pr = project(verts + (long long)vi * 3, c, eps);
+    const float gpx = g.x / pr.denom, gpy = g.y / pr.denom;
+    const float gden = -(g.x * pr.px + g.y * pr.py) / (pr.denom * pr.denom);
+    const float ab = pr.pw < 0.f ? -pr.pw : pr.pw;
+    const float gpw = ab >= eps ? gden : 0.f;
+    f3 o;
+    o.x = gpx * c.K[0] + gpy * c.K[4] + gpw * c.K[12];
+    o.y = gpx * c.K[1] + gpy * c.K[5] + gpw * c.K[13];
+    o.z = gpx * c.K[2] + gpy * c.K[6] + gpw * c.K[14] + g.z;
+    return o;
+}
+
 // grads of q = clip_point(pa, pb) (w detached) pushed to ga, gb
 DBW_HD void clip_point_bwd(f3 pa, f3 pb, float c, int persp, float w, f3 gq, f3 &ga, f3 &gb) {
     const float omw = 1.f - w;

@@ -189,11 +189,19 @@ INGEST_OTHER_SIGNATURES = {
 RESAMPLE_AUTO, RESAMPLE_GENERAL, RESAMPLE_FUSED = 0, 1, 2     # DBW_RESAMPLE_* of include/dbw_ingest.h
 INGEST_ABI_VERSION = header_define('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION')
 
-# the lens rectification: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by tests/test_abi_families.py).
+# the camera of a custom capture, its lens and its pose: name -> argtypes, exactly the int-returning prototypes of include/dbw_lens.h (checked by
+# tests/test_abi_families.py); the one size_t-returning entry point next to them.
 LENS_SIGNATURES = {
     'dbw_images_undistort_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     # the validity map of a rectified frame, added under revision 1 of the header
     'dbw_lens_valid_u8': [c_i, c_i, c_p, c_p, c_p],
+    # camera pose refinement (csrc/pose_grad.hip), added under revision 1 of the header
+    'dbw_lens_pose_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_i, c_p],
+    'dbw_lens_pose_apply': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
+    'dbw_lens_pose_chain': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+}
+LENS_OTHER_SIGNATURES = {
+    'dbw_lens_pose_grad_workspace_bytes': (c_sz, [c_i, c_i]),
 }
 LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h
 LENS_ABI_VERSION = header_define('dbw_lens.h', 'DBW_LENS_ABI_VERSION')
@@ -239,7 +247,8 @@ FAMILIES = {
     'export': Family('dbw_export.h', 'DBW_EXPORT_ABI_VERSION', 'dbw_export_abi_version', EXPORT_SIGNATURES, {}, 'frame export entry point'),
     'ingest': Family('dbw_ingest.h', 'DBW_INGEST_ABI_VERSION', 'dbw_ingest_abi_version', INGEST_SIGNATURES, INGEST_OTHER_SIGNATURES,
                      'image ingest entry point'),
-    'lens': Family('dbw_lens.h', 'DBW_LENS_ABI_VERSION', 'dbw_lens_abi_version', LENS_SIGNATURES, {}, 'lens rectification entry point'),
+    'lens': Family('dbw_lens.h', 'DBW_LENS_ABI_VERSION', 'dbw_lens_abi_version', LENS_SIGNATURES, LENS_OTHER_SIGNATURES,
+                   'lens rectification and pose refinement entry points'),
     'monitor': Family('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION', 'dbw_monitor_abi_version', MONITOR_SIGNATURES, MONITOR_OTHER_SIGNATURES,
                       'run monitor entry points'),
     'icp': Family('dbw_icp.h', 'DBW_ICP_ABI_VERSION', 'dbw_icp_abi_version', ICP_SIGNATURES, ICP_OTHER_SIGNATURES, 'gradient ICP entry points'),

@@ -232,6 +232,27 @@ def project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z
     return g
 
 
+def project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z_clip=0.001, perspective_correct=True, out=None):
+    """dbw_lens_pose_grad: the gradient of the clipped faces with respect to each view's camera, -> (g_R (B,3,3), g_T (B,3)).  The same
+    per-slot work as project_clip_bwd, summed over the slots of a view instead of over the views (csrc/pose_grad.hip; fixed summation
+    order, no atomics).  out=(g_R, g_T): the sums are ADDED to these (the second pass over the same views) and the pair is returned."""
+    _lib.family('lens')
+    B, V, F_ = R.shape[0], verts.shape[0], faces_i32.shape[0]
+    g_R, g_T = out if out is not None else (torch.empty(B, 3, 3, dtype=torch.float32, device=verts.device),
+                                            torch.empty(B, 3, dtype=torch.float32, device=verts.device))
+    ws_bytes = int(_lib.load().dbw_lens_pose_grad_workspace_bytes(B, F_))
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=verts.device)
+    _lib.call('dbw_lens_pose_grad', _ptr(verts), _ptr(faces_i32), _ptr(R), _ptr(T), _ptr(Kmat), B, V, F_, float(eps), float(z_clip or 0.0),
+              int(perspective_correct), _ptr(cl['num_faces']), _ptr(cl['c2o']), _ptr(cl['clip_code']), _ptr(cl['clip_w']), _ptr(g_face_verts),
+              _ptr(ws), ws_bytes, _ptr(g_R), _ptr(g_T), int(out is not None), _stream(verts))
+    return g_R, g_T
+
+
+def _cam_grads(ctx, iR, g_R, g_T):
+    """The entries of a backward's result for R and T: what was asked for of (g_R, g_T)."""
+    return (g_R if ctx.needs_input_grad[iR] else None), (g_T if ctx.needs_input_grad[iR + 1] else None)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # shade + blend on given fragments
 # ---------------------------------------------------------------------------------------------------------------------
@@ -384,14 +405,19 @@ class _RenderScene(torch.autograd.Function):
         verts, maps, fa, faces_i32, R, T, Kmat, face_uvs, face_map, map_desc, p2f, bary, dists = ctx.saved_tensors
         cfg, cl, bg = ctx.cfg, ctx.cl, ctx.bg
         fa = fa if ctx.has_alpha else None
-        need_geom = ctx.needs_input_grad[0]
+        need_verts = ctx.needs_input_grad[0]
+        need_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]        # camera pose refinement: R, T of the views
+        need_geom = need_verts or need_cam
         want_dists = need_geom and cfg.sigma != 0
         want_bary = need_geom and not cfg.detach_bary
+        g_R = g_T = None
         if FUSED_BACKWARD and (ctx.tiled or (need_geom and (want_dists or want_bary))):
             g_maps, g_alpha, g_fvc = _fused_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, cfg, bg, ctx.tiled, g_img.contiguous(),
                                                 R.shape[0], None)
-            g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_geom else None
-            return g_verts, g_maps, g_alpha, None, None, None, None, None, None, None, None, None
+            g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_verts else None
+            if need_cam:
+                g_R, g_T = _cam_grads(ctx, 4, *project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp))
+            return g_verts, g_maps, g_alpha, None, g_R, g_T, None, None, None, None, None, None
         if ctx.tiled:
             raise RuntimeError('tiled fragments can only be consumed by the fused backward')
         g_maps, g_alpha, g_dists, g_bary = shade_blend_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, cfg.F,
@@ -403,10 +429,14 @@ class _RenderScene(torch.autograd.Function):
             B = R.shape[0]
             _lib.call('dbw_rasterize_bwd', _ptr(fvc), _ptr(p2f), 0, _ptr(g_bary), _ptr(g_dists), B, fvc.shape[0], cfg.H, cfg.W,
                       cfg.K, int(cfg.persp), 1, _ptr(g_fvc), _stream(fvc))
-            g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp)
+            g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_verts else None
+            if need_cam:
+                g_R, g_T = _cam_grads(ctx, 4, *project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp))
         elif need_geom:
-            g_verts = torch.zeros_like(verts)
-        return g_verts, g_maps, g_alpha, None, None, None, None, None, None, None, None, None
+            g_verts = torch.zeros_like(verts) if need_verts else None
+            if need_cam:
+                g_R, g_T = _cam_grads(ctx, 4, torch.zeros_like(R), torch.zeros_like(T))
+        return g_verts, g_maps, g_alpha, None, g_R, g_T, None, None, None, None, None, None
 
 
 _UNIFORM_LAYOUTS = {}
@@ -586,7 +616,13 @@ class _DecoupledRenderMSE(torch.autograd.Function):
         gv_f = project_clip_bwd(vf, faces_f, R, T, Kmat, cl_f, g_fvc_f, cfg_f.eps, cfg_f.z_clip, cfg_f.persp) if ctx.needs_input_grad[2] else None
         gm_e, _, g_fvc_e = _fused_bwd(p2f_e, bary_e, dists_e, cl_e, uv_e, fmap_e, desc_e, me, None, cfg_e, bg_e, ctx.lay_e, g_env, B, gs)
         gv_e = project_clip_bwd(ve, faces_e, R, T, Kmat, cl_e, g_fvc_e, cfg_e.eps, cfg_e.z_clip, cfg_e.persp) if ctx.needs_input_grad[0] else None
-        return (gv_e, gm_e, gv_f, gm_f, ga) + (None,) * 11
+        g_R = g_T = None
+        if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
+            # camera pose refinement: env then fg into one pair of buffers, so that the order of the sum is fixed
+            cam = project_clip_bwd_cam(ve, faces_e, R, T, Kmat, cl_e, g_fvc_e, cfg_e.eps, cfg_e.z_clip, cfg_e.persp)
+            cam = project_clip_bwd_cam(vf, faces_f, R, T, Kmat, cl_f, g_fvc_f, cfg_f.eps, cfg_f.z_clip, cfg_f.persp, out=cam)
+            g_R, g_T = _cam_grads(ctx, 7, *cam)
+        return (gv_e, gm_e, gv_f, gm_f, ga, None, None, g_R, g_T) + (None,) * 7
 
 
 def render_decoupled_mse(env, fg, alpha, imgs, scale, R, T, Kmat, cfg_e, cfg_f, bg_e, bg_f):
@@ -1035,6 +1071,59 @@ def lens_valid_u8(H, W, intr, dist, zoom=1.0, device='cuda'):
         raise RuntimeError('lens_valid_u8 runs on the GPU (there is no CPU fallback)')
     _lib.call('dbw_lens_valid_u8', H, W, lens.data_ptr(), _ptr(out), _stream(out))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# camera pose refinement (include/dbw_lens.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def _pose_ids(ids, B, V, ids_host=None):
+    """The batch's rows of delta as a contiguous int32 device tensor; a row named twice is refused (the chain kernel writes rows without
+    atomics), and so is one outside the table.  Checked on ids_host -- the same ids where the caller holds them on the host too (the
+    Trainer draws them there) -- or on one host copy of the B integers, which waits for the device."""
+    if ids.numel() != B:
+        raise ValueError(f'ids: one per view of the batch ({B}), got {ids.numel()}')
+    if ids_host is not None and len(ids_host) != B:
+        raise ValueError(f'ids_host: one per view of the batch ({B}), got {len(ids_host)}')
+    host = [int(i) for i in (ids if ids_host is None else torch.as_tensor(ids_host)).reshape(-1).tolist()]
+    if len(set(host)) != len(host):
+        raise ValueError(f'pose_apply: the view ids of a batch must be distinct, got {host}')
+    if host and (min(host) < 0 or max(host) >= V):
+        raise ValueError(f'pose_apply: view ids outside [0, {V}): {host}')
+    return ids.reshape(-1).to(torch.int32).contiguous()
+
+
+class _PoseApply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, R0, T0, delta, ids):
+        B, V = R0.shape[0], delta.shape[0]
+        R1, T1 = torch.empty_like(R0), torch.empty_like(T0)
+        _lib.call('dbw_lens_pose_apply', _ptr(R0), _ptr(T0), _ptr(delta), _ptr(ids), B, V, _ptr(R1), _ptr(T1), _stream(R0))
+        ctx.save_for_backward(R0, T0, delta, ids)
+        return R1, T1
+
+    @staticmethod
+    def backward(ctx, g_R, g_T):
+        R0, T0, delta, ids = ctx.saved_tensors
+        B, V = R0.shape[0], delta.shape[0]
+        g_R = torch.zeros_like(R0) if g_R is None else g_R.contiguous()
+        g_T = torch.zeros_like(T0) if g_T is None else g_T.contiguous()
+        g_delta = torch.zeros_like(delta)
+        _lib.call('dbw_lens_pose_chain', _ptr(R0), _ptr(T0), _ptr(delta), _ptr(ids), B, V, _ptr(g_R), _ptr(g_T), _ptr(g_delta), _stream(R0))
+        return None, None, g_delta, None
+
+
+def pose_apply(R0, T0, delta, ids, ids_host=None):
+    """dbw_lens_pose_apply / dbw_lens_pose_chain as one autograd function: R0 (B,3,3), T0 (B,3) of a batch, delta (V,6) = one (w, tau) per view
+    of the scene, ids (B) = the batch's rows of delta, distinct -> (R', T') with R' = R0.E(w), T' = T0.E(w) + tau (csrc/pose_math.h).  Only
+    delta receives a gradient: R0, T0 are data.  ids_host: the same ids on the host, where the caller has them (no wait for the device).
+    The caller GUARANTEES that ids_host and ids hold the same integers: they are not compared (that would be the wait), and the
+    distinctness that lets the chain kernel write rows without atomics is checked on ids_host alone."""
+    if R0.dim() != 3 or tuple(R0.shape[1:]) != (3, 3) or tuple(T0.shape) != (R0.shape[0], 3) or delta.dim() != 2 or delta.shape[1] != 6:
+        raise ValueError(f'pose_apply: R0 (B,3,3), T0 (B,3), delta (V,6); got {tuple(R0.shape)}, {tuple(T0.shape)}, {tuple(delta.shape)}')
+    ids = _pose_ids(ids, R0.shape[0], delta.shape[0], ids_host)
+    _lib.family('lens')
+    return _PoseApply.apply(_chk(R0.detach(), torch.float32, 'R0'), _chk(T0.detach(), torch.float32, 'T0'),
+                            _chk(delta, torch.float32, 'delta'), ids.to(R0.device))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

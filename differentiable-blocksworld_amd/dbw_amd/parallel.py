@@ -131,6 +131,13 @@ class ShardedTrainStep:
         if masked and self.world_size > 1:
             raise NotImplementedError('a batch with masks under data parallelism: the masked terms are normalised by the valid count of the '
                                       'GLOBAL batch, which the ranks do not exchange yet')
+        # ... and so does a batch whose poses are being refined (pose.PoseRefiner.apply: R, T require a gradient): the camera gradients
+        # come out of the autograd nodes only (ops._RenderScene, ops._DecoupledRenderMSE)
+        posed = bool(getattr(inp.get('R'), 'requires_grad', False) or getattr(inp.get('T'), 'requires_grad', False))
+        if posed and self.world_size > 1:
+            raise NotImplementedError('camera pose refinement under data parallelism: the pose gradients are per view and the ranks do not '
+                                      'exchange them')
+        masked = masked or posed
         self.model._global_count = self._global_count(inp['imgs'], global_count)
         dirty = None
         if (self.cstep is not None and self.model.training and inp['imgs'].shape[0] > 0 and self._fused_adam() and self.cstep.supported()

@@ -1,5 +1,6 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
+                          [--pose-refine LR]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -17,7 +18,10 @@ the cloud and the cameras (worldfit.estimate_world_frame), printed and written t
 The perceptual term needs the weights of a VGG16 and of the LPIPS heads, which do not ship with the package: a config with
 perceptual_weight > 0 is refused unless both files are given, or --no-perceptual sets the weight to 0 (and says so).  With
 model.loss.perceptual_name: ssim -- or --perceptual ssim, which overrides the config's key -- the term is the built-in SSIM term
-(metrics.SSIMTerm) and needs no file; giving the LPIPS weight files beside it is refused as a contradiction."""
+(metrics.SSIMTerm) and needs no file; giving the LPIPS weight files beside it is refused as a contradiction.
+
+training.pose_refine: {lr, start_epoch, rot, trans} -- or --pose-refine LR -- refines the camera poses of the training views beside the model
+(pose.py); the refined poses are written to <run_dir>/transforms_refined.json (custom captures) or poses_refined.npz at the end."""
 import argparse
 import os
 import sys
@@ -40,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument('--no-perceptual', action='store_true', help='train without the perceptual term')
     ap.add_argument('--resume', nargs='?', const=True, default=None, metavar='TAG', help="continue the run TAG of this dataset (default: --tag's own run)")
     ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
+    ap.add_argument('--pose-refine', type=float, default=None, metavar='LR',
+                    help='refine the camera poses of the training views beside the model, with this learning rate (training.pose_refine.lr)')
     ap.add_argument('--device', default='cuda:0')
     return ap.parse_args(argv)
 
@@ -66,6 +72,9 @@ def prepare_config(args):
                              '--perceptual ssim for the built-in SSIM term')
     if args.epochs is not None:
         cfg.setdefault('training', {})['n_epoches'] = args.epochs
+    if getattr(args, 'pose_refine', None) is not None:
+        entry = cfg.setdefault('training', {}).get('pose_refine')
+        cfg['training']['pose_refine'] = dict(entry if isinstance(entry, dict) else {}, lr=args.pose_refine)
     return cfg
 
 
@@ -139,6 +148,7 @@ def main(argv=None):
         net.load_weights(torch.load(args.lpips_vgg, map_location='cpu'), torch.load(args.lpips_lin, map_location='cpu'))
         model.set_perceptual(net.to(args.device))
     trainer = Trainer(cfg, model, train.views(args.device))
+    trainer.scene = train                       # (pose refinement: the refined poses go back into the capture's own files)
     print(f'Trainer init: config_file={args.config}, run_dir={run_dir}, n_epoches={trainer.n_epoches}')
     if args.no_record:
         if 'resume' in start:                   # (a recorded run's model.pkl may stop inside an epoch: the position and the schedule are the recorder's to read)

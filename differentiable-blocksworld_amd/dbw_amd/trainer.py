@@ -64,6 +64,24 @@ class MultiStepLR:
                 self.step()
 
 
+class _RefinedLoader:
+    """A loader over the training views in their order, with R, T replaced by the refined poses (Trainer.evaluate)."""
+
+    def __init__(self, loader, R, T):
+        self.loader, self.R, self.T = loader, R, T
+        self.dataset, self.batch_size = loader.dataset, loader.batch_size
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        a = 0
+        for inp, labels in self.loader:
+            n = len(inp['R'])
+            yield dict(inp, R=self.R[a:a + n].to(inp['R'].device), T=self.T[a:a + n].to(inp['T'].device)), labels
+            a += n
+
+
 class Trainer:
     """cfg: the reference's YAML dict (`model`, `training.{batch_size, optimizer, scheduler, n_epoches, seed}`).
     views: dict of tensors {'imgs' (V,3,H,W), 'R' (V,3,3), 'T' (V,3), 'K' (V,4,4)} resident on the device (the reference's
@@ -105,6 +123,19 @@ class Trainer:
         # it (lpips_vgg.LPIPSVGG.cache_targets) computes it once for this rank's views, if that fits in a quarter of the free memory, and
         # every batch then carries the local indices of its views.  A third of the criterion's FLOPs; the values do not change.
         self.view_ids = False
+        # Camera pose refinement (training.pose_refine: {lr, start_epoch, rot, trans}; pose.py): absent -> nothing is built and
+        # no batch changes.  Present -> batches carry view_ids, their R, T go through the refiner from start_epoch on, and its Adam step
+        # follows the model's.  `scene`: the training scene, for the files evaluate() writes (train.main sets it).
+        self.pose, self.pose_cfg, self.scene = None, None, None
+        from .pose import PoseRefiner, parse_config
+        self.pose_cfg = parse_config(tr.get('pose_refine'))
+        if self.pose_cfg is not None:
+            if ws > 1:
+                raise NotImplementedError('training.pose_refine under data parallelism: the pose gradients are per view and the ranks do not '
+                                          'exchange them')
+            self.pose = PoseRefiner(self.local['imgs'].shape[0], self.local['imgs'].device, lr=self.pose_cfg['lr'],
+                                    betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))), rot=self.pose_cfg['rot'],
+                                    trans=self.pose_cfg['trans'])
         # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
         # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
         self.mask_sums = None
@@ -117,6 +148,8 @@ class Trainer:
             if need <= torch.cuda.mem_get_info(self.local['imgs'].device)[0] // 4:
                 fn.cache_targets(self._perceptual_targets())
                 self.view_ids = True
+        self._cached_targets = self.view_ids        # (view_ids may also be on for the pose refiner alone: no cache to keep then)
+        self.view_ids = self.view_ids or self.pose is not None
 
     def _perceptual_targets(self):
         """What a caching criterion keeps the features of: this rank's images, times their masks where the views have them (the model calls
@@ -152,7 +185,7 @@ class Trainer:
         rec = self.recorder
         if rec is not None:
             rec.begin_epoch(order)
-        if self.view_ids:
+        if self._cached_targets:
             # the criterion is shared by whoever holds the model: if its cache is not (or no longer) the one of THESE views -- new weights,
             # another Trainer on other views -- the ids would index foreign features; built again (a forward pass over the views, once)
             fn = self.model.perceptual_fn
@@ -170,9 +203,16 @@ class Trainer:
             batch = {k: v[idx] for k, v in self.local.items()}
             if self.view_ids:
                 batch['view_ids'] = idx
+            if self.pose is not None:
+                batch['view_ids_host'] = ids                      # (the refiner checks the ids without waiting for the device)
             if self.mask_sums is not None:
                 batch['mask_sum'] = float(self.mask_sums[ids].sum())
+            refine = self.pose is not None and self.epoch >= self.pose_cfg['start_epoch'] and idx.numel() > 0
+            if refine:
+                batch = self.pose.apply(batch)
             last, _ = self.run_single_batch_train(batch, self.global_count(b))
+            if refine:
+                self.pose.step()
             n_img += idx.numel()
             if rec is not None:
                 rec.after_step(self.epoch, b + 1, last, ids)
@@ -226,6 +266,12 @@ class Trainer:
         os.makedirs(os.path.join(run_dir, 'quali_eval'), exist_ok=True)
         device = self.views['imgs'].device
         self.model.eval()
+        if self.pose is not None:
+            from .pose import write_refined
+            if self.scene is not None:
+                write_refined(self.scene, self.pose, run_dir, self.local['R'], self.local['T'])
+            if getattr(loader, 'dataset', None) is not None and loader.dataset is self.scene:
+                loader = _RefinedLoader(loader, *self.pose.refined(self.local['R'], self.local['T']))      # the training views: at their refined poses
         self.model.qualitative_eval(loader, device, path=os.path.join(run_dir, 'quali_eval'), **({'parse': True} if parse else {}))
         scores = self.model.quantitative_eval(loader, device, hard_inference=True)
         with open(os.path.join(run_dir, 'final_scores.tsv'), mode='w') as f:
@@ -278,7 +324,7 @@ class Trainer:
                 'model_state': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
                 'optimizer_state': {'exp_avg': self.step_fn.exp_avg.clone(), 'exp_avg_sq': self.step_fn.exp_avg_sq.clone(),
                                     'n_steps': self.step_fn.n_steps},
-                'scheduler_state': self.scheduler.state_dict()}
+                'scheduler_state': self.scheduler.state_dict(), **({} if self.pose is None else {'pose_refine': self.pose.state_dict()})}
 
     def load_state_dict(self, ckpt):
         self.model.load_state_dict(ckpt['model_state'])
@@ -293,3 +339,5 @@ class Trainer:
         self.step_fn.lrs = tuple(self.scheduler.get_last_lr())
         self.epoch = ckpt['epoch'] + 1                         # trainer.py:94-97: resume with the epoch after the saved one
         self.model.set_cur_epoch(ckpt['epoch'])
+        if self.pose is not None and 'pose_refine' in ckpt:
+            self.pose.load_state_dict(ckpt['pose_refine'])

@@ -1,8 +1,10 @@
 /*
- * dbw_lens.h -- C ABI of the lens rectification of libdbw_hip.so: raw 8-bit frames of a custom capture, resident on the device, resampled
- * from the distorted image of an OpenCV radial-tangential lens (the k1..k4, p1, p2 of a Nerfstudio transforms.json) into the pinhole frame
- * the renderer assumes, before the image ingest (dbw_ingest.h) resizes them.
- * Python side: dbw_amd/ops.py (undistort_u8), bound through _lib.LENS_SIGNATURES.  The arithmetic is csrc/lens_math.h.
+ * dbw_lens.h -- C ABI of the camera of a custom capture in libdbw_hip.so: its lens and its pose.
+ * Lens: raw 8-bit frames, resident on the device, resampled from the distorted image of an OpenCV radial-tangential lens (the k1..k4, p1,
+ * p2 of a Nerfstudio transforms.json) into the pinhole frame the renderer assumes, before the image ingest (dbw_ingest.h) resizes them.
+ * Pose: the gradient of a render with respect to each view's R and T, and the per-view 6-vector that refines a pose during training.
+ * Python side: dbw_amd/ops.py (undistort_u8, lens_valid_u8, project_clip_bwd_cam, pose_apply), bound through _lib.LENS_SIGNATURES and
+ * _lib.LENS_OTHER_SIGNATURES.  The arithmetic is csrc/lens_math.h and csrc/pose_math.h.
  *
  * Conventions are those of dbw_hip.h: DEVICE pointers owned by the caller, contiguous, unless said otherwise; return 0 or a negative
  * DBW_ERR_*, the text in dbw_last_error(); arguments are validated before any launch; kernels are enqueued on `stream`, no host
@@ -41,6 +43,33 @@ int dbw_images_undistort_u8(const uint8_t *src, int N, int H, int W, const float
  * a NaN coordinate.  lens: the HOST array of dbw_images_undistort_u8.  One map serves every frame of a scene: with it as a mask of the
  * loss the frames need no zoom that crops the border away.  H >= 1, W >= 1. */
 int dbw_lens_valid_u8(int H, int W, const float *lens, uint8_t *out, dbw_stream_t stream);
+
+/* Camera pose refinement, added under revision 1 of this header.  Conventions of the camera transform (dbw_project_clip_fwd): row vectors,
+ * v = X.R + T, R (B,3,3) row-major, T (B,3).
+ *
+ * dbw_lens_pose_grad: the gradient of the clipped faces of B views with respect to each view's camera.  The arguments up to
+ * grad_face_verts_c (B,2F,3,3) are those of dbw_project_clip_bwd, which sums the same per-slot gradient over the views into the vertices;
+ * this call sums it over the slots j < num_faces[b] of view b into grad_R (B,3,3) and grad_T (B,3).  What grad_face_verts_c holds in the
+ * other slots reaches nothing.  accumulate != 0: the sums are added to what grad_R, grad_T hold (a second pass over the same views), else
+ * they replace it.  workspace: dbw_lens_pose_grad_workspace_bytes(B, F) bytes on the DEVICE, 4-byte aligned, contents irrelevant.  The
+ * sums have a fixed order (no atomics): two calls give the same bits.  B >= 0 (B == 0: nothing is done), V > 0, F > 0, B <= 65535. */
+size_t dbw_lens_pose_grad_workspace_bytes(int B, int F);
+int dbw_lens_pose_grad(const float *verts_world, const int32_t *faces, const float *R, const float *T, const float *Kmat, int B, int V, int F,
+                       float eps, float z_clip, int perspective_correct, const int32_t *num_faces, const int32_t *c2o,
+                       const int32_t *clip_code, const float *clip_w, const float *grad_face_verts_c, void *workspace,
+                       size_t workspace_bytes, float *grad_R, float *grad_T, int accumulate, dbw_stream_t stream);
+
+/* The refined poses of a batch.  delta (V,6): one row (w, tau) per view of the scene; ids (B) int32: the row of each view of the batch.
+ * R_out[b] = R0[b].E(w), T_out[b] = T0[b].E(w) + tau with E = exp([w]x) (csrc/pose_math.h has the sign convention and the series near
+ * w = 0: a zero row gives R0[b], T0[b] bit for bit).  An id outside [0, V) leaves the pose as it is.  B >= 0, V > 0. */
+int dbw_lens_pose_apply(const float *R0, const float *T0, const float *delta, const int32_t *ids, int B, int V, float *R_out, float *T_out,
+                        dbw_stream_t stream);
+
+/* Backward of dbw_lens_pose_apply with respect to delta: grad_R (B,3,3), grad_T (B,3) of the refined poses -> row ids[b] of grad_delta
+ * (V,6), WRITTEN, not added: the caller zeroes the rows beforehand and passes ids that are distinct within the batch.  R0, T0 are data
+ * and receive no gradient. */
+int dbw_lens_pose_chain(const float *R0, const float *T0, const float *delta, const int32_t *ids, int B, int V, const float *grad_R,
+                        const float *grad_T, float *grad_delta, dbw_stream_t stream);
 
 #ifdef __cplusplus
 }

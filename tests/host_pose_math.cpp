@@ -1,0 +1,163 @@
+// Checker-side build of the camera pose refinement arithmetic (differentiable-blocksworld_amd/csrc/pose_math.h, the header pose_grad.hip
+// compiles) for the host.  tests/test_host_pose_math.py holds the camera gradient to autograd of the oracle and to the existing vertex
+// backward, and the Rodrigues forward / backward to a float64 restatement, without a GPU; tests/test_gpu_pose.py holds the kernels to this
+// build.  With -DPOSE_MATH_MAIN the file is a program of its own (its main walks the same cases on exactly sized heap buffers) for
+// -fsanitize=address,undefined.  Test infrastructure only.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../differentiable-blocksworld_amd/csrc/pose_math.h"
+
+using namespace dbw;
+
+extern "C" {
+
+// dbw_lens_pose_grad for B views, slot by slot in fp32: gR (B,3,3), gT (B,3) written.  abs_terms (B,12) or null: per component the sum of
+// the |terms| of the sum (a term = what one vertex of one slot adds), for the bound of an fp32 sum in the tests; with it n_terms (B): the
+// number of terms of view b's sums (vertices whose gradient is not all zero: the others add nothing).
+int host_pose_grad(const float *verts, const int *faces, const float *R, const float *T, const float *Kmat, int B, int F, float eps, float zc,
+                   int persp, const int *num_faces, const int *c2o, const int *code, const float *cw, const float *g, float *gR, float *gT,
+                   double *abs_terms, int *n_terms) {
+    for (int b = 0; b < B; ++b) {
+        Cam cam;
+        load_cam(R, T, Kmat, b, cam);
+        float acc[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < num_faces[b]; ++j) {
+            const long long o = (long long)b * 2 * F + j;
+            float g9[9];
+            bool any = false;
+            for (int i = 0; i < 9; ++i) { g9[i] = g[o * 9 + i]; any |= (g9[i] != 0.f); }
+            if (!any) continue;
+            const int f = c2o[o];
+            float one[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            slot_cam_grad(verts, faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2], cam, eps, zc, persp, code[o], cw[o * 2], cw[o * 2 + 1], g9, acc);
+            if (abs_terms) {
+                // the terms of this slot, vertex by vertex: the same calls with one vertex's gradient at a time
+                const f3 ga{g9[0], g9[1], g9[2]}, gb{g9[3], g9[4], g9[5]}, gc{g9[6], g9[7], g9[8]};
+                f3 q[3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+                if (code[o] >= 0)
+                    for (int i = 0; i < 3; ++i) q[i] = project(verts + (long long)faces[f * 3 + i] * 3, cam, eps).ndc;
+                f3 gv[3];
+                clip_slot_bwd(code[o], q[0], q[1], q[2], zc, persp, cw[o * 2], cw[o * 2 + 1], ga, gb, gc, gv[0], gv[1], gv[2]);
+                for (int i = 0; i < 3; ++i) {
+                    if (n_terms && (gv[i].x != 0.f || gv[i].y != 0.f || gv[i].z != 0.f)) ++n_terms[b];
+                    for (int c = 0; c < 12; ++c) one[c] = 0.f;
+                    vertex_cam_grad(verts, faces[f * 3 + i], cam, eps, gv[i], one);
+                    for (int c = 0; c < 12; ++c) abs_terms[b * 12 + c] += std::fabs((double)one[c]);
+                }
+            }
+        }
+        for (int c = 0; c < 9; ++c) gR[b * 9 + c] = acc[c];
+        for (int c = 0; c < 3; ++c) gT[b * 3 + c] = acc[9 + c];
+    }
+    return 0;
+}
+
+int host_rodrigues(const float *w, float *E) { rodrigues(w, E); return 0; }
+int host_rodrigues_bwd(const float *w, const float *gE, float *gw) { rodrigues_bwd(w, gE, gw); return 0; }
+
+int host_pose_apply(const float *R0, const float *T0, const float *delta, const int *ids, int B, int V, float *R1, float *T1) {
+    for (int b = 0; b < B; ++b) {
+        const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const int v = ids[b];
+        pose_apply(R0 + b * 9, T0 + b * 3, v >= 0 && v < V ? delta + (long long)v * 6 : zero, R1 + b * 9, T1 + b * 3);
+    }
+    return 0;
+}
+
+int host_pose_chain(const float *R0, const float *T0, const float *delta, const int *ids, int B, int V, const float *gR, const float *gT, float *gdelta) {
+    for (int b = 0; b < B; ++b) {
+        const int v = ids[b];
+        if (v < 0 || v >= V) continue;
+        pose_chain(R0 + b * 9, T0 + b * 3, delta + (long long)v * 6, gR + b * 9, gT + b * 3, gdelta + (long long)v * 6);
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+#ifdef POSE_MATH_MAIN
+// The cases of the tests on exactly sized heap buffers: a read or write outside them is the sanitizer's to report.
+int main() {
+    uint32_t seed = 2024u;
+    auto rnd = [&seed]() { seed = seed * 1664525u + 1013904223u; return (float)(seed >> 8) / 16777216.f - 0.5f; };
+    // Rodrigues at the angles of the tests, forward, backward, apply and chain
+    const double angles[] = {0.0, 1e-8, 1e-4, 1e-2, 1.0, 3.14159265358979 - 1e-3};
+    for (double th : angles) {
+        const int V = 5, B = 3;
+        std::vector<float> delta((size_t)V * 6), R0((size_t)B * 9), T0((size_t)B * 3), R1((size_t)B * 9), T1((size_t)B * 3), gR((size_t)B * 9), gT((size_t)B * 3),
+            gd((size_t)V * 6, 0.f), E(9), gw(3);
+        std::vector<int> ids = {4, 0, 2};
+        for (int v = 0; v < V; ++v) {
+            float a[3] = {rnd(), rnd(), rnd()};
+            const float n = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) + 1e-20f;
+            for (int i = 0; i < 3; ++i) { delta[v * 6 + i] = (float)(th * a[i] / n); delta[v * 6 + 3 + i] = 0.1f * rnd(); }
+        }
+        for (auto &x : R0) x = rnd();
+        for (auto &x : T0) x = rnd();
+        for (auto &x : gR) x = rnd();
+        for (auto &x : gT) x = rnd();
+        host_rodrigues(delta.data(), E.data());
+        host_rodrigues_bwd(delta.data(), gR.data(), gw.data());
+        host_pose_apply(R0.data(), T0.data(), delta.data(), ids.data(), B, V, R1.data(), T1.data());
+        host_pose_chain(R0.data(), T0.data(), delta.data(), ids.data(), B, V, gR.data(), gT.data(), gd.data());
+        double s = 0.0;
+        for (float x : R1) s += x;
+        for (float x : gd) s += x;
+        if (!(s - s == 0.0)) { std::printf("angle %g: not finite\n", th); return 1; }
+        if (th == 0.0 && !(E[0] == 1.f && E[4] == 1.f && E[8] == 1.f && E[1] == 0.f && E[2] == 0.f && E[3] == 0.f && E[5] == 0.f && E[6] == 0.f && E[7] == 0.f)) {
+            std::printf("E(0) is not the identity\n");
+            return 1;
+        }
+        std::printf("angle %g: ok\n", th);
+    }
+    // camera gradient: a fan of triangles across the near plane of two cameras, so that untouched, dropped and clipped faces all occur
+    for (int persp = 0; persp < 2; ++persp) {
+        const int V = 40, F = 60, B = 2;
+        const float zc = 0.25f, eps = 1e-8f;
+        std::vector<float> verts((size_t)V * 3), R = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0.8f, 0, -0.6f, 0, 1, 0, 0.6f, 0, 0.8f}, T = {0, 0, 0.3f, 0.1f, -0.1f, 0.2f},
+                           K = {2.1f, 0, 0.05f, 0, 0, 2.1f, -0.03f, 0, 0, 0, 0, 1, 0, 0, 1, 0};
+        std::vector<int> faces((size_t)F * 3);
+        for (auto &x : verts) x = 2.f * rnd();
+        for (int f = 0; f < F; ++f) { faces[f * 3] = f % V; faces[f * 3 + 1] = (f * 7 + 1) % V; faces[f * 3 + 2] = (f * 11 + 2) % V; }
+        std::vector<int> num(B), c2o((size_t)B * 2 * F), code((size_t)B * 2 * F);
+        std::vector<float> cw((size_t)B * 2 * F * 2), g((size_t)B * 2 * F * 9), gR((size_t)B * 9), gT((size_t)B * 3);
+        std::vector<double> abs_terms((size_t)B * 12, 0.0);
+        std::vector<int> n_terms((size_t)B, 0);
+        int kinds[4] = {0, 0, 0, 0};
+        for (int b = 0; b < B; ++b) {
+            Cam cam;
+            load_cam(R.data(), T.data(), K.data(), b, cam);
+            int n = 0;
+            for (int f = 0; f < F; ++f) {
+                f3 p[3];
+                for (int i = 0; i < 3; ++i) p[i] = project(verts.data() + (size_t)faces[f * 3 + i] * 3, cam, eps).ndc;
+                ClippedFace cf;
+                clip_face(p, 1, zc, persp, cf);
+                for (int t = 0; t < cf.emit; ++t) {
+                    const size_t o = (size_t)b * 2 * F + n + t;
+                    c2o[o] = f; code[o] = t == 0 ? cf.code0 : cf.code1; cw[o * 2] = cf.w2; cw[o * 2 + 1] = cf.w3;
+                    ++kinds[code[o] < 0 ? 3 : code[o] >> 2];
+                }
+                n += cf.emit;
+            }
+            num[b] = n;
+        }
+        for (auto &x : g) x = rnd();
+        host_pose_grad(verts.data(), faces.data(), R.data(), T.data(), K.data(), B, F, eps, zc, persp, num.data(), c2o.data(), code.data(), cw.data(),
+                       g.data(), gR.data(), gT.data(), abs_terms.data(), n_terms.data());
+        double s = 0.0;
+        for (float x : gR) s += x;
+        for (float x : gT) s += x;
+        if (!(s - s == 0.0) || !kinds[0] || !kinds[1] || !kinds[2] || !kinds[3]) {
+            std::printf("camera gradient persp=%d: sum %g, kinds %d %d %d, untouched %d\n", persp, s, kinds[0], kinds[1], kinds[2], kinds[3]);
+            return 1;
+        }
+        std::printf("camera gradient persp=%d: ok\n", persp);
+    }
+    return 0;
+}
+#endif
