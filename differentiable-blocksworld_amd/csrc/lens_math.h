@@ -87,4 +87,103 @@ DBW_HD uint8_t lens_blend(uint8_t p00, uint8_t p01, uint8_t p10, uint8_t p11, fl
     return (uint8_t)(int)(val + 0.5f);
 }
 
+// ---- per-frame cameras rectified to one pinhole (lens_rectify.hip) -------------------------------------------------------------
+// Every frame of a chunk has a source camera of its own -- a model id (0: the radial-tangential model above, 1: OpenCV's fisheye), fx, fy,
+// cx, cy, k1..k4, p1, p2 -- and all of them are resampled into ONE target pinhole (cx0, cy0, 1/fx0, 1/fy0; the reciprocals rounded from
+// fp64 by the host like inv_zf* above).  Output pixel (i, j) reads its frame at
+//   x  = (j + 0.5 - cx0) * inv_fx0          y  = (i + 0.5 - cy0) * inv_fy0          r2 = x*x + y*y
+//   model 0:  d, xd, yd, u, v as above with the source's k*, p*, fx, fy, cx, cy: where cx0 = cx, cy0 = cy, inv_f*0 = inv_zf* this is
+//             lens_source operation for operation
+//   model 1:  r  = sqrt(r2)                 th = atan(r)                            t2 = th*th
+//             td = th*(1 + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4))))
+//             s  = td / r   (1 where r2 == 0: the principal point on a pixel centre)
+//             u  = (x*s)*fx + cx - 0.5      v  = (y*s)*fy + cy - 0.5               (p1, p2 are not read)
+// The arctangent is written here (lens_atan), from + - * and the IEEE division and square root both builds round correctly (hipcc's default,
+// build.py; g++ -O2 has no fast-math): a library atanf differs between the device and the host, and the tests of this family compare bytes.
+// It is the Cephes single-precision reduction for t >= 0,
+//   t > tan(3 pi/8):  y0 = pi/2, a = -(1 / t)      t > tan(pi/8):  y0 = pi/4, a = (t - 1) / (t + 1)      else  y0 = 0, a = t
+//   z = a*a,  q = ((A3*z + A2)*z + A1)*z + A0,  atan(t) = y0 + ((q*z)*a + a)
+// one rounding per operation in this order.  Its relative error stays below 8 * 2^-24 (the account: tests/test_host_rectify_math.py, which
+// measures 3.3 * 2^-24 at the worst of its arguments); the chain from r2 to (u, v) adds a rounding per
+// operation, each relative to a value of at most the largest coordinate (tests/test_host_rectify_math.py holds the whole map to
+// 64 * 2^-23 * max(H, W) px against fp64, the bound of the shared map).  A NaN fails every comparison, takes the last branch and stays a NaN
+// up to the clamps of lens_split, which land it on 0.
+constexpr int LENS_RECT_N_PARAMS = 16;    // a row of the `cams` table of dbw_lens_rectify_u8: the struct below and 5 floats of padding (64 bytes)
+constexpr int LENS_RECT_PINHOLE = 0, LENS_RECT_FISHEYE = 1;     // (0: radial-tangential, a pinhole where every coefficient is 0)
+
+struct LensCam {
+    float model, fx, fy, cx, cy, k1, k2, k3, k4, p1, p2;
+};
+struct LensTarget {
+    float cx0, cy0, inv_fx0, inv_fy0;
+};
+
+DBW_HD LensCam lens_cam(const float *row) {
+    LensCam C;
+    C.model = row[0]; C.fx = row[1]; C.fy = row[2]; C.cx = row[3]; C.cy = row[4];
+    C.k1 = row[5]; C.k2 = row[6]; C.k3 = row[7]; C.k4 = row[8]; C.p1 = row[9]; C.p2 = row[10];
+    return C;
+}
+
+DBW_HD LensTarget lens_target(const float *target) {
+    LensTarget T;
+    T.cx0 = target[0]; T.cy0 = target[1]; T.inv_fx0 = target[2]; T.inv_fy0 = target[3];
+    return T;
+}
+
+// atan(t) for t >= 0 (the order of the operations: the comment above).
+DBW_HD float lens_atan(float t) {
+    float y0, a;
+    if (t > 2.414213562373095f) {                               // tan(3 pi / 8)
+        y0 = 1.5707963267948966f;
+        a = -(1.0f / t);
+    } else if (t > 0.4142135623730950f) {                       // tan(pi / 8)
+        y0 = 0.7853981633974483f;
+        a = (t - 1.0f) / (t + 1.0f);
+    } else {
+        y0 = 0.0f;
+        a = t;
+    }
+    const float z = a * a;
+    const float q = ((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f;
+    return y0 + ((q * z) * a + a);
+}
+
+// The source index coordinates of output pixel (i, j) of the target in the frame of camera C, not clamped.
+DBW_HD void lens_rect_source(const LensCam &C, const LensTarget &T, int i, int j, float *u, float *v) {
+    const float x = ((float)j + 0.5f - T.cx0) * T.inv_fx0, y = ((float)i + 0.5f - T.cy0) * T.inv_fy0;
+    const float xx = x * x, yy = y * y, xy = x * y;
+    const float r2 = xx + yy;
+    if (C.model == (float)LENS_RECT_FISHEYE) {
+        const float r = __builtin_sqrtf(r2);
+        const float th = lens_atan(r);
+        const float t2 = th * th;
+        const float td = th * (1.0f + t2 * (C.k1 + t2 * (C.k2 + t2 * (C.k3 + t2 * C.k4))));
+        const float s = r2 == 0.0f ? 1.0f : td / r;
+        *u = (x * s) * C.fx + C.cx - 0.5f;
+        *v = (y * s) * C.fy + C.cy - 0.5f;
+        return;
+    }
+    const float d = 1.0f + r2 * (C.k1 + r2 * (C.k2 + r2 * (C.k3 + r2 * C.k4)));
+    const float xd = x * d + (2.0f * C.p1) * xy + C.p2 * (r2 + 2.0f * xx);
+    const float yd = y * d + (2.0f * C.p2) * xy + C.p1 * (r2 + 2.0f * yy);
+    *u = xd * C.fx + C.cx - 0.5f;
+    *v = yd * C.fy + C.cy - 0.5f;
+}
+
+// lens_valid and lens_tap of a frame with a camera of its own.
+DBW_HD bool lens_rect_valid(const LensCam &C, const LensTarget &T, int i, int j, int H, int W) {
+    float u, v;
+    lens_rect_source(C, T, i, j, &u, &v);
+    return u >= 0.0f && u <= (float)(W - 1) && v >= 0.0f && v <= (float)(H - 1);
+}
+DBW_HD LensTap lens_rect_tap(const LensCam &C, const LensTarget &T, int i, int j, int H, int W) {
+    float u, v;
+    lens_rect_source(C, T, i, j, &u, &v);
+    LensTap t;
+    t.x0 = lens_split(u, W, &t.wx);
+    t.y0 = lens_split(v, H, &t.wy);
+    return t;
+}
+
 }  // namespace dbw

@@ -195,6 +195,9 @@ LENS_SIGNATURES = {
     'dbw_images_undistort_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     # the validity map of a rectified frame, added under revision 1 of the header
     'dbw_lens_valid_u8': [c_i, c_i, c_p, c_p, c_p],
+    # frames with a camera each rectified to one pinhole (csrc/lens_rectify.hip), added under revision 1 of the header
+    'dbw_lens_rectify_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    'dbw_lens_rectify_valid_u8': [c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     # camera pose refinement (csrc/pose_grad.hip), added under revision 1 of the header
     'dbw_lens_pose_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_i, c_p],
     'dbw_lens_pose_apply': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
@@ -204,6 +207,7 @@ LENS_OTHER_SIGNATURES = {
     'dbw_lens_pose_grad_workspace_bytes': (c_sz, [c_i, c_i]),
 }
 LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h
+LENS_RECT_N_PARAMS = 16                                       # DBW_LENS_RECT_N_PARAMS
 LENS_ABI_VERSION = header_define('dbw_lens.h', 'DBW_LENS_ABI_VERSION')
 
 # the run monitor: name -> argtypes, exactly the int-returning prototypes of include/dbw_monitor.h (checked by tests/test_abi_families.py);

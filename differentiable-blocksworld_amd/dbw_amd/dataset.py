@@ -93,10 +93,13 @@ class ImageStore:
     masks (N,1,h,w) fp32 of 0 / 1 beside the targets.  A decoded mask (decode_mask: 0 / 255) is expanded to 3 channels, goes through
     mask_prepare (default: prepare, the frames' own warp), is ANDed with valid and resized by the kernel that resizes the frames
     (ops.resample_u8, out='u8'); a training pixel is valid where that byte is 255, that is where its whole footprint is valid.  The
-    existing kernels do the warp and the resize: three identical channels on a once-per-scene pass are accepted for that."""
+    existing kernels do the warp and the resize: three identical channels on a once-per-scene pass are accepted for that.
+    per_frame=True (a scene whose frames have a camera each): prepare and mask_prepare are called with the chunk AND the file
+    indices of its frames, prepare(raw, ids), and valid is one map per frame, (N,Hraw,Wraw) or a callable from the device to that."""
 
-    def __init__(self, files, img_size, chunk=16, prepare=None, mask_files=None, mask_prepare=None, valid=None):
+    def __init__(self, files, img_size, chunk=16, prepare=None, mask_files=None, mask_prepare=None, valid=None, per_frame=False):
         self.files, self.img_size, self.chunk, self.prepare = list(files), tuple(img_size), chunk, prepare
+        self.per_frame = bool(per_frame)
         self.mask_files = None if mask_files is None else list(mask_files)
         if self.mask_files is not None and len(self.mask_files) != len(self.files):
             raise ValueError(f'{len(self.mask_files)} masks for {len(self.files)} frames')
@@ -126,8 +129,9 @@ class ImageStore:
                         self.valid = self.valid(device)
                     if self.valid is not None:
                         self.valid = torch.as_tensor(self.valid, dtype=torch.uint8).to(device)
-                        if tuple(self.valid.shape) != tuple(self.raw_size):
-                            raise ValueError(f'valid: {tuple(self.valid.shape)}, the frames are {tuple(self.raw_size)}')
+                        want = ((len(self.files),) if self.per_frame else ()) + tuple(self.raw_size)
+                        if tuple(self.valid.shape) != want:
+                            raise ValueError(f'valid: {tuple(self.valid.shape)}, the frames are {want}')
             if keep_raw and self.raw is None:
                 self.raw = torch.empty(len(self.files), *self.raw_size, 3, dtype=torch.uint8, device=device)
             slot = b % 2                                         # two staging buffers: the next chunk is decoded while this one is copied
@@ -148,7 +152,7 @@ class ImageStore:
                 events[slot] = torch.cuda.Event()
                 events[slot].record(torch.cuda.current_stream(device))
             idx = torch.as_tensor(part, device=device)
-            self.imgs[idx] = ops.resample_u8(raw if self.prepare is None else self.prepare(raw), self.img_size, out='f32')
+            self.imgs[idx] = ops.resample_u8(self._warp(self.prepare, raw, part), self.img_size, out='f32')
             if self.has_masks:
                 self.masks[idx] = self._masks_of(part, device)
             if self.raw is not None:
@@ -157,6 +161,11 @@ class ImageStore:
             self.have[part] = True
         idx = torch.as_tensor(ids, dtype=torch.long, device=device)
         return self.imgs[idx], (self.raw[idx] if keep_raw else None)
+
+    def _warp(self, prepare, chunk, part):
+        if prepare is None:
+            return chunk
+        return prepare(chunk, part) if self.per_frame else prepare(chunk)
 
     def _masks_of(self, part, device):
         """(n,1,h,w) fp32 masks of the frames `part` (file indices), made on the device as the class docstring says."""
@@ -167,10 +176,9 @@ class ImageStore:
                 if self.mask_files[i] is not None:
                     m[j] = torch.from_numpy(decode_mask(self.mask_files[i], (H, W)))[:, :, None]
         m = m.to(device)
-        if self.mask_prepare is not None:
-            m = self.mask_prepare(m)
+        m = self._warp(self.mask_prepare, m, part)
         if self.valid is not None:
-            m = m & self.valid[None, :, :, None]
+            m = m & (self.valid[torch.as_tensor(part, device=device)][:, :, :, None] if self.per_frame else self.valid[None, :, :, None])
         small = ops.resample_u8(m.contiguous(), self.img_size, out='u8')
         return (small[..., 0] == 255).to(torch.float32)[:, None]
 
@@ -290,14 +298,26 @@ CAMERA_KEYS = ('fl_x', 'fl_y', 'cx', 'cy', 'w', 'h') + LENS_COEFFS
 TRAIN_SPLIT_FRACTION = 0.9                                                  # Nerfstudio's default split of a capture
 
 
-def lens_source(H, W, intr, dist, zoom, i, j):
+def lens_source(H, W, intr, dist, zoom, i, j, model=0, target=None):
     """The map of csrc/lens_math.h in fp64: the source INDEX coordinates (u, v) of the output pixels (i, j) (arrays) of an H x W frame
-    rectified with the focal lengths zoom * (fx, fy).  intr = (fx, fy, cx, cy), dist = (k1, k2, k3, k4, p1, p2)."""
+    rectified with the focal lengths zoom * (fx, fy).  intr = (fx, fy, cx, cy), dist = (k1, k2, k3, k4, p1, p2).  model: 0 OpenCV's
+    radial-tangential lens, 1 its fisheye lens (k1..k4; p1, p2 are not read).  target = (fx0, fy0, cx0, cy0): the pinhole camera the
+    output pixels belong to, zoomed by `zoom` (a scene of per-frame cameras: common_pinhole); None: the source's own."""
     fx, fy, cx, cy = [float(v) for v in intr]
     k1, k2, k3, k4, p1, p2 = [float(v) for v in dist]
-    x = (np.asarray(j, np.float64) + 0.5 - cx) / (zoom * fx)
-    y = (np.asarray(i, np.float64) + 0.5 - cy) / (zoom * fy)
+    fx0, fy0, cx0, cy0 = (fx, fy, cx, cy) if target is None else [float(v) for v in target]
+    x = (np.asarray(j, np.float64) + 0.5 - cx0) / (zoom * fx0)
+    y = (np.asarray(i, np.float64) + 0.5 - cy0) / (zoom * fy0)
     r2 = x * x + y * y
+    if model == 1:
+        r = np.sqrt(r2)
+        th = np.arctan(r)
+        t2 = th * th
+        td = th * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+        s = np.where(r2 == 0, 1.0, td / np.where(r2 == 0, 1.0, r))
+        return x * s * fx + cx - 0.5, y * s * fy + cy - 0.5
+    if model != 0:
+        raise ValueError(f'model: 0 (radial-tangential) or 1 (fisheye), got {model!r}')
     d = 1 + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * k4)))
     xd = x * d + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
     yd = y * d + 2 * p2 * x * y + p1 * (r2 + 2 * y * y)
@@ -308,17 +328,29 @@ def lens_zoom(H, W, intr, dist):
     """The smallest zoom s >= 1 at which every border pixel centre of the rectified H x W frame reads inside the source frame
     (0 <= u <= W - 1, 0 <= v <= H - 1): no black or smeared border reaches the loss, which has no mask.  1.0 where that holds at s = 1;
     otherwise [1, 2] is bisected 40 times and the upper end returned.  ValueError where s = 2 does not suffice."""
-    i = np.concatenate([np.zeros(W), np.full(W, H - 1), np.arange(H), np.arange(H)])
-    j = np.concatenate([np.arange(W), np.arange(W), np.zeros(H), np.full(H, W - 1)])
+    i, j = _border(H, W)
 
     def inside(s):
         u, v = lens_source(H, W, intr, dist, s, i, j)
         return bool(np.all((u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)))           # (False for a NaN)
 
+    return _smallest_zoom(inside, f'lens_zoom: the border of a {H}x{W} frame leaves the source even at a zoom of 2 (intr={tuple(intr)}, '
+                                  f'dist={tuple(dist)})')
+
+
+def _border(H, W):
+    """(i, j) of the border pixels of an H x W frame."""
+    i = np.concatenate([np.zeros(W), np.full(W, H - 1), np.arange(H), np.arange(H)])
+    j = np.concatenate([np.arange(W), np.arange(W), np.zeros(H), np.full(H, W - 1)])
+    return i, j
+
+
+def _smallest_zoom(inside, refusal):
+    """The bisection of lens_zoom and rectify_zoom: 1.0 where inside(1.0), ValueError(refusal) where not inside(2.0)."""
     if inside(1.0):
         return 1.0
     if not inside(2.0):
-        raise ValueError(f'lens_zoom: the border of a {H}x{W} frame leaves the source even at a zoom of 2 (intr={tuple(intr)}, dist={tuple(dist)})')
+        raise ValueError(refusal)
     lo, hi = 1.0, 2.0
     for _ in range(40):
         mid = 0.5 * (lo + hi)
@@ -327,6 +359,35 @@ def lens_zoom(H, W, intr, dist):
         else:
             lo = mid
     return hi
+
+
+def common_pinhole(intrs):
+    """The pinhole camera (fx0, fy0, cx0, cy0) that the frames of a capture with per-frame intrinsics (N,4) are rectified into, before any
+    zoom: the median of each component over the frames.  Equal cameras give exactly the camera they share; one odd frame (a refocus, a
+    second body of a rig) does not move it."""
+    intrs = np.asarray(intrs, dtype=np.float64).reshape(-1, 4)
+    if len(intrs) == 0:
+        raise ValueError('common_pinhole: no cameras')
+    return tuple(float(v) for v in np.median(intrs, axis=0))
+
+
+def rectify_zoom(H, W, intrs, dists, models, target):
+    """lens_zoom for per-frame cameras: the smallest s >= 1 at which every border pixel centre of the H x W frame of the pinhole `target`
+    (fx0, fy0, cx0, cy0), zoomed by s, reads inside the source frame of EVERY camera (intrs (N,4), dists (N,6), models (N,)).  The same
+    bisection; ValueError where s = 2 does not suffice."""
+    i, j = _border(H, W)
+    cams = sorted(set((tuple(float(v) for v in a), tuple(float(v) for v in d), int(m)) for a, d, m in zip(intrs, dists, models)))
+
+    def inside(s):
+        for intr, dist, model in cams:
+            u, v = lens_source(H, W, intr, dist, s, i, j, model=model, target=target)
+            if not bool(np.all((u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1))):
+                return False
+        return True
+
+    return _smallest_zoom(inside, f'rectify_zoom: the border of a {H}x{W} frame of the common camera {tuple(target)} leaves the source of one '
+                                  f"of the {len(cams)} distinct cameras even at a zoom of 2: lens='mask' rectifies without a zoom and masks "
+                                  'what a frame cannot fill')
 
 
 def _rotation_to_z(up):
@@ -376,12 +437,21 @@ class CustomScene(_Scene):
     val none.  scale_mat: the normalised frame back to the file's; pc_gt: the points of `ply_file_path` or points.ply, normalised.
     masks=True reads each frame's `mask_path` (relative to the json, as Nerfstudio's exporters write it; a frame without one is all
     valid) into views()['masks']; lens='mask' rectifies at zoom 1 and masks what reads outside the source frame (ops.lens_valid_u8)
-    instead of cropping it away with lens_zoom ('crop'), and never raises lens_zoom's ValueError."""
+    instead of cropping it away with lens_zoom ('crop'), and never raises lens_zoom's ValueError.
+    cameras='per_frame'  reads fl_x, fl_y, cx, cy, k1..k4, p1, p2 frame by frame (the frame's own value where it has one,
+    else the top level's; w, h must still agree) and accepts camera_model OPENCV_FISHEYE: every frame is warped from its own camera into
+    ONE pinhole (ops.rectify_u8) -- intr = common_pinhole(intrs), zoomed by rectify_zoom under 'crop'; under lens='mask' at zoom 1 with
+    a validity map per frame --, so K stays one matrix.  intrs (N,4), dists (N,6), models (N,) keep the frames' cameras; dist is what they
+    share, None where they differ.  'shared', the default, refuses both kinds of capture."""
     name, folder = 'custom', 'custom'
 
     def __init__(self, root, tag, split, downscale_factor=1, img_size=None, undistort=True, normalize='poses', view_ids=None, store=None,
-                 masks=False, lens='crop'):
+                 masks=False, lens='crop', cameras='shared'):
         import json
+        if cameras not in ('shared', 'per_frame'):
+            raise ValueError(f"cameras: 'shared' or 'per_frame', got {cameras!r}")
+        per_frame = cameras == 'per_frame'
+        self.cameras = cameras
         self.split, self.tag = split, tag
         self.data_path = Path(root) / self.folder / tag
         path = self.data_path / 'transforms.json'
@@ -393,11 +463,20 @@ class CustomScene(_Scene):
         if not frames:
             raise ValueError(f'{path}: no frames')
         model = meta.get('camera_model')
-        if model not in (None, 'OPENCV', 'PINHOLE'):
-            raise NotImplementedError(f"{path}: camera_model '{model}' is not supported (OPENCV and PINHOLE are)")
-        cam = {}
+        if per_frame and model not in (None, 'OPENCV', 'OPENCV_FISHEYE', 'PINHOLE'):
+            raise NotImplementedError(f"{path}: camera_model '{model}' is not supported (OPENCV, OPENCV_FISHEYE and PINHOLE are)")
+        if not per_frame and model not in (None, 'OPENCV', 'PINHOLE'):
+            hint = " (OPENCV_FISHEYE is under cameras='per_frame')" if model == 'OPENCV_FISHEYE' else ''
+            raise NotImplementedError(f"{path}: camera_model '{model}' is not supported (OPENCV and PINHOLE are){hint}")
+        cam, each = {}, {}
         for k in CAMERA_KEYS:
             given = [f[k] for f in frames if k in f]
+            if per_frame and k not in ('w', 'h'):
+                # the frame's own value where it has one, else the top level's; a coefficient nobody gives is 0
+                if k not in meta and len(given) != len(frames) and k not in LENS_COEFFS:
+                    raise ValueError(f"{path}: '{k}' is neither given at the top level nor on every frame")
+                each[k] = [float(f[k]) if k in f else float(meta.get(k, 0.0)) for f in frames]
+                continue
             if k in meta:
                 cam[k] = meta[k]
             elif len(given) == len(frames):
@@ -407,11 +486,21 @@ class CustomScene(_Scene):
             else:
                 cam[k] = 0.0
             if any(float(v) != float(cam[k]) for v in given):
-                raise NotImplementedError(f"{path}: per-frame intrinsics differ ('{k}'): the model keeps one K for all views")
+                raise NotImplementedError(f"{path}: per-frame intrinsics differ ('{k}'): the model keeps one K for all views"
+                                          + ('' if k in ('w', 'h') else " (cameras='per_frame' rectifies every frame into one K)"))
         h, w = int(cam['h']), int(cam['w'])
         self.raw_img_size = (h, w)
-        self.intr = tuple(float(cam[k]) for k in ('fl_x', 'fl_y', 'cx', 'cy'))
-        self.dist = tuple(0.0 if model == 'PINHOLE' else float(cam[k]) for k in LENS_COEFFS)
+        if per_frame:
+            # a camera per frame; intr is the pinhole they are all rectified into, dist what they share (None where they do not)
+            self.intrs = np.array([each[k] for k in ('fl_x', 'fl_y', 'cx', 'cy')], dtype=np.float64).T
+            self.dists = np.array([each[k] for k in LENS_COEFFS], dtype=np.float64).T * (0.0 if model == 'PINHOLE' else 1.0)
+            self.models = np.full(len(frames), ops.LENS_MODELS[model or 'OPENCV'], dtype=np.int64)
+            self.intr = common_pinhole(self.intrs)
+            differ = bool((self.intrs != self.intrs[0]).any() or (self.dists != self.dists[0]).any())
+            self.dist = None if (self.dists != self.dists[0]).any() else tuple(float(v) for v in self.dists[0])
+        else:
+            self.intr = tuple(float(cam[k]) for k in ('fl_x', 'fl_y', 'cx', 'cy'))
+            self.dist = tuple(0.0 if model == 'PINHOLE' else float(cam[k]) for k in LENS_COEFFS)
 
         self.input_files = [self._frame_file(path.parent, f['file_path']) for f in frames]
         from PIL import Image
@@ -437,15 +526,26 @@ class CustomScene(_Scene):
 
         if lens not in ('crop', 'mask'):
             raise ValueError(f"lens: 'crop' or 'mask', got {lens!r}")
-        rectify = bool(undistort) and any(c != 0 for c in self.dist)
-        lens_mask = rectify and lens == 'mask'
-        self.zoom = lens_zoom(h, w, self.intr, self.dist) if (rectify and not lens_mask) else 1.0
-        intr, dist, zoom = self.intr, self.dist, self.zoom
-        self.prepare = (lambda raw: ops.undistort_u8(raw, intr, dist, zoom)) if rectify else None
+        if per_frame:
+            if differ and not undistort:
+                raise ValueError(f"{path}: undistort=False with per-frame cameras that differ: there is no single K to train on")
+            # a fisheye frame is no pinhole frame even with every coefficient at 0
+            rectify = bool(undistort) and bool(differ or (self.models != 0).any() or (self.dists != 0).any())
+            lens_mask = rectify and lens == 'mask'
+            self.zoom = rectify_zoom(h, w, self.intrs, self.dists, self.models, self.intr) if (rectify and not lens_mask) else 1.0
+            table, target = ops.lens_table(self.intrs, self.dists, self.models), ops.lens_target(self.intr, self.zoom)
+            self.prepare = (lambda raw, ids: ops.rectify_u8(raw, table[list(ids)], target)) if rectify else None
+            valid = (lambda device: ops.rectify_valid_u8(h, w, table, target, device=device)) if lens_mask else None
+        else:
+            rectify = bool(undistort) and any(c != 0 for c in self.dist)
+            lens_mask = rectify and lens == 'mask'
+            self.zoom = lens_zoom(h, w, self.intr, self.dist) if (rectify and not lens_mask) else 1.0
+            intr, dist, zoom = self.intr, self.dist, self.zoom
+            self.prepare = (lambda raw: ops.undistort_u8(raw, intr, dist, zoom)) if rectify else None
+            valid = (lambda device: ops.lens_valid_u8(h, w, intr, dist, 1.0, device=device)) if lens_mask else None
         self.mask_files = None
         if masks:
             self.mask_files = [self._frame_file(path.parent, f['mask_path']) if f.get('mask_path') else None for f in frames]
-        valid = (lambda device: ops.lens_valid_u8(h, w, intr, dist, 1.0, device=device)) if lens_mask else None
         has_masks = self.mask_files is not None or valid is not None
 
         c2w = np.stack([np.asarray(f['transform_matrix'], dtype=np.float64)[:4, :4] for f in frames])
@@ -487,10 +587,11 @@ class CustomScene(_Scene):
             self.pc_gt = torch.from_numpy(points @ F[:3, :3].T + F[:3, 3]).float()
 
         if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size
-                                  or (store.prepare is None) != (self.prepare is None) or store.has_masks != has_masks):
-            raise ValueError('store: made for other files, another img_size, another lens treatment or other masks')
+                                  or (store.prepare is None) != (self.prepare is None) or store.has_masks != has_masks
+                                  or store.per_frame != per_frame):
+            raise ValueError('store: made for other files, another img_size, another lens treatment (or another `cameras` mode) or other masks')
         self.store = store if store is not None else ImageStore(self.input_files, self.img_size, prepare=self.prepare,
-                                                                mask_files=self.mask_files, valid=valid)
+                                                                mask_files=self.mask_files, valid=valid, per_frame=per_frame)
 
     def world_frame(self, device=None, T_range=(1, 1, 1), **kw):
         """worldfit.estimate_world_frame on this capture's cloud and cameras (both in the normalised frame R, T live in) -> WorldFrame: the

@@ -1073,6 +1073,84 @@ def lens_valid_u8(H, W, intr, dist, zoom=1.0, device='cuda'):
     return out
 
 
+LENS_MODELS = {'OPENCV': 0, 'PINHOLE': 0, 'OPENCV_FISHEYE': 1}         # the model id of a row of lens_table
+
+
+def lens_table(intrs, dists, models):
+    """The HOST `cams` table of dbw_lens_rectify_u8, an (N,16) fp32 CPU tensor with one row [model, fx, fy, cx, cy, k1, k2, k3, k4, p1, p2,
+    0, 0, 0, 0, 0] per frame, from intrs (N,4) = (fx, fy, cx, cy) in pixels, dists (N,6) = (k1, k2, k3, k4, p1, p2) and models (N,) of 0
+    (radial-tangential) or 1 (fisheye)."""
+    intrs = torch.as_tensor(intrs, dtype=torch.float64).reshape(-1, 4)
+    dists = torch.as_tensor(dists, dtype=torch.float64).reshape(-1, 6)
+    models = torch.as_tensor(models, dtype=torch.float64).reshape(-1)
+    N = intrs.shape[0]
+    if dists.shape[0] != N or models.shape[0] != N:
+        raise ValueError(f'intrs (N,4), dists (N,6), models (N,): got {N}, {dists.shape[0]} and {models.shape[0]} rows')
+    if not bool(((models == 0) | (models == 1)).all()):
+        raise ValueError('models: 0 (radial-tangential) or 1 (fisheye)')
+    if not bool((intrs[:, :2] > 0).all()):
+        raise ValueError('the focal lengths must be positive')
+    table = torch.zeros(N, _lib.LENS_RECT_N_PARAMS, dtype=torch.float64)
+    table[:, 0], table[:, 1:5], table[:, 5:11] = models, intrs, dists
+    return table.to(torch.float32)
+
+
+def lens_target(intr0, zoom=1.0):
+    """The HOST `target` array of dbw_lens_rectify_u8, a (4,) fp32 CPU tensor [cx0, cy0, 1/(zoom fx0), 1/(zoom fy0)], from the pinhole camera
+    intr0 = (fx0, fy0, cx0, cy0) every frame is resampled into.  The reciprocals are taken in fp64 and rounded once."""
+    intr0 = [float(v) for v in intr0]
+    if len(intr0) != 4:
+        raise ValueError(f'intr0: (fx, fy, cx, cy), got {len(intr0)} values')
+    zoom = float(zoom)
+    if not (zoom > 0 and intr0[0] > 0 and intr0[1] > 0):
+        raise ValueError(f'zoom and the focal lengths must be positive, got zoom={zoom}, fx={intr0[0]}, fy={intr0[1]}')
+    return torch.tensor([intr0[2], intr0[3], 1.0 / (zoom * intr0[0]), 1.0 / (zoom * intr0[1])], dtype=torch.float64).to(torch.float32)
+
+
+def _rect_tables(table_rows, target, N):
+    table = torch.as_tensor(table_rows, dtype=torch.float32).contiguous()
+    target = torch.as_tensor(target, dtype=torch.float32).contiguous()
+    if table.is_cuda or target.is_cuda:
+        raise ValueError('table_rows and target are HOST arrays (ops.lens_table, ops.lens_target)')
+    if tuple(table.shape) != (N, _lib.LENS_RECT_N_PARAMS) or tuple(target.shape) != (4,):
+        raise ValueError(f'table_rows: ({N},{_lib.LENS_RECT_N_PARAMS}), target: (4,); got {tuple(table.shape)} and {tuple(target.shape)}')
+    return table, target
+
+
+def rectify_u8(raw_u8, table_rows, target):
+    """dbw_lens_rectify_u8: (N,H,W,3) uint8 frames on the GPU, frame n taken by the camera of row n of table_rows (ops.lens_table: a model,
+    intrinsics and coefficients of its own), -> the (N,H,W,3) uint8 frames of the one pinhole camera `target` (ops.lens_target), bilinear
+    (csrc/lens_math.h)."""
+    _lib.family('lens')
+    src = _chk(raw_u8, torch.uint8, 'raw_u8')
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f'raw_u8: (N,H,W,3), got {tuple(src.shape)}')
+    N, H, W, _ = src.shape
+    if H < 2 or W < 2:
+        raise ValueError(f'frames of {(H, W)}: at least 2 x 2')
+    table, target = _rect_tables(table_rows, target, N)
+    out = torch.empty_like(src)
+    if N > 0:
+        _lib.call('dbw_lens_rectify_u8', _ptr(src), N, H, W, table.data_ptr(), target.data_ptr(), _ptr(out), _stream(src))
+    return out
+
+
+def rectify_valid_u8(H, W, table_rows, target, device='cuda'):
+    """dbw_lens_rectify_valid_u8: the (N,H,W) uint8 validity maps of the frames rectify_u8 makes with the same arguments, on `device` -- 255
+    where the output pixel reads inside its source frame (not clamped), 0 elsewhere."""
+    _lib.family('lens')
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f'a frame of {(H, W)}')
+    table, target = _rect_tables(table_rows, target, len(table_rows))
+    out = torch.empty(table.shape[0], H, W, dtype=torch.uint8, device=device)
+    if not out.is_cuda:
+        raise RuntimeError('rectify_valid_u8 runs on the GPU (there is no CPU fallback)')
+    if table.shape[0] > 0:
+        _lib.call('dbw_lens_rectify_valid_u8', table.shape[0], H, W, table.data_ptr(), target.data_ptr(), _ptr(out), _stream(out))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # camera pose refinement (include/dbw_lens.h, DESIGN.md 6o)
 # ---------------------------------------------------------------------------------------------------------------------

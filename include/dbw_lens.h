@@ -3,7 +3,8 @@
  * Lens: raw 8-bit frames, resident on the device, resampled from the distorted image of an OpenCV radial-tangential lens (the k1..k4, p1,
  * p2 of a Nerfstudio transforms.json) into the pinhole frame the renderer assumes, before the image ingest (dbw_ingest.h) resizes them.
  * Pose: the gradient of a render with respect to each view's R and T, and the per-view 6-vector that refines a pose during training.
- * Python side: dbw_amd/ops.py (undistort_u8, lens_valid_u8, project_clip_bwd_cam, pose_apply), bound through _lib.LENS_SIGNATURES and
+ * A capture whose frames have a camera each, or a fisheye lens, is rectified frame by frame into one pinhole (dbw_lens_rectify_u8).
+ * Python side: dbw_amd/ops.py (undistort_u8, lens_valid_u8, rectify_u8, rectify_valid_u8, project_clip_bwd_cam, pose_apply), bound through _lib.LENS_SIGNATURES and
  * _lib.LENS_OTHER_SIGNATURES.  The arithmetic is csrc/lens_math.h and csrc/pose_math.h.
  *
  * Conventions are those of dbw_hip.h: DEVICE pointers owned by the caller, contiguous, unless said otherwise; return 0 or a negative
@@ -43,6 +44,34 @@ int dbw_images_undistort_u8(const uint8_t *src, int N, int H, int W, const float
  * a NaN coordinate.  lens: the HOST array of dbw_images_undistort_u8.  One map serves every frame of a scene: with it as a mask of the
  * loss the frames need no zoom that crops the border away.  H >= 1, W >= 1. */
 int dbw_lens_valid_u8(int H, int W, const float *lens, uint8_t *out, dbw_stream_t stream);
+
+/* Frames with a camera each, rectified to one pinhole: added under revision 1 of this header.  Number of floats of a row of `cams`. */
+#define DBW_LENS_RECT_N_PARAMS 16
+
+/* src (N,H,W,3) uint8 -> out (N,H,W,3) uint8, both on the DEVICE; they must not overlap (DBW_ERR_INVALID).  N >= 1, H >= 2, W >= 2.
+ * cams: a HOST array of N * DBW_LENS_RECT_N_PARAMS floats, one row per frame of the chunk in the chunk's order:
+ * [model, fx, fy, cx, cy, k1, k2, k3, k4, p1, p2, 0, 0, 0, 0, 0] -- model 0: OpenCV's radial-tangential lens (the one of
+ * dbw_images_undistort_u8; a pinhole where the coefficients are 0), model 1: OpenCV's fisheye lens (k1..k4; p1, p2 are not read) --, focal
+ * lengths and principal point of THAT frame in pixels (pixel centres at +0.5).  target: a HOST array of 4 floats [cx0, cy0, 1/fx0, 1/fy0],
+ * the pinhole camera every frame is resampled into, the reciprocals rounded once from fp64.  Both arrays are read before the call returns.
+ * Output pixel (i, j) of frame n is the bilinear sample of that frame at
+ *   x = (j + 0.5 - cx0) / fx0, y = (i + 0.5 - cy0) / fy0, r2 = x*x + y*y,
+ *   model 0: (u, v) of dbw_images_undistort_u8 from (x, y, r2) on, with the frame's own coefficients, focal lengths and principal point
+ *            (with cx0 = cx, cy0 = cy, 1/fx0 = inv_zfx, 1/fy0 = inv_zfy: the bytes of dbw_images_undistort_u8),
+ *   model 1: r = sqrt(r2), th = atan(r), td = th*(1 + k1 th^2 + k2 th^4 + k3 th^6 + k4 th^8), s = td / r (1 where r2 == 0),
+ *            u = x*s*fx + cx - 0.5, v = y*s*fy + cy - 0.5,
+ * clamped to the frame, in fp32 and rounded half up; csrc/lens_math.h has the order of the operations and the arctangent, which is
+ * written there from + - * / sqrt so that a host build gives the same bytes.  Refused before any launch (DBW_ERR_INVALID): a value of cams
+ * (its padding too) or of target that is not finite, a model id other than 0 and 1, a focal length or a reciprocal that is not > 0.
+ * The table travels in the arguments of the launches, 32 frames to a launch: no allocation, no copy, no synchronisation.  Any alignment
+ * of src and out and any W give the same bytes. */
+int dbw_lens_rectify_u8(const uint8_t *src, int N, int H, int W, const float *cams, const float *target, uint8_t *out, dbw_stream_t stream);
+
+/* The validity maps of the frames dbw_lens_rectify_u8 makes from the same cams and target: out (N,H,W) uint8 on the DEVICE, 255 where
+ * output pixel (i, j) of frame n reads inside its source frame -- 0 <= u <= W - 1 and 0 <= v <= H - 1, NOT clamped --, 0 elsewhere and
+ * for a NaN coordinate.  The per-frame form of dbw_lens_valid_u8: what one source frame cannot fill of the common target is masked in
+ * that frame alone.  N >= 1, H >= 1, W >= 1. */
+int dbw_lens_rectify_valid_u8(int N, int H, int W, const float *cams, const float *target, uint8_t *out, dbw_stream_t stream);
 
 /* Camera pose refinement, added under revision 1 of this header.  Conventions of the camera transform (dbw_project_clip_fwd): row vectors,
  * v = X.R + T, R (B,3,3) row-major, T (B,3).
