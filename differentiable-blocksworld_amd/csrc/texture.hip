@@ -188,11 +188,12 @@ __device__ __forceinline__ void adam_tex_set(const AdamTailK &A, const AdamTex &
     if (t.d <= 1) {
         const long long total = (long long)t.n * t.h * t.w * 3;
         for (long long i = etid; i < total; i += neth) {
-            const float s = tex_sigmoid(t.tex[i]);
+            float oms;          // 1 - s
+            const float s = tex_sigmoid(t.tex[i], oms);
             float g = t.gmaps[i];
             if (A.clear_maps) t.gmaps[i] = 0.f;
             if (t.gsig) g += t.gsig[i];
-            const float gt = g * s * (1.f - s);
+            const float gt = g * s * oms;
             const long long o = t.off + i;
             A.g[o] = gt;
             if (!skip) adam_update(A.p[o], gt, A.m[o], A.v[o], group_step_size(A.G, o), A.beta1, A.beta2, A.eps, A.bc2_sqrt);
@@ -214,10 +215,11 @@ __device__ __forceinline__ void adam_tex_set(const AdamTailK &A, const AdamTex &
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const long long i = e + ch;
-                const float s = tex_sigmoid(t.tex[i]);
+                float oms;          // 1 - s
+                const float s = tex_sigmoid(t.tex[i], oms);
                 float g = gc[ch] * inv;
                 if (t.gsig) g += t.gsig[i];
-                const float gt = g * s * (1.f - s);
+                const float gt = g * s * oms;
                 const long long o = t.off + i;
                 A.g[o] = gt;
                 if (!skip) adam_update(A.p[o], gt, A.m[o], A.v[o], group_step_size(A.G, o), A.beta1, A.beta2, A.eps, A.bc2_sqrt);

@@ -7,6 +7,15 @@ namespace dbw {
 
 __device__ __forceinline__ float tex_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
+// the same sigmoid and 1 - s for its derivative s (1 - s).  For x >= 0, 1 - s = e / (1 + e) = e s with e = exp(-x): the float32 s rounds to 1
+// above x = 16.6 and 1.f - s cancels to 0 there (and has lost 3 digits by x = 8), which flushed the gradient of a saturated texel.
+// x < 0: 1.f - s as before, bit for bit.
+__device__ __forceinline__ float tex_sigmoid(float x, float &one_minus_s) {
+    const float e = expf(-x), s = 1.f / (1.f + e);
+    one_minus_s = x >= 0.f ? e * s : 1.f - s;
+    return s;
+}
+
 // d == 1: elementwise.  d > 1: one WAVE per (d x d) cell (lane <-> texel, wave-sum for the cell mean); `maps` is written
 // at CELL resolution (n, h/d, w/d, 3).
 // (blocks bid of nblk: a kernel that runs the preparation next to something else gives it a slice of its own grid)
@@ -47,7 +56,7 @@ __device__ __forceinline__ void texture_prep_fwd_body(const float *__restrict__ 
     }
 }
 
-// Backward of the preparation, elementwise: gtex = (gcell[cell of the texel] / d^2 + gsig) * s (1 - s).  A grid-stride loop over blocks
+// Backward of the preparation, elementwise: gtex = (gcell[cell of the texel] / d^2 + gsig) * s (1 - s) (tex_sigmoid's 1 - s).  A grid-stride loop over blocks
 // bid of nblk (a kernel that runs it next to something else gives it a slice of its own grid)
 __device__ __forceinline__ void texture_prep_bwd_body(const float *__restrict__ tex, int n, int h, int w, int d,
                                                       const float *__restrict__ gmaps, const float *__restrict__ gsig,
@@ -56,7 +65,8 @@ __device__ __forceinline__ void texture_prep_bwd_body(const float *__restrict__ 
     const float inv = 1.f / (float)(d * d);
     const int ch_ = h / d, cw_ = w / d;
     for (long long i = bid * blockDim.x + threadIdx.x; i < total; i += nblk * blockDim.x) {
-        const float s = tex_sigmoid(tex[i]);
+        float oms;          // 1 - s
+        const float s = tex_sigmoid(tex[i], oms);
         float g;
         if (d <= 1) g = gmaps[i];
         else {
@@ -66,7 +76,7 @@ __device__ __forceinline__ void texture_prep_bwd_body(const float *__restrict__ 
             g = gmaps[(((long long)m * ch_ + y / d) * cw_ + x / d) * 3 + k] * inv;
         }
         if (gsig) g += gsig[i];
-        gtex[i] = g * s * (1.f - s);
+        gtex[i] = g * s * oms;
     }
 }
 

@@ -340,7 +340,7 @@ int dbw_tv_l2sq(const float *maps, int n, int h, int w, int wrap_x, float scale,
  * samples; sample p of block k is ((u*2-1)*ratio*S_k)@R_k+T_k (no grad), tested against EVERY block.
  * loss += scale*mean_p(clamp(sum_k sigmoid(-sdf_k/temperature)*alpha_k - n_blocks_thresh, 0)).
  * alpha (Kb) = _alpha_full.  Grads accumulate into g_sq_eps,g_S,g_R6,g_T,g_alpha.
- * workspace: Kb*17 floats, zeroed by the caller. */
+ * workspace: Kb*18 floats (17 raw pose / shape accumulators and alpha's per block), zeroed by the caller. */
 int dbw_overlap_loss(const float *u, int npts, const float *sq_eps, const float *S, const float *R6, const float *T,
                      const float *alpha, int Kb, float ratio, float scale_min, float temperature,
                      float n_blocks_thresh, float scale, float *loss, float *g_sq_eps, float *g_S, float *g_R6,

@@ -1,5 +1,6 @@
 """GPU parity of the model-level path and of the small kernels around the renderer (param -> mesh, texture prep,
-regularisers, composite+MSE, Adam) against the CPU oracle / torch fp32 references.  `-m gpu`."""
+regularisers, composite+MSE, Adam) against the CPU oracle / torch fp32 references.  `-m gpu`.
+(The same kernels at the edges of their launch geometry, per element against float64 with measured bars: tests/test_gpu_model_kernels.py.)"""
 import numpy as np
 import pytest
 import torch

@@ -32,36 +32,52 @@ def _tail_fn():
     return lib, fn
 
 
-def _case(ts, decim, tv, seed):
-    """flat buffers of 3 groups' worth of parameters, the sky texture straddling the lr groups' boundary, the ground texture in group 1;
+# where the texture sets lie in the flat buffers: tex_n (one set's elements) -> (n, the sets' offsets, the lr groups' ends)
+LAYOUTS = {
+    'default': lambda t: (3 * t + 1234, [1000, 1000 + t + 777], [1000 + t // 2, 3 * t + 1234]),
+    'no-sets': lambda t: (t + 1234, [], [600, t + 1234]),
+    'one-set': lambda t: (2 * t + 1234, [1000], [1000 + t // 2, 2 * t + 1234]),
+    'descending': lambda t: (3 * t + 1234, [1000 + t + 777, 1000], [1000 + t // 2, 3 * t + 1234]),          # the second set lower in memory than the first
+    'offset-0': lambda t: (3 * t + 1234, [0, t + 777], [t // 2, 3 * t + 1234]),
+    'ends-at-n': lambda t: (3 * t + 1234, [1000, 2 * t + 1234], [1000 + t // 2, 3 * t + 1234]),
+    'adjacent': lambda t: (3 * t + 1234, [1000, 1000 + t], [1000 + t // 2, 3 * t + 1234]),
+    'adjacent-descending': lambda t: (3 * t + 1234, [1000 + t, 1000], [1000 + t // 2, 3 * t + 1234]),
+    'rest-0': lambda t: (2 * t, [0, t], [t // 2, 2 * t]),                                                    # the whole buffer is the two sets
+    'rest-0-descending': lambda t: (2 * t, [t, 0], [t // 2, 2 * t]),
+    'one-workgroup': lambda t: (2 * t + 100, [16, t + 60], [t // 2, 2 * t + 100]),                           # with a small set: grid_for(n) == 1, the launcher's grid = 2
+}
+
+
+def _case(ts, decim, tv, seed, shape=None, layout='default'):
+    """flat buffers of 3 groups' worth of parameters, the sky texture straddling the lr groups' boundary, the ground texture in group 1
+    (LAYOUTS: other placements; shape: (n, h, w) of a set instead of (1, ts, ts));
     an arena of random bytes whose hole holds the two prepared maps' gradients (cell resolution)"""
     g = torch.Generator().manual_seed(seed)
-    tex_n = ts * ts * 3
-    cells = (ts // decim) * (ts // decim) * 3
-    n = 3 * tex_n + 1234
-    off = [1000, 1000 + tex_n + 777]
-    group_end = [1000 + tex_n // 2, n]
+    tn, h, w = shape or (1, ts, ts)
+    tex_n = tn * h * w * 3
+    cells = tn * (h // decim) * (w // decim) * 3
+    n, off, group_end = LAYOUTS[layout](tex_n)
     B = {'param': torch.randn(n, generator=g), 'grad': torch.randn(n, generator=g),
          'm': torch.randn(n, generator=g) * 0.1, 'v': torch.rand(n, generator=g) * 0.01}
     hole_lo = 4096
-    hole_hi = hole_lo + ((2 * cells * 4 + 255) // 256) * 256
+    hole_hi = hole_lo + (((2 * cells * 4 + 255) // 256) * 256 if off else 0)
     arena = torch.randint(1, 255, (hole_hi + 8192,), generator=g, dtype=torch.uint8)
     maps = torch.randn(2 * cells, generator=g)
     hole = torch.zeros((hole_hi - hole_lo) // 4)
-    hole[:2 * cells] = maps
+    hole[:len(off) * cells] = maps[:len(off) * cells]          # (the lanes that read a map's gradient clear it: the hole holds nothing else)
     arena[hole_lo:hole_hi] = hole.view(torch.uint8)
     B['arena'] = arena
     B['gsig'] = torch.randn(2 * tex_n, generator=g) if tv else None
     B = {k: (None if v is None else v.to(DEV)) for k, v in B.items()}
-    return B, dict(ts=ts, decim=decim, tex_n=tex_n, cells=cells, off=off, group_end=group_end, hole=(hole_lo, hole_hi))
+    return B, dict(shape=(tn, h, w), decim=decim, tex_n=tex_n, cells=cells, off=off, group_end=group_end, hole=(hole_lo, hole_hi))
 
 
 def _sets(B, c):
     maps = B['arena'][c['hole'][0]:].view(torch.float32)
     out = []
-    for k in range(2):
-        o = c['off'][k]
-        out.append(dict(texture=B['param'][o:].data_ptr(), n=1, h=c['ts'], w=c['ts'], decim=c['decim'],
+    tn, h, w = c['shape']
+    for k, o in enumerate(c['off']):
+        out.append(dict(texture=B['param'][o:].data_ptr(), n=tn, h=h, w=w, decim=c['decim'],
                         grad_maps=maps[k * c['cells']:].data_ptr(),
                         grad_sig=0 if B['gsig'] is None else B['gsig'][k * c['tex_n']:].data_ptr(),
                         grad_texture=B['grad'][o:].data_ptr()))
@@ -74,8 +90,9 @@ ADAM = dict(lr=(5e-3, 5e-2), beta1=0.9, beta2=0.999, eps=1e-8, step=7)
 def _reference(B, c, raised):
     lib = _lib.load()
     arr, ns = _sets(B, c)
-    rc = lib.dbw_texture_prep_bwd_sets(arr, ns, _stream())
-    assert rc == 0, lib.dbw_last_error()
+    if ns:
+        rc = lib.dbw_texture_prep_bwd_sets(arr, ns, _stream())
+        assert rc == 0, lib.dbw_last_error()
     ends = (c_i64 * 2)(*c['group_end'])
     lr = (c_f * 2)(*ADAM['lr'])
     skip = torch.full((1,), raised, device=DEV)
@@ -97,11 +114,7 @@ def _tail(B, c, raised):
     return void_flag
 
 
-@pytest.mark.parametrize('raised', [0.0, 1.0])
-@pytest.mark.parametrize('tv', [False, True])
-@pytest.mark.parametrize('decim', [8, 1])
-def test_adam_tail_is_bit_equal_to_the_texture_backward_then_adam(decim, tv, raised):
-    ref, c = _case(64, decim, tv, seed=11 + decim + 2 * tv)
+def _check_tail(ref, c, raised):
     got = {k: (None if v is None else v.clone()) for k, v in ref.items()}
     before = {k: (None if v is None else v.clone()) for k, v in ref.items()}
     _reference(ref, c, raised)
@@ -112,11 +125,44 @@ def test_adam_tail_is_bit_equal_to_the_texture_backward_then_adam(decim, tv, rai
     if raised:
         for k in ('param', 'm', 'v'):
             assert torch.equal(got[k], before[k]), k          # a voided step moves nothing ...
-    assert not torch.equal(got['grad'], before['grad'])        # ... but its texture gradients are still written
+    else:
+        assert not any(torch.equal(got[k], before[k]) for k in ('param', 'm', 'v'))
+    if c['off']:
+        assert not torch.equal(got['grad'], before['grad'])    # ... but its texture gradients are still written
+    else:
+        assert torch.equal(got['grad'], before['grad'])
     assert float(flag) == raised                                 # the latch
     # the whole arena is clear: the hole by the lanes that read it, the rest by the arena loop
     assert int(got['arena'].count_nonzero()) == 0
     assert int(ref['arena'].count_nonzero()) == 0
+
+
+@pytest.mark.parametrize('raised', [0.0, 1.0])
+@pytest.mark.parametrize('tv', [False, True])
+@pytest.mark.parametrize('decim', [8, 1, 2, 4, 16])
+def test_adam_tail_is_bit_equal_to_the_texture_backward_then_adam(decim, tv, raised):
+    ref, c = _case(64, decim, tv, seed=11 + decim + 2 * tv)
+    _check_tail(ref, c, raised)
+
+
+@pytest.mark.parametrize('raised', [0.0, 1.0])
+@pytest.mark.parametrize('decim', [1, 2, 4, 8, 16])
+def test_adam_tail_on_several_oblong_maps_per_set(decim, raised):
+    """sets of 3 maps of 16 x 48: n > 1 and h != w in the cell indexing of the decimated tail"""
+    ref, c = _case(0, decim, True, seed=31 + decim, shape=(3, 16, 48))
+    _check_tail(ref, c, raised)
+
+
+@pytest.mark.parametrize('decim', [1, 4])
+@pytest.mark.parametrize('layout', [k for k in LAYOUTS if k != 'default'])
+def test_adam_tail_wherever_the_sets_lie_in_the_flat_buffers(layout, decim):
+    """0, 1 and 2 sets; the second set lower in memory than the first (the launcher orders the ranges its compacted Adam index steps over);
+    a set at offset 0, a set ending at n, adjacent sets, nothing but the two sets, and a buffer of one workgroup"""
+    shape = (1, 4, 4) if layout == 'one-workgroup' else (3, 16, 48)
+    ref, c = _case(0, decim, True, seed=51 + decim, shape=shape, layout=layout)
+    if layout == 'one-workgroup':
+        assert c['group_end'][-1] <= 256
+    _check_tail(ref, c, 0.0)
 
 
 def test_adam_tail_refuses_textures_outside_the_flat_buffers():
