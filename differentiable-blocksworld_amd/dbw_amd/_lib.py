@@ -145,9 +145,12 @@ EVAL_SIGNATURES = {
     'dbw_radius_downsample_round': [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_d, c_p, c_p, c_p],
     # plane RANSAC (csrc/plane_fit.hip), added under revision 1 of the header
     'dbw_eval_plane_fit': [c_p, c_i64, c_i, c_i, c_f, c_i64, c_p, c_p, c_f, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    # k-means with per-cluster PCA (csrc/cluster_fit.hip), added under revision 1 of the header
+    'dbw_eval_cluster_fit': [c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 EVAL_OTHER_SIGNATURES = {
     'dbw_eval_plane_workspace_bytes': (c_sz, [c_i64, c_i]),
+    'dbw_eval_cluster_workspace_bytes': (c_sz, [c_i64, c_i]),
 }
 EVAL_PLANE_ORTHOGONAL, EVAL_PLANE_VERTICAL = 0, 1             # DBW_EVAL_PLANE_* of include/dbw_eval.h
 EVAL_ABI_VERSION = header_define('dbw_eval.h', 'DBW_EVAL_ABI_VERSION')
@@ -327,10 +330,12 @@ def family(name):
     got, want = getattr(lib, f.version_fn)(), header_define(f.header, f.macro)
     if got != want:
         raise RuntimeError(f'the library was built for {name} ABI {got}, include/{f.header} declares {want}: rebuild it')
-    # functions added under an unchanged revision: a library that holds some of the family's functions holds all of them
+    # functions added under an unchanged revision: a library that holds some of the family's entry points holds all of them.  The entry
+    # points (the int-returning functions of f.signatures) decide: a size query of f.other_signatures is defined in the source of the entry
+    # point it sizes the workspace of, so it is there exactly when that entry point is; the message names everything that is absent.
     names = list(f.signatures) + list(f.other_signatures)
     missing = [n for n in names if not hasattr(lib, n)]
-    if missing and len(missing) < len(names):
+    if any(n in f.signatures for n in missing) and len(missing) < len(names):
         raise RuntimeError(f'the loaded libdbw_hip.so has the {name} family of include/{f.header} at revision {got} but not '
                            f'{", ".join(missing)}: it was built from older sources, rebuild it')
     return lib

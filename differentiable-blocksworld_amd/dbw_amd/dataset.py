@@ -604,6 +604,16 @@ class CustomScene(_Scene):
         pts = self.pc_gt if device is None else self.pc_gt.to(device)
         return estimate_world_frame(pts, self.cam2world, T_range=T_range, **kw)
 
+    def block_init(self, model, device=None, **kw):
+        """model.init_blocks_from_points on this capture's cloud (in the normalised frame R, T live in): the blocks of `model` start at the
+        clusters of the cloud -> worldfit.BlockInit.  device: where the clustering runs (a cuda device: the HIP kernel).  ValueError for a
+        capture without a cloud."""
+        if self.ply_file is None:
+            raise ValueError(f"'{self.tag}': no point cloud (ply_file_path of transforms.json, or points.ply next to it): the blocks are "
+                             'fitted to the cloud, there is no fit without one')
+        pts = self.pc_gt if device is None else self.pc_gt.to(device)
+        return model.init_blocks_from_points(pts, **kw)
+
     @staticmethod
     def _frame_file(folder, file_path):
         f = folder / file_path

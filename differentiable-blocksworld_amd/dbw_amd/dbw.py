@@ -72,6 +72,33 @@ class DifferentiableBlocksWorld(nn.Module):
     def init_kwargs(self):
         return deepcopy(self._init_kwargs)
 
+    # ------------------------------------------------------------------------------------------------ block poses given from outside
+    @torch.no_grad()
+    def init_blocks(self, T, R_6d, S, index=None):
+        """Sets the poses of the blocks `index` (default: the first len(T)) to T (n,3), R_6d (n,6), S (n,3).  In-place copies into the rows of
+        self.T, self.R_6d and self.S, on purpose: parallel.FlatParams re-homes p.data as views of its flat buffer, and a copy into the view
+        survives that whether it comes before or after.  Nothing else is touched: opacities, shapes and textures keep their init."""
+        n = T.shape[0]
+        index = torch.arange(n) if index is None else torch.as_tensor(index)
+        index = index.to(device=self.T.device, dtype=torch.int64).reshape(-1)
+        if not (tuple(T.shape) == (n, 3) and tuple(R_6d.shape) == (n, 6) and tuple(S.shape) == (n, 3) and index.shape[0] == n):
+            raise ValueError(f'init_blocks: T (n,3), R_6d (n,6), S (n,3) and index (n,) expected, got {tuple(T.shape)}, {tuple(R_6d.shape)}, '
+                             f'{tuple(S.shape)}, {tuple(index.shape)}')
+        if n and not (0 <= int(index.min()) and int(index.max()) < self.n_blocks):
+            raise ValueError(f'init_blocks: block index outside [0, {self.n_blocks})')
+        for p, v in ((self.T, T), (self.R_6d, R_6d), (self.S, S)):
+            p.data.index_copy_(0, index, v.detach().to(device=p.device, dtype=p.dtype))
+
+    def init_blocks_from_points(self, points, **kw):
+        """Starts the blocks where the cloud `points` (N,3, in the frame of the cameras) has its clusters: worldfit.blocks_from_points with
+        this model's world frame, block count, T_range, ratio_block_scene and scale_min, applied through init_blocks -> the BlockInit.  The
+        clustering runs where the points are (a cuda device: the HIP kernel)."""
+        from .worldfit import blocks_from_points
+        init = blocks_from_points(points, self.S_world, self.R_world[0], self.T_world[0], self.n_blocks, T_range=self.T_range,
+                                  ratio_block_scene=self.ratio_block_scene, scale_min=self.scale_min, **kw)
+        self.init_blocks(init.T, init.R_6d, init.S, init.index)
+        return init
+
     # ------------------------------------------------------------------------------------------------ init (dbw.py:55-119)
     def _init_blocks(self, **kwargs):
         self.n_blocks = kwargs.pop('n_blocks', 1)
@@ -86,6 +113,7 @@ class DifferentiableBlocksWorld(nn.Module):
         self.scale_min = kwargs.pop('scale_min', 0.2)
         opacity_init = kwargs.pop('opacity_init', 0.5)
         T_range = kwargs.pop('T_range', [1, 1, 1])
+        self.T_range = tuple(float(t) for t in T_range)         # (init_blocks_from_points: what counts as inside the scene)
         T_init_mode = kwargs.pop('T_init_mode', 'gauss')
         assert len(kwargs) == 0, kwargs
         N, TS = self.n_blocks, self.txt_size

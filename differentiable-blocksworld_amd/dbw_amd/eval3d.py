@@ -18,6 +18,8 @@ nearest neighbours, the DTU dense lattice and its radius downsample -- is HIP (c
     plane_ransac(points, ...)             robust plane fit: N points x H hypotheses in one call (dbw_eval_plane_fit) -> PlaneResult
     plane_ransac_torch(...)               the same fit in torch, any device; dtype=torch.float64: the oracle of the tests
     filter_ground(points, ...)            utils/ransac.py as dtu_3d_process.py:36-41 uses it           -> (points off the ground, (p0, p1, p2))
+    cluster_points(points, k, ...)        k-means with a PCA of every cluster in one call (dbw_eval_cluster_fit)  -> ClusterResult
+    cluster_points_torch(...)             the same fit in torch, any device: the CPU path and the readable restatement
 """
 import collections
 import ctypes
@@ -926,3 +928,150 @@ def filter_ground(points, thresh=VERTICAL_THRESH, n_iter=100, seed=0, batch_size
     res = plane_ransac(points, n_hyp=n_hyp, thresh=thresh, residual='vertical', refine=0, seed=seed, triples=triples, return_mask=True)
     params = torch.stack([res.offset, -res.normal[0], -res.normal[1]])
     return points[~res.mask], params
+
+
+# ------------------------------------------------------------------------------------------------ k-means with per-cluster PCA
+ClusterResult = collections.namedtuple('ClusterResult', 'centres labels counts mean cov evals axes rounds changed n_nonempty')
+ClusterResult.__doc__ = """A k-means fit, every field a tensor on the device of the points: centres (K,3) fp32, the centres the labels belong to;
+labels (N,) int32 (-1: a point with a non-finite coordinate); counts (K,) int32; mean (K,3), cov (K,6: xx xy xz yy yz zz), evals (K,3,
+descending) and axes (K,3,3: row i the unit eigenvector of evals[i], a proper rotation) fp64; rounds, changed (labels that changed in the last
+pass), n_nonempty () int32."""
+CLUSTER_MAX_K, CLUSTER_MAX_ITER = 256, 64        # csrc/cluster_math.h
+_COV_PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+
+
+def _cluster_args(points, k, n_iter, init):
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'cluster_points: points (N,3) expected, got {tuple(points.shape)}')
+    if init is not None:
+        init = torch.as_tensor(init).detach().to(device=points.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+        if init.shape[0] != int(k):
+            raise ValueError(f'cluster_points: init (k,3) = ({int(k)},3) expected, got {tuple(init.shape)}')
+    k, n_iter, N = int(k), int(n_iter), points.shape[0]
+    if not (1 <= k <= CLUSTER_MAX_K and k <= N < 2 ** 31 and 0 <= n_iter <= CLUSTER_MAX_ITER):
+        raise ValueError(f'cluster_points: 1 <= k <= {CLUSTER_MAX_K}, k <= N < 2^31 and 0 <= n_iter <= {CLUSTER_MAX_ITER} expected, got k={k}, '
+                         f'N={N}, n_iter={n_iter}')
+    return k, n_iter, init
+
+
+def _cluster_dist2(p, c):
+    d = p[:, None, :] - c[None, :, :]
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def _cluster_assign(p, finite, c, chunk):
+    """labels (N,) int64 of the fp32 points p against the centres c: the first smallest dist2, -1 for a non-finite point"""
+    out = torch.empty(p.shape[0], dtype=torch.int64, device=p.device)
+    for a in range(0, p.shape[0], chunk):
+        d2 = _cluster_dist2(p[a:a + chunk], c)
+        d2 = torch.where(d2 != d2, torch.full_like(d2, math.inf), d2)               # (a NaN distance is never the smallest)
+        m = d2.min(1, keepdim=True).values
+        ks = torch.arange(c.shape[0], device=p.device)[None].expand_as(d2)
+        out[a:a + chunk] = torch.where(d2 == m, ks, c.shape[0]).min(1).values
+    return torch.where(finite, out, torch.full_like(out, -1))
+
+
+def _cluster_moments(p, labels, c):
+    """(K,10) fp64: count, sum d, sum d d^T of every cluster about its centre"""
+    K = c.shape[0]
+    keep = labels >= 0
+    lab = labels[keep]
+    d = p[keep].to(torch.float64) - c.to(torch.float64)[lab]
+    terms = torch.cat([torch.ones_like(d[:, :1]), d] + [(d[:, a] * d[:, b])[:, None] for a, b in _COV_PAIRS], 1)
+    return torch.zeros(K, 10, dtype=torch.float64, device=p.device).index_add_(0, lab, terms)
+
+
+def _cluster_finish(sums, c):
+    n = sums[:, :1]
+    safe = n.clamp(min=1)
+    m = sums[:, 1:4] / safe
+    mean = torch.where(n > 0, c.to(torch.float64) + m, c.to(torch.float64))
+    cov = sums[:, 4:] / safe - torch.stack([m[:, a] * m[:, b] for a, b in _COV_PAIRS], 1)
+    return mean.to(torch.float32), mean, torch.where(n >= 2, cov, torch.zeros_like(cov)), n[:, 0].to(torch.int32)
+
+
+def _cluster_seed(p, finite, K):
+    """farthest-point seeding (include/dbw_eval.h) -> centres (K,3) fp32"""
+    q = p[finite]
+    if q.shape[0] == 0:
+        return torch.zeros(K, 3, dtype=torch.float32, device=p.device)
+    first = lambda hit: torch.where(hit, torch.arange(q.shape[0], device=p.device), q.shape[0]).min()       # noqa: E731
+    c = (q.to(torch.float64).sum(0) / q.shape[0]).to(torch.float32)
+    d = _cluster_dist2(q, c[None])[:, 0]
+    order = [first(d == d.min())]
+    mind = None
+    for _ in range(1, K):
+        d = _cluster_dist2(q, q[order[-1]][None])[:, 0]
+        mind = d if mind is None else torch.minimum(mind, d)
+        order.append(first(mind == mind.max()))
+    return q[torch.stack(order)]
+
+
+def _cluster_axes(cov, counts):
+    """eigenvalues (descending) and axes (rows, signed as csrc/cluster_math.h's sym3_eigen signs them) of (K,6) covariances, through eigh"""
+    C = torch.stack([cov[:, 0], cov[:, 1], cov[:, 2], cov[:, 1], cov[:, 3], cov[:, 4], cov[:, 2], cov[:, 4], cov[:, 5]], 1).reshape(-1, 3, 3)
+    w, V = torch.linalg.eigh(C.cpu())                                               # (K small matrices: the host's LAPACK)
+    w, V = w.to(cov.device).flip(1), V.to(cov.device).flip(2).transpose(1, 2)      # descending, vectors as rows
+    big = V[:, :2].abs().argmax(2, keepdim=True)
+    sign = torch.where(V[:, :2].gather(2, big) < 0, -1.0, 1.0)
+    r01 = V[:, :2] * sign
+    axes = torch.cat([r01, torch.linalg.cross(r01[:, 0], r01[:, 1])[:, None]], 1)
+    few = (counts < 2)[:, None]
+    eye = torch.eye(3, dtype=cov.dtype, device=cov.device)[None].expand_as(axes)
+    return torch.where(few, torch.zeros_like(w), w), torch.where(few[:, :, None], eye, axes)
+
+
+def cluster_points_torch(points, k, n_iter=20, init=None, chunk=1 << 16):
+    """cluster_points in torch, on any device: the readable restatement of csrc/cluster_fit.hip and the path of CPU tensors.  fp32 distances
+    in the stated order of operations, fp64 sums (index_add_: torch's order, not the kernel's -- the sums agree within the rounding of a
+    reordered fp64 sum, the labels exactly unless a centre differs in its last bit), eigh for the axes."""
+    k, n_iter, init = _cluster_args(points, k, n_iter, init)
+    p = points.detach().to(torch.float32)
+    finite = torch.isfinite(p).all(1)
+    c = _cluster_seed(p, finite, k) if init is None else init.clone()
+    prev = None
+    for r in range(n_iter + 1):
+        labels = _cluster_assign(p, finite, c, chunk)
+        changed = (labels != prev).sum() if prev is not None else torch.tensor(p.shape[0], device=p.device)
+        sums = _cluster_moments(p, labels, c)
+        new, mean, cov, counts = _cluster_finish(sums, c)
+        if r < n_iter:
+            c, prev = new, labels
+    evals, axes = _cluster_axes(cov, counts)
+    i32 = lambda v: torch.as_tensor(v, device=p.device).to(torch.int32)            # noqa: E731
+    return ClusterResult(c, labels.to(torch.int32), counts, mean, cov, evals, axes, i32(n_iter), i32(changed), i32((counts > 0).sum()))
+
+
+def cluster_fit(points, k, n_iter=20, init=None, with_labels=True):
+    """dbw_eval_cluster_fit on device tensors, arguments as in include/dbw_eval.h (points (N,3) fp32 contiguous, init (k,3) fp32 or None) ->
+    dict(centres, labels or None, counts, mean, cov, evals, axes, info (4,) int32).  Everything is enqueued on the current stream; nothing is
+    read by the host."""
+    dev, N = points.device, points.shape[0]
+    lib = _lib.family('eval')
+    nbytes = lib.dbw_eval_cluster_workspace_bytes(N, int(k))
+    if nbytes == 0:
+        raise ValueError(f'cluster_fit: sizes N={N}, K={k} are refused (1 <= K <= {CLUSTER_MAX_K}, K <= N < 2^31)')
+    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)      # noqa: E731
+    out = dict(centres=torch.empty(k, 3, dtype=torch.float32, device=dev), labels=torch.empty(N, dtype=torch.int32, device=dev) if with_labels else None,
+               counts=torch.empty(k, dtype=torch.int32, device=dev), mean=f64(k, 3), cov=f64(k, 6), evals=f64(k, 3), axes=f64(k, 3, 3),
+               info=torch.empty(4, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        _call('dbw_eval_cluster_fit', _p(points), N, int(k), _p(init), int(n_iter), _p(ws), _p(out['centres']), _p(out['labels']), _p(out['counts']),
+              _p(out['mean']), _p(out['cov']), _p(out['evals']), _p(out['axes']), _p(out['info']), _stream(dev))
+    return out
+
+
+def cluster_points(points, k, n_iter=20, init=None):
+    """k-means of a cloud (N,3) with a PCA of every cluster -> ClusterResult.  k centres: the rows of `init` (k,3), or deterministic
+    farthest-point seeding (centre 0 the point nearest the mean, centre j the point farthest from the centres before it, the lowest index on
+    ties); n_iter Lloyd rounds with no early stop, then one more pass against the final centres that gives every field.  A point with a
+    non-finite coordinate gets the label -1 and enters no sum; an empty cluster keeps its centre.
+
+    Device tensors run csrc/cluster_fit.hip in one call with no host read (the result's fields are device tensors) and give the same bytes on
+    every call; CPU tensors run cluster_points_torch."""
+    if points.device.type == 'cpu':
+        return cluster_points_torch(points, k, n_iter, init)
+    k, n_iter, init = _cluster_args(points, k, n_iter, init)
+    o = cluster_fit(points.detach().to(torch.float32).contiguous(), k, n_iter, init)
+    return ClusterResult(o['centres'], o['labels'], o['counts'], o['mean'], o['cov'], o['evals'], o['axes'], o['info'][0], o['info'][1], o['info'][2])

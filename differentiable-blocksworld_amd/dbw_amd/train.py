@@ -1,6 +1,6 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
-                          [--pose-refine LR]
+                          [--pose-refine LR] [--blocks-init points]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -21,7 +21,12 @@ model.loss.perceptual_name: ssim -- or --perceptual ssim, which overrides the co
 (metrics.SSIMTerm) and needs no file; giving the LPIPS weight files beside it is refused as a contradiction.
 
 training.pose_refine: {lr, start_epoch, rot, trans} -- or --pose-refine LR -- refines the camera poses of the training views beside the model
-(pose.py); the refined poses are written to <run_dir>/transforms_refined.json (custom captures) or poses_refined.npz at the end."""
+(pose.py); the refined poses are written to <run_dir>/transforms_refined.json (custom captures) or poses_refined.npz at the end.
+
+training.blocks_init: points -- or --blocks-init points, or the mapping {oversample, min_points, n_iter, ground_margin, extent_scale} -- on a
+custom scene with a point cloud: the blocks start at the clusters of the cloud (worldfit.blocks_from_points: k-means and a PCA of every
+cluster, on the device) and no longer at random poses; how many were seeded is printed and the poses are written to
+<run_dir>/blocks_init.yml.  A resumed or pretrained start skips the fit: the checkpoint carries the blocks."""
 import argparse
 import os
 import sys
@@ -46,6 +51,8 @@ def parse_args(argv=None):
     ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
     ap.add_argument('--pose-refine', type=float, default=None, metavar='LR',
                     help='refine the camera poses of the training views beside the model, with this learning rate (training.pose_refine.lr)')
+    ap.add_argument('--blocks-init', choices=('points',), default=None,
+                    help="'points': start the blocks at the clusters of the custom scene's point cloud (training.blocks_init)")
     ap.add_argument('--device', default='cuda:0')
     return ap.parse_args(argv)
 
@@ -75,6 +82,8 @@ def prepare_config(args):
     if getattr(args, 'pose_refine', None) is not None:
         entry = cfg.setdefault('training', {}).get('pose_refine')
         cfg['training']['pose_refine'] = dict(entry if isinstance(entry, dict) else {}, lr=args.pose_refine)
+    if getattr(args, 'blocks_init', None) is not None and not isinstance(cfg.setdefault('training', {}).get('blocks_init'), dict):
+        cfg['training']['blocks_init'] = args.blocks_init      # (a mapping in the config already asks for the points, with its options)
     return cfg
 
 
@@ -120,10 +129,60 @@ def resolve_world_frame(cfg, scene, device, run_dir=None, resume=None):
     return frame
 
 
+BLOCKS_INIT_KEYS = ('oversample', 'min_points', 'n_iter', 'ground_margin', 'extent_scale')
+
+
+def blocks_init_options(cfg):
+    """None where training.blocks_init is absent (or null / false), else the keyword arguments it gives worldfit.blocks_from_points: {} for
+    `points`, the mapping's entries for a mapping of BLOCKS_INIT_KEYS.  The key lives under `training`: model.mesh refuses keys it does not
+    know."""
+    entry = (cfg.get('training') or {}).get('blocks_init')
+    if entry is None or entry is False:
+        return None
+    if entry == 'points':
+        return {}
+    if isinstance(entry, dict):
+        bad = [k for k in entry if k not in BLOCKS_INIT_KEYS]
+        if bad:
+            raise SystemExit(f"training.blocks_init.{bad[0]}: not one of {', '.join(BLOCKS_INIT_KEYS)}")
+        return dict(entry)
+    raise SystemExit(f"training.blocks_init: '{entry}' is neither 'points' nor a mapping of {', '.join(BLOCKS_INIT_KEYS)}")
+
+
+def resolve_blocks_init(cfg, scene, model, device, run_dir=None, start=None):
+    """training.blocks_init: the blocks of `model` are started at the clusters of the scene's cloud (scene.block_init), the number seeded is
+    printed and the poses are written to <run_dir>/blocks_init.yml -> the BlockInit.  With `start` (the checkpoint of a resumed or pretrained
+    run, a path) nothing is fitted: the checkpoint carries the blocks.  A scene without a cloud is refused, and so are the DTU / BlendedMVS
+    scenes: their cloud is the ground truth the scores are computed against.
+
+    Data parallel: every rank computes the same init from the same cloud -- the fit has no random draw and adds its sums in a fixed order, so
+    the ranks start from the same bytes without a broadcast."""
+    opts = blocks_init_options(cfg)
+    if opts is None:
+        return None
+    if start is not None:
+        print(f'blocks_init: points -> skipped, {start} carries the blocks')
+        return None
+    if not hasattr(scene, 'block_init'):
+        raise SystemExit(f"training.blocks_init is for custom scenes: the cloud of a '{scene.name}' scene is the ground truth its scores are "
+                         'computed against, and the blocks must not start from it')
+    try:
+        init = scene.block_init(model, device, **opts)
+    except ValueError as e:
+        raise SystemExit(f'training.blocks_init: {e}') from e
+    print(f'blocks_init: points -> {len(init)} of {init.n_blocks} blocks seeded from {init.n_points_used} points '
+          f'(cluster sizes {[int(c) for c in init.counts.cpu().tolist()]}), the others keep their random draw')
+    if run_dir is not None:
+        with open(os.path.join(run_dir, 'blocks_init.yml'), 'w') as f:
+            f.write(init.yaml())
+    return init
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = prepare_config(args)
     wants_world_frame(cfg)                      # (a malformed entry is refused before anything is read)
+    blocks_init_options(cfg)
     from . import create_model
     from .dataset import create_train_val_test
     from .runlog import RunRecorder, resolve_start
@@ -142,6 +201,7 @@ def main(argv=None):
     train, val, test = create_train_val_test(cfg, args.data_root, args.device)
     resolve_world_frame(cfg, train, args.device, run_dir, start.get('resume'))
     model = create_model(cfg, train.img_size).to(args.device).train()
+    resolve_blocks_init(cfg, train, model, args.device, run_dir, start.get('resume') or start.get('pretrained'))
     if 'perceptual' in model.loss_weights and model.perceptual_name != 'ssim':     # (ssim: the model installed its built-in term)
         from .lpips_vgg import LPIPSVGG
         net = LPIPSVGG()

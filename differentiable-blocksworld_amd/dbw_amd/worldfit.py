@@ -137,3 +137,83 @@ def estimate_world_frame(points, cam2world, T_range=(1, 1, 1), n_hyp=512, tau_re
     S = max(0.5 * r, 1.5 * float(np.linalg.norm(C - c, axis=1).max()) / SKY_DOME)
     T = c + n * 0.9 * float(T_range[1]) * S
     return WorldFrame(S, rotation_to_euler(Rw), T.tolist(), Rw, (n, d), c, r, r0, int(got[5]), tau)
+
+
+# ------------------------------------------------------------------------------------------------ where the blocks start
+class BlockInit:
+    """Block poses read off the clusters of a cloud: T (n,3), R_6d (n,6), S (n,3) fp32 tensors for the block slots index (n,) int64 (slot i gets
+    the i-th most populous good cluster; the slots that are not in index keep their random draw), counts (n,) the points of each cluster,
+    n_points_used the points that were clustered, n_blocks the model's block count."""
+
+    def __init__(self, T, R_6d, S, index, counts, n_points_used, n_blocks):
+        self.T, self.R_6d, self.S, self.index, self.counts = T, R_6d, S, index, counts
+        self.n_points_used, self.n_blocks = int(n_points_used), int(n_blocks)
+
+    def __len__(self):
+        return int(self.index.shape[0])
+
+    def as_dict(self):
+        rows = lambda t: [[float(v) for v in r] for r in t.detach().cpu().tolist()]        # noqa: E731
+        return {'n_blocks': self.n_blocks, 'n_points_used': self.n_points_used, 'index': [int(i) for i in self.index.cpu().tolist()],
+                'counts': [int(c) for c in self.counts.cpu().tolist()], 'T': rows(self.T), 'R_6d': rows(self.R_6d), 'S': rows(self.S)}
+
+    def yaml(self):
+        """The seeded poses as YAML (flow lists): what <run_dir>/blocks_init.yml records."""
+        import yaml
+        return yaml.safe_dump(self.as_dict(), default_flow_style=None, sort_keys=False)
+
+    def __repr__(self):
+        return (f'BlockInit({len(self)} of {self.n_blocks} blocks from {self.n_points_used} points, counts='
+                f'{[int(c) for c in self.counts.cpu().tolist()]})')
+
+
+def blocks_from_points(points, S_world, R_world, T_world, n_blocks, T_range=(1, 1, 1), ratio_block_scene=0.25, scale_min=0.2, oversample=2, n_iter=20,
+                       min_points=30, ground_margin=0.05, bound=2.0, extent_scale=math.sqrt(3), size_range=None, cluster=None):
+    """Where the blocks of a model start, from the cloud `points` (N,3) of its scene (in the frame the cameras live in) -> BlockInit.  points
+    on a cuda device: the clustering is the HIP kernel (eval3d.cluster_points); on the CPU: eval3d.cluster_points_torch.
+
+    1. the model's scene frame: q = ((p - T_world) @ R_world^T) / S_world -- the model places v at (v * S_world) @ R_world + T_world; R_world is
+       the (3,3) matrix (a (1,3,3) buffer is accepted), T_world (3,) or (1,3);
+    2. the points kept: above the initial ground, q.y > -0.9 T_range[1] + ground_margin, and within |q.x| <= bound T_range[0],
+       |q.z| <= bound T_range[2], q.y <= -0.9 T_range[1] + 2 bound T_range[1]; ValueError below MIN_POINTS of them;
+    3. k-means with K' = min(oversample * n_blocks, 256, kept) centres: farthest-point seeding spends centres on stray points, and those
+       clusters stay tiny -- oversampling is the defence against outliers;
+    4. the clusters of at least min_points points, most populous first (the lower cluster index on ties), at most n_blocks: block slot i gets
+       the i-th;
+    5. T = the cluster's mean; R = its axes matrix (the model computes (v * S) @ R + T: row i of R is where block axis i points, the largest
+       extent goes to block axis 0), R_6d = mesh.matrix_to_rotation_6d(R);
+    6. the half-extent along axis i is a_i = extent_scale * sqrt(lambda_i) (a solid box, or a sphere's surface, of half-extent a has variance
+       a^2 / 3) and a block's is ratio_block_scene * (exp(S_i) + scale_min): S_i = log(clamp(a_i / ratio_block_scene, lo, hi) - scale_min) with
+       (lo, hi) = size_range or (scale_min + 0.1, 3.0).
+    The selection of step 4 reads the counts (one small host read).  cluster: the clustering function to use instead of eval3d.cluster_points
+    (same signature: the tests pass the torch path).  The fit is deterministic: the same cloud gives the same BlockInit on every call and on
+    every rank of a data-parallel run."""
+    from . import mesh
+    points = torch.as_tensor(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'blocks from points: points (N,3) expected, got {tuple(points.shape)}')
+    n_blocks = int(n_blocks)
+    if n_blocks < 1 or int(oversample) < 1:
+        raise ValueError(f'blocks from points: n_blocks >= 1 and oversample >= 1 expected, got {n_blocks}, {oversample}')
+    dev = points.device
+    Rw = torch.as_tensor(R_world).detach().to(device=dev, dtype=torch.float32).reshape(3, 3)
+    Tw = torch.as_tensor(T_world).detach().to(device=dev, dtype=torch.float32).reshape(1, 3)
+    q = ((points.detach().to(torch.float32) - Tw) @ Rw.T) / float(S_world)
+    tx, ty, tz = (float(t) for t in T_range)
+    y0 = -0.9 * ty
+    keep = (q[:, 1] > y0 + ground_margin) & (q[:, 1] <= y0 + 2 * bound * ty) & (q[:, 0].abs() <= bound * tx) & (q[:, 2].abs() <= bound * tz)
+    q = q[keep].contiguous()
+    kept = int(q.shape[0])
+    if kept < MIN_POINTS:
+        raise ValueError(f'blocks from points: at least {MIN_POINTS} points above the ground and within {bound} T_range of the scene are needed, '
+                         f'got {kept} of {points.shape[0]}')
+    K = min(int(oversample) * n_blocks, eval3d.CLUSTER_MAX_K, kept)
+    fit = (cluster or eval3d.cluster_points)(q, K, n_iter=n_iter)
+    counts = fit.counts.cpu().to(torch.int64)                                          # the one read
+    order = torch.argsort(-counts, stable=True)                                        # most populous first, the lower index on ties
+    good = order[counts[order] >= int(min_points)][:n_blocks].to(dev)
+    lo, hi = size_range if size_range is not None else (scale_min + 0.1, 3.0)
+    a = float(extent_scale) * fit.evals[good].clamp(min=0).sqrt()
+    S = ((a / float(ratio_block_scene)).clamp(float(lo), float(hi)) - float(scale_min)).log().to(torch.float32)
+    R_6d = mesh.matrix_to_rotation_6d(fit.axes[good].to(torch.float32))
+    return BlockInit(fit.mean[good].to(torch.float32), R_6d, S, torch.arange(good.shape[0], device=dev), fit.counts[good], kept, n_blocks)

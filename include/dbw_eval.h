@@ -68,6 +68,29 @@ int dbw_eval_plane_fit(const float *points, int64_t N, int H, int mode, float th
                        float cos_tilt, const float *cams, int M, float tau, int min_cams, int refine, void *workspace, double *plane,
                        int32_t *info, int32_t *counts, int32_t *triples_out, uint8_t *mask, dbw_stream_t stream);
 
+/* k-means with a PCA of every cluster (csrc/cluster_fit.hip, arithmetic csrc/cluster_math.h), added under revision 1 of this header: where the
+ * blocks of a custom scene start (dbw_amd/worldfit.py: blocks_from_points).  points (N,3) fp32, K centres.
+ *   distance    dist2 = ((dx*dx + dy*dy) + dz*dz), d = p - c, fp32, as in dbw_nn_points.  The label of a point is the k of the smallest dist2,
+ *               the lowest k on ties; a point with a non-finite coordinate gets -1 and enters no sum.
+ *   seeding     init (K,3) fp32, or (NULL) farthest-point seeding: centre 0 is the point nearest the fp32-rounded mean of the finite points,
+ *               centre j the point whose smallest dist2 to the centres 0 .. j-1 is largest, the lowest index on ties.  With fewer than K
+ *               distinct points later centres repeat earlier ones and stay empty; without a finite point every centre is zero.
+ *   rounds      n_iter Lloyd rounds, no early stop: every point is assigned and the fp64 moments of each cluster about its current centre
+ *               (count, sum d, sum d d^T) are added in a fixed order (no floating-point atomics: the same call gives the same bytes); the
+ *               centre becomes the fp64 mean rounded to fp32, an empty cluster keeps its centre.  One more pass against the final centres
+ *               gives every output.
+ * Outputs: centres (K,3) fp32, the centres the labels belong to; labels (N) int32 or NULL; counts (K) int32; mean (K,3) fp64 or NULL;
+ * cov (K,6) fp64 or NULL (xx xy xz yy yz zz about the mean; zero below two points); evals (K,3) fp64 or NULL, descending; axes (K,3,3) fp64
+ * or NULL: row i the unit eigenvector of evals[i], the largest-magnitude component of rows 0 and 1 positive (lowest index on ties), row 2 =
+ * row 0 x row 1 (identity below two points); info (4) int32 = rounds done, labels that changed in the last pass (N when it is the only
+ * one), non-empty clusters, 0.
+ * 1 <= K <= 256, K <= N < 2^31, 0 <= n_iter <= 64.  workspace: dbw_eval_cluster_workspace_bytes(N, K) bytes (0: sizes refused), 16-byte
+ * aligned. */
+size_t dbw_eval_cluster_workspace_bytes(int64_t N, int K);
+int dbw_eval_cluster_fit(const float *points, int64_t N, int K, const float *init, int n_iter, void *workspace, float *centres,
+                         int32_t *labels, int32_t *counts, double *mean, double *cov, double *evals, double *axes, int32_t *info,
+                         dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
