@@ -427,6 +427,56 @@ def normalize_poses(c2w, method='poses'):
     return c2w, F
 
 
+CLOUD_KEYS = ('source', 'unit', 'range', 'grid', 'bound', 'stride', 'edge', 'min_count')
+CLOUD_DEFAULTS = {'unit': None, 'range': (0.1, 10.0), 'grid': 128, 'bound': 2.0, 'stride': 1, 'edge': 0.05, 'min_count': 2}
+
+
+def cloud_options(cloud):
+    """The `cloud` argument of CustomScene -> None for 'file' (the capture's .ply), else the options of the depth cloud with their
+    defaults filled in: 'depth', or a mapping of CLOUD_KEYS {source: depth, unit, range, grid, bound, stride, edge, min_count}.
+    unit: metres per depth step (None: the file's depth_unit_scale_factor, else 1e-3); range: (near, far) in metres; grid: cells per axis;
+    bound: the half-size of the cube around the origin of the normalised frame that is gridded.  The default bound of 2.0 is a design
+    choice, not a measured value: the cameras are normalised into [-1, 1]^3, and what lies more than one rig extent outside them is not
+    what the plane and block fits are after.  stride: every stride-th depth row and column; edge: the relative depth jump to a
+    4-neighbour above which a sample counts as a mixed pixel and is dropped (0: off); min_count: samples a cell needs to give a point."""
+    from collections.abc import Mapping
+    if isinstance(cloud, str) and cloud == 'file':
+        return None
+    if isinstance(cloud, str) and cloud == 'depth':
+        cloud = {}
+    elif isinstance(cloud, Mapping):
+        bad = [k for k in cloud if k not in CLOUD_KEYS]
+        if bad:
+            raise ValueError(f"cloud: '{bad[0]}' is not one of {', '.join(CLOUD_KEYS)}")
+        source = cloud.get('source', 'depth')
+        if source == 'file':
+            return None
+        if source != 'depth':
+            raise ValueError(f"cloud.source: 'file' or 'depth', got {source!r}")
+    else:
+        raise ValueError(f"cloud: 'file', 'depth' or a mapping of {', '.join(CLOUD_KEYS)}, got {cloud!r}")
+    o = dict(CLOUD_DEFAULTS)
+    o.update({k: v for k, v in cloud.items() if k != 'source'})
+    o['range'] = tuple(float(v) for v in o['range'])
+    if len(o['range']) != 2 or not 0 < o['range'][0] < o['range'][1]:
+        raise ValueError(f"cloud.range: (near, far) in metres with 0 < near < far, got {o['range']}")
+    if o['unit'] is not None and not float(o['unit']) > 0:
+        raise ValueError(f"cloud.unit: metres per depth step, positive; got {o['unit']}")
+    if not float(o['bound']) > 0:
+        raise ValueError(f"cloud.bound: positive, got {o['bound']}")
+    return o
+
+
+def read_depth_png(path):
+    """A 16-bit single-channel PNG -> (H,W) uint16."""
+    from PIL import Image
+    with Image.open(path) as im:
+        a = np.asarray(im)
+    if a.ndim != 2 or a.dtype.kind not in 'iu' or int(a.min()) < 0 or int(a.max()) > 65535:
+        raise ValueError(f'{path}: a single-channel 16-bit PNG is expected, got an array of {a.dtype} {a.shape}')
+    return a.astype(np.uint16)
+
+
 class CustomScene(_Scene):
     """A capture of one's own: <root>/custom/<tag>/transforms.json -- top-level fl_x, fl_y, cx, cy, w, h, optional k1..k4, p1, p2 and
     camera_model (OPENCV or PINHOLE; a PINHOLE file's coefficients are not read), and per frame a file_path relative to the json and an
@@ -442,14 +492,22 @@ class CustomScene(_Scene):
     else the top level's; w, h must still agree) and accepts camera_model OPENCV_FISHEYE: every frame is warped from its own camera into
     ONE pinhole (ops.rectify_u8) -- intr = common_pinhole(intrs), zoomed by rectify_zoom under 'crop'; under lens='mask' at zoom 1 with
     a validity map per frame --, so K stays one matrix.  intrs (N,4), dists (N,6), models (N,) keep the frames' cameras; dist is what they
-    share, None where they differ.  'shared', the default, refuses both kinds of capture."""
+    share, None where they differ.  'shared', the default, refuses both kinds of capture.
+    cloud: where cloud(), world_frame and block_init take their points from.  'file', the default: the .ply above.
+    'depth', or a mapping (cloud_options has the keys and defaults): from the capture's depth maps -- each frame's `depth_file_path`
+    (relative to the json, a 16-bit PNG in steps of `depth_unit_scale_factor` metres, of one size that may differ from the images'; a frame
+    without one contributes nothing), every sample unprojected through the TRUE lens of its frame (also under undistort=False and under
+    cameras='shared') and its normalised pose, and reduced to one point per cell of a grid (ops.depth_cloud on a device, ops.depth_cloud_host
+    without one: the same bytes).  Every frame with a depth map contributes, whichever split it is in.  pc_gt stays the .ply: a depth
+    cloud is no ground truth."""
     name, folder = 'custom', 'custom'
 
     def __init__(self, root, tag, split, downscale_factor=1, img_size=None, undistort=True, normalize='poses', view_ids=None, store=None,
-                 masks=False, lens='crop', cameras='shared'):
+                 masks=False, lens='crop', cameras='shared', cloud='file'):
         import json
         if cameras not in ('shared', 'per_frame'):
             raise ValueError(f"cameras: 'shared' or 'per_frame', got {cameras!r}")
+        self.cloud_options = cloud_options(cloud)
         per_frame = cameras == 'per_frame'
         self.cameras = cameras
         self.split, self.tag = split, tag
@@ -586,6 +644,10 @@ class CustomScene(_Scene):
             points = np.asarray(read_ply_points(ply), dtype=np.float64)
             self.pc_gt = torch.from_numpy(points @ F[:3, :3].T + F[:3, 3]).float()
 
+        self.cloud_info, self._clouds, self._depth = None, {}, None
+        if self.cloud_options is not None:
+            self._depth = self._depth_setup(path, meta, frames, c2w, F, (h, w))
+
         if store is not None and ([str(f) for f in store.files] != [str(f) for f in self.input_files] or store.img_size != self.img_size
                                   or (store.prepare is None) != (self.prepare is None) or store.has_masks != has_masks
                                   or store.per_frame != per_frame):
@@ -598,21 +660,82 @@ class CustomScene(_Scene):
         R_world, T_world and S_world of model.mesh.  device: where the plane fit runs (a cuda device: the HIP kernel).  ValueError for a
         capture without a cloud."""
         from .worldfit import estimate_world_frame
-        if self.ply_file is None:
+        if self._depth is None and self.ply_file is None:
             raise ValueError(f"'{self.tag}': no point cloud (ply_file_path of transforms.json, or points.ply next to it): the world frame is "
                              'fitted to the cloud, there is no fit without one')
-        pts = self.pc_gt if device is None else self.pc_gt.to(device)
-        return estimate_world_frame(pts, self.cam2world, T_range=T_range, **kw)
+        return estimate_world_frame(self.cloud(device), self.cam2world, T_range=T_range, **kw)
 
     def block_init(self, model, device=None, **kw):
         """model.init_blocks_from_points on this capture's cloud (in the normalised frame R, T live in): the blocks of `model` start at the
         clusters of the cloud -> worldfit.BlockInit.  device: where the clustering runs (a cuda device: the HIP kernel).  ValueError for a
         capture without a cloud."""
-        if self.ply_file is None:
+        if self._depth is None and self.ply_file is None:
             raise ValueError(f"'{self.tag}': no point cloud (ply_file_path of transforms.json, or points.ply next to it): the blocks are "
                              'fitted to the cloud, there is no fit without one')
-        pts = self.pc_gt if device is None else self.pc_gt.to(device)
-        return model.init_blocks_from_points(pts, **kw)
+        return model.init_blocks_from_points(self.cloud(device), **kw)
+
+    def cloud(self, device=None):
+        """The points the fits use, (M,3) float32 in the normalised frame R, T live in, on `device` (None: the CPU): the .ply's under
+        cloud='file' (ValueError without one), the depth cloud under cloud='depth' -- built on first use, by the HIP kernel for a cuda
+        device and in numpy otherwise, and kept per device.  cloud_info then holds {points, samples, outside, frames}: the cells that gave a
+        point, the depth samples accumulated, those that fell outside the cube, and the frames with a depth map."""
+        if self._depth is None:
+            if self.ply_file is None:
+                raise ValueError(f"'{self.tag}': no point cloud (ply_file_path of transforms.json, or points.ply next to it)")
+            return self.pc_gt if device is None else self.pc_gt.to(device)
+        dev = None if device is None else torch.device(device)
+        host = dev is None or dev.type == 'cpu'
+        key = 'cpu' if host else str(dev)
+        if key not in self._clouds:
+            D = self._depth
+            depth = np.stack([read_depth_png(f) for f in D['files']])
+            args = (depth, D['cams'], D['target'], D['poses'], D['lo'], D['hi'])
+            kw = {k: D[k] for k in ('grid', 'd_range', 'stride', 'edge', 'min_count')}
+            if host:
+                pts, _, info = ops.depth_cloud_host(*args, return_info=True, **kw)
+                pts = torch.from_numpy(pts)
+            else:
+                pts, _, info = ops.depth_cloud(*args, device=dev, return_info=True, **kw)
+            self._clouds[key] = pts
+            self.cloud_info = {'points': info[0], 'samples': info[1], 'outside': info[2], 'frames': len(D['files'])}
+        pts = self._clouds[key]
+        return pts if device is None else pts.to(device)
+
+    def _depth_setup(self, path, meta, frames, c2w, F, size):
+        """What cloud() hands ops.depth_cloud: the depth files and, per frame that has one, the camera row at the depth maps' resolution
+        and the pose row [A, t] -- A = R_c2w . diag(1, -1, -1) * (unit * scale of F): the camera point (x right, y down, z forward, in
+        depth steps) through the OpenGL axes (x, -y, -z) of the normalised cam2world --, the common target at zoom 1, the cube and the
+        rules.  The intrinsics scale by (Wd / W, Hd / H): with pixel centres at +0.5 that is exact."""
+        from PIL import Image
+        o = self.cloud_options
+        ids = [n for n, f in enumerate(frames) if f.get('depth_file_path')]
+        if not ids:
+            raise ValueError(f"{path}: cloud='depth', but no frame has a depth_file_path")
+        files = [self._frame_file(path.parent, frames[n]['depth_file_path']) for n in ids]
+        sizes = set()
+        for f in files:
+            with Image.open(f) as im:
+                sizes.add(im.size)
+        if len(sizes) != 1:
+            raise ValueError(f'{path}: the depth maps must share one size, got {sorted(s[::-1] for s in sizes)}')
+        Wd, Hd = sizes.pop()
+        zoom = np.array([Wd / size[1], Hd / size[0]] * 2)
+        if self.cameras == 'per_frame':
+            intrs, dists, models = self.intrs[ids], self.dists[ids], self.models[ids]
+        else:
+            intrs, dists, models = np.tile(np.array(self.intr), (len(ids), 1)), np.tile(np.array(self.dist), (len(ids), 1)), np.zeros(len(ids), np.int64)
+        unit = float(o['unit'] if o['unit'] is not None else meta.get('depth_unit_scale_factor', 1e-3))
+        if not unit > 0:
+            raise ValueError(f'{path}: depth_unit_scale_factor must be positive, got {unit}')
+        scale = float(abs(np.linalg.det(F[:3, :3])) ** (1.0 / 3.0))
+        poses = np.stack([np.concatenate([(c2w[n, :3, :3] * np.array([1.0, -1.0, -1.0]) * (unit * scale)).reshape(9), c2w[n, :3, 3]]) for n in ids])
+        d_min, d_max = max(1, int(np.ceil(o['range'][0] / unit - 1e-9))), min(65535, int(np.floor(o['range'][1] / unit + 1e-9)))
+        if d_min > d_max:
+            raise ValueError(f"{path}: cloud.range {o['range']} m holds no 16-bit depth step of {unit} m")
+        return {'files': files, 'frames': ids, 'size': (Hd, Wd), 'unit': unit, 'cams': ops.lens_table(intrs * zoom, dists, models),
+                'target': ops.lens_target(np.array(self.intr) * zoom, 1.0), 'poses': poses.astype(np.float32), 'lo': -float(o['bound']),
+                'hi': float(o['bound']), 'grid': int(o['grid']), 'd_range': (d_min, d_max), 'stride': int(o['stride']), 'edge': float(o['edge']),
+                'min_count': int(o['min_count'])}
 
     @staticmethod
     def _frame_file(folder, file_path):

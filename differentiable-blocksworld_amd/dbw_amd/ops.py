@@ -9,6 +9,7 @@ Operator-level mirrors of what the reference reaches in PyTorch3D
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1149,6 +1150,181 @@ def rectify_valid_u8(H, W, table_rows, target, device='cuda'):
     if table.shape[0] > 0:
         _lib.call('dbw_lens_rectify_valid_u8', table.shape[0], H, W, table.data_ptr(), target.data_ptr(), _ptr(out), _stream(out))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the point cloud of a capture's depth maps (include/dbw_lens.h)
+# ---------------------------------------------------------------------------------------------------------------------
+DEPTH_SUB = 1024                # quantisation steps of a cell along an axis (csrc/depth_math.h: 1 << DEPTH_SUB_BITS)
+DEPTH_MAX_GRID = 256
+
+
+def depth_box(lo, hi, grid):
+    """The HOST `box` array of dbw_lens_depth_cloud, 4 fp32 [lo_x, lo_y, lo_z, inv_step] as a numpy array, from the corners lo, hi (a number
+    or 3 numbers each) of a CUBE and the cells per axis: inv_step = grid * 1024 / (hi - lo), taken in fp64 and rounded once."""
+    lo, hi = np.broadcast_to(np.asarray(lo, np.float64), (3,)), np.broadcast_to(np.asarray(hi, np.float64), (3,))
+    side = hi - lo
+    if not (np.isfinite(side).all() and side[0] > 0 and side[1] == side[0] and side[2] == side[0]):
+        raise ValueError(f'lo, hi: the corners of a cube (hi - lo the same positive number on the three axes), got {lo.tolist()} and {hi.tolist()}')
+    if not 1 <= int(grid) <= DEPTH_MAX_GRID:
+        raise ValueError(f'grid: 1 .. {DEPTH_MAX_GRID}, got {grid}')
+    return np.array([lo[0], lo[1], lo[2], int(grid) * float(DEPTH_SUB) / side[0]], dtype=np.float64).astype(np.float32)
+
+
+def _depth_args(shape, cams, target, poses, lo, hi, grid, d_range, stride, edge, min_count):
+    """The arguments the kernel and the numpy path share, checked: (cams (N,16), target (4,), poses (N,12), box (4,)) as contiguous fp32
+    numpy arrays and (G, d_min, d_max, stride, edge_permille, min_count) as ints."""
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f'depth: (N,H,W) with N, H, W >= 1, got {tuple(shape)}')
+    N = shape[0]
+    as_np = lambda a: np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
+    cams, target, poses = as_np(cams), as_np(target), as_np(poses).reshape(-1, 12)
+    if cams.shape != (N, _lib.LENS_RECT_N_PARAMS) or target.shape != (4,) or poses.shape != (N, 12):
+        raise ValueError(f'cams: ({N},{_lib.LENS_RECT_N_PARAMS}), target: (4,), poses: ({N},12); got {cams.shape}, {target.shape} and {poses.shape}')
+    box = depth_box(lo, hi, grid)
+    for name, a in (('cams', cams), ('target', target), ('poses', poses), ('box', box)):
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name}: a value that is not finite')
+    if not (box[3] > 0 and (target[2:] > 0).all() and (cams[:, 1:3] > 0).all() and np.isin(cams[:, 0], (0.0, 1.0)).all()):
+        raise ValueError('inv_step, the focal lengths and the reciprocals of the target must be positive, a model id 0 or 1')
+    d_min, d_max = int(d_range[0]), int(d_range[1])
+    permille = int(round(float(edge) * 1000))
+    stride, min_count = int(stride), int(min_count)
+    if not (1 <= d_min <= d_max <= 65535 and stride >= 1 and 0 <= permille <= 1000 and min_count >= 1):
+        raise ValueError(f'd_range: 1 <= d_min <= d_max <= 65535, stride >= 1, edge in [0, 1], min_count >= 1; got {d_range}, {stride}, {edge}, {min_count}')
+    return cams, target, poses, box, int(grid), d_min, d_max, stride, permille, min_count
+
+
+def depth_cloud(depth, cams, target, poses, lo, hi, grid=128, d_range=(1, 65535), stride=1, edge=0.0, min_count=1, device=None, return_info=False,
+                workspace=None):
+    """dbw_lens_depth_cloud: (N,H,W) 16-bit depth maps -> (points (M,3) float32, counts (M,) int32) on depth's device, one point per cell of
+    the grid^3 cells of the cube [lo, hi] that at least min_count samples fall into, in ascending cell order (csrc/depth_math.h).
+    depth: a torch.int16 tensor holding the 16 bits (or torch.uint16), or a numpy uint16 array, which is uploaded to `device` ('cuda' by
+    default).  cams (N,16) and target (4,): ops.lens_table and ops.lens_target at the depth maps' resolution; poses (N,12): rows [A, t],
+    camera (x right, y down, z forward, in depth units) to world; d_range = (d_min, d_max) in depth units; stride: every stride-th row and
+    column of the target; edge: a sample whose source pixel has a 4-neighbour that is 0 or differs by more than edge * d is dropped (0:
+    off).  The one host read is M.  return_info: also [M, samples accumulated, samples outside the box] as a list.  workspace: a uint8
+    tensor of dbw_lens_depth_cloud_workspace_bytes(grid) bytes to use instead of a fresh one (its contents do not matter: the call clears it)."""
+    lib = _lib.family('lens')
+    if isinstance(depth, np.ndarray):
+        if depth.dtype != np.uint16:
+            raise TypeError(f'depth: a numpy array of uint16, got {depth.dtype}')
+        depth = torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(device or 'cuda')
+    if depth.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)):
+        raise TypeError(f'depth: torch.int16 holding the 16 bits (or torch.uint16), got {depth.dtype}')
+    if not depth.is_cuda:
+        raise RuntimeError('depth_cloud runs on the GPU (ops.depth_cloud_host is the numpy path)')
+    depth = depth.contiguous()
+    cams, target, poses, box, G, d_min, d_max, stride, permille, min_count = _depth_args(depth.shape, cams, target, poses, lo, hi, grid, d_range,
+                                                                                        stride, edge, min_count)
+    N, H, W = depth.shape
+    samples = N * -(-H // stride) * -(-W // stride)
+    if samples >= 1 << 31:
+        raise ValueError(f'{samples} samples: below 2^31 a call')
+    capacity = min(G ** 3, samples)
+    dev = depth.device
+    need = lib.dbw_lens_depth_cloud_workspace_bytes(G)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f'workspace: a contiguous uint8 tensor of at least {need} bytes on {dev}')
+    points = torch.empty(capacity, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(capacity, dtype=torch.int32, device=dev)
+    info = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.call('dbw_lens_depth_cloud', _ptr(depth), N, H, W, cams.ctypes.data, target.ctypes.data, poses.ctypes.data, box.ctypes.data, G, d_min, d_max,
+              stride, permille, min_count, _ptr(workspace), _ptr(points), _ptr(counts), capacity, _ptr(info), _stream(depth))
+    info = [int(v) for v in info.tolist()]
+    out = (points[:info[0]], counts[:info[0]])
+    return out + (info,) if return_info else out
+
+
+def _lens_atan32(t):
+    """lens_atan of csrc/lens_math.h on a float32 array t >= 0, operation by operation."""
+    F = np.float32
+    big = t > F(2.414213562373095)
+    mid = ~big & (t > F(0.4142135623730950))
+    a = np.where(big, -(F(1.0) / t), np.where(mid, (t - F(1.0)) / (t + F(1.0)), t))
+    y0 = np.where(big, F(1.5707963267948966), np.where(mid, F(0.7853981633974483), F(0.0)))
+    z = a * a
+    q = ((F(8.05374449538e-2) * z - F(1.38776856032e-1)) * z + F(1.99777106478e-1)) * z - F(3.33329491539e-1)
+    return y0 + ((q * z) * a + a)
+
+
+def _lens_rect_source32(cam, target, i, j):
+    """lens_rect_source of csrc/lens_math.h on int arrays (i, j), operation by operation in float32 -> (x, y, u, v)."""
+    F = np.float32
+    model, fx, fy, cx, cy, k1, k2, k3, k4, p1, p2 = [F(v) for v in cam[:11]]
+    cx0, cy0, inv_fx0, inv_fy0 = [F(v) for v in target]
+    x = (j.astype(F) + F(0.5) - cx0) * inv_fx0
+    y = (i.astype(F) + F(0.5) - cy0) * inv_fy0
+    xx, yy, xy = x * x, y * y, x * y
+    r2 = xx + yy
+    if model == F(1.0):
+        r = np.sqrt(r2)
+        th = _lens_atan32(r)
+        t2 = th * th
+        td = th * (F(1.0) + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+        s = np.where(r2 == F(0.0), F(1.0), td / r)
+        return x, y, (x * s) * fx + cx - F(0.5), (y * s) * fy + cy - F(0.5)
+    d = F(1.0) + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * k4)))
+    xd = x * d + (F(2.0) * p1) * xy + p2 * (r2 + F(2.0) * xx)
+    yd = y * d + (F(2.0) * p2) * xy + p1 * (r2 + F(2.0) * yy)
+    return x, y, xd * fx + cx - F(0.5), yd * fy + cy - F(0.5)
+
+
+def depth_cloud_host(depth, cams, target, poses, lo, hi, grid=128, d_range=(1, 65535), stride=1, edge=0.0, min_count=1, return_info=False):
+    """ops.depth_cloud in numpy, for a run without a GPU: depth (N,H,W) uint16 (numpy, or a CPU tensor of int16 / uint16 bits) -> (points
+    (M,3) float32, counts (M,) int32) as numpy arrays, the same bytes as the kernel: csrc/depth_math.h operation by operation in float32,
+    the cells' counts and sums added up as integers (np.add.at), the points formed in float64 and rounded once."""
+    F = np.float32
+    if torch.is_tensor(depth):
+        depth = depth.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+    depth = np.ascontiguousarray(depth)
+    if depth.dtype != np.uint16:
+        raise TypeError(f'depth: uint16, got {depth.dtype}')
+    cams, target, poses, box, G, d_min, d_max, stride, permille, min_count = _depth_args(depth.shape, cams, target, poses, lo, hi, grid, d_range,
+                                                                                        stride, edge, min_count)
+    N, H, W = depth.shape
+    i, j = np.meshgrid(np.arange(0, H, stride), np.arange(0, W, stride), indexing='ij')
+    i, j = i.reshape(-1), j.reshape(-1)
+    count = np.zeros(G ** 3, np.uint32)
+    sums = np.zeros((3, G ** 3), np.uint64)
+    lim = F(G * DEPTH_SUB)
+    n_in = n_out = 0
+    with np.errstate(all='ignore'):
+        for n in range(N):
+            x, y, u, v = _lens_rect_source32(cams[n], target, i, j)
+            fu, fv = np.floor(u + F(0.5)), np.floor(v + F(0.5))
+            keep = (fu >= F(0.0)) & (fu <= F(W - 1)) & (fv >= F(0.0)) & (fv <= F(H - 1))                     # (False for a NaN)
+            sx, sy = np.where(keep, fu, F(0.0)).astype(np.int64), np.where(keep, fv, F(0.0)).astype(np.int64)
+            frame = depth[n].astype(np.int64)
+            d = frame[sy, sx]
+            keep &= (d >= d_min) & (d <= d_max)
+            if permille > 0:
+                for inside, ny, nx in ((sx > 0, sy, sx - 1), (sx < W - 1, sy, sx + 1), (sy > 0, sy - 1, sx), (sy < H - 1, sy + 1, sx)):
+                    nb = frame[np.clip(ny, 0, H - 1), np.clip(nx, 0, W - 1)]
+                    keep &= ~(inside & ((nb == 0) | (1000 * np.abs(d - nb) > permille * d)))
+            z = d.astype(F)
+            cx, cy = x * z, y * z
+            A = poses[n]
+            q, inside = [], keep.copy()
+            for a in range(3):
+                p = ((A[3 * a] * cx + A[3 * a + 1] * cy) + A[3 * a + 2] * z) + A[9 + a]
+                f = np.floor((p - box[a]) * box[3])
+                ok = (f >= F(0.0)) & (f < lim)                                                          # (False for a NaN)
+                inside &= ok
+                q.append(np.where(ok, f, F(0.0)).astype(np.int64))
+            n_in += int(inside.sum())
+            n_out += int((keep & ~inside).sum())
+            cell = (((q[0] >> 10) * G + (q[1] >> 10)) * G + (q[2] >> 10))[inside]
+            np.add.at(count, cell, np.uint32(1))
+            for a in range(3):
+                np.add.at(sums[a], cell, q[a][inside].astype(np.uint64))
+    rows = np.nonzero(count >= min_count)[0]
+    c = count[rows].astype(np.float64)
+    points = np.stack([box[a].astype(np.float64) + ((sums[a][rows].astype(np.float64) + 0.5 * c) / c) / np.float64(box[3]) for a in range(3)], 1)
+    out = (points.astype(F).reshape(-1, 3), count[rows].astype(np.int32))
+    return out + ([len(rows), n_in, n_out],) if return_info else out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

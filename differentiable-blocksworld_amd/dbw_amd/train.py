@@ -26,7 +26,11 @@ training.pose_refine: {lr, start_epoch, rot, trans} -- or --pose-refine LR -- re
 training.blocks_init: points -- or --blocks-init points, or the mapping {oversample, min_points, n_iter, ground_margin, extent_scale} -- on a
 custom scene with a point cloud: the blocks start at the clusters of the cloud (worldfit.blocks_from_points: k-means and a PCA of every
 cluster, on the device) and no longer at random poses; how many were seeded is printed and the poses are written to
-<run_dir>/blocks_init.yml.  A resumed or pretrained start skips the fit: the checkpoint carries the blocks."""
+<run_dir>/blocks_init.yml.  A resumed or pretrained start skips the fit: the checkpoint carries the blocks.
+
+dataset.cloud: depth -- or the mapping {source: depth, unit, range, grid, bound, stride, edge, min_count} -- on a custom scene whose frames
+ship depth maps and no .ply: the cloud both fits above use is made from the depth maps (ops.depth_cloud), its size is
+printed and it is written to <run_dir>/depth_cloud.ply."""
 import argparse
 import os
 import sys
@@ -129,6 +133,23 @@ def resolve_world_frame(cfg, scene, device, run_dir=None, resume=None):
     return frame
 
 
+def resolve_depth_cloud(scene, device, run_dir=None):
+    """dataset.cloud: depth -- the cloud of the capture's depth maps is built now (scene.cloud: the fits that follow find it cached), its size
+    is printed and, with a run directory, it is written to <run_dir>/depth_cloud.ply -> the points, or None for any other scene."""
+    if getattr(scene, 'cloud_options', None) is None:
+        return None
+    try:
+        points = scene.cloud(device)
+    except ValueError as e:
+        raise SystemExit(f'dataset.cloud: {e}') from e
+    info = scene.cloud_info
+    print(f"depth_cloud: {info['points']} points from {info['samples']} samples of {info['frames']} frames")
+    if run_dir is not None:
+        from .export import save_ply
+        save_ply(os.path.join(run_dir, 'depth_cloud.ply'), points)
+    return points
+
+
 BLOCKS_INIT_KEYS = ('oversample', 'min_points', 'n_iter', 'ground_margin', 'extent_scale')
 
 
@@ -199,6 +220,7 @@ def main(argv=None):
     seed = cfg['training'].get('seed', 4321)
     torch.manual_seed(seed)
     train, val, test = create_train_val_test(cfg, args.data_root, args.device)
+    resolve_depth_cloud(train, args.device, run_dir)
     resolve_world_frame(cfg, train, args.device, run_dir, start.get('resume'))
     model = create_model(cfg, train.img_size).to(args.device).train()
     resolve_blocks_init(cfg, train, model, args.device, run_dir, start.get('resume') or start.get('pretrained'))

@@ -100,6 +100,33 @@ int dbw_lens_pose_apply(const float *R0, const float *T0, const float *delta, co
 int dbw_lens_pose_chain(const float *R0, const float *T0, const float *delta, const int32_t *ids, int B, int V, const float *grad_R,
                         const float *grad_T, float *grad_delta, dbw_stream_t stream);
 
+/* The point cloud of a capture's depth maps, added under revision 1 of this header (csrc/depth_cloud.hip, arithmetic: csrc/depth_math.h).
+ * depth (N,H,W) uint16 on the DEVICE, at any 2-byte alignment: one depth map per frame, at the maps' own resolution.  cams (N rows of
+ * DBW_LENS_RECT_N_PARAMS floats) and target (4 floats) are the HOST arrays of dbw_lens_rectify_u8, with the intrinsics at the depth maps'
+ * resolution; poses: a HOST array of N * 12 floats, a row [A (3x3 row-major), t] per frame, camera (x right, y down, z forward, in depth
+ * units) to world: the caller folds the axis flip of its convention and the depth unit into A.  box: a HOST array of 4 floats
+ * [lo_x, lo_y, lo_z, inv_step], inv_step = G * 1024 / (hi - lo) rounded once from fp64.  The four arrays are read before the call returns
+ * and travel in the arguments of the launches, 16 frames to a launch: no allocation, no copy, no synchronisation.
+ * Target pixel (i, j) with i % stride == 0 and j % stride == 0 of frame n reads its lens map (u, v) as dbw_lens_rectify_u8 forms it and
+ * takes the NEAREST source pixel (floor(v + 0.5), floor(u + 0.5)); it is dropped where that is not finite or outside the frame, where the
+ * depth d is outside [d_min, d_max] (0 is "no measurement"), and, with edge_permille > 0, where an in-frame 4-neighbour d_nb of the source
+ * pixel is 0 or has 1000 * |d - d_nb| > edge_permille * d.  The camera point (x*z, y*z, z), z = (float)d, goes to p = A.c + t, each axis
+ * is quantised to q = floor((p - lo) * inv_step), the sample is dropped (and counted in info[2]) unless 0 <= q < G * 1024 on all axes, and
+ * its cell is ((qx >> 10) * G + (qy >> 10)) * G + (qz >> 10).  A cell adds up integers only (a 32-bit count, three 64-bit sums of q), so
+ * the result does not depend on the order of arrival: two calls give the same bytes.  Outputs on the DEVICE: points (capacity,3) fp32 and
+ * counts (capacity,) int32, one row per cell with count >= min_count in ascending cell order, point = lo + ((sum + 0.5 count) / count) /
+ * inv_step in fp64, rounded once; rows from M on are not written.  info: 3 int64 [M, samples accumulated, samples outside the box].
+ * workspace: dbw_lens_depth_cloud_workspace_bytes(G) bytes on the DEVICE, 16-byte aligned, contents irrelevant (the call clears it); the
+ * size is 0 for a G outside [1, 256], else a multiple of 16.
+ * Refused before any launch (DBW_ERR_INVALID): a null pointer; a misaligned one (workspace 16 bytes, points and counts 4, info 8, depth 2);
+ * N, H, W, stride or min_count below 1; G outside [1, 256]; d_min outside [1, d_max] or d_max above 65535; edge_permille outside
+ * [0, 1000]; N * ceil(H / stride) * ceil(W / stride) of 2^31 or more; capacity below the smaller of G^3 and that product; a value of cams,
+ * target, poses or box that is not finite, an inv_step that is not > 0, and the cameras dbw_lens_rectify_u8 refuses. */
+size_t dbw_lens_depth_cloud_workspace_bytes(int G);
+int dbw_lens_depth_cloud(const uint16_t *depth, int N, int H, int W, const float *cams, const float *target, const float *poses,
+                         const float *box, int G, int d_min, int d_max, int stride, int edge_permille, int min_count, void *workspace,
+                         float *points, int32_t *counts, int64_t capacity, int64_t *info, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
