@@ -227,12 +227,15 @@ MONITOR_SIGNATURES = {
     # the image terms under a validity mask (csrc/masked_loss.hip), added under revision 1 of the header
     'dbw_monitor_masked_composite': [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'dbw_monitor_masked_ssim_term': [c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p],
+    # the reconstruction term under a per-view exposure (csrc/exposure_loss.hip), added under revision 1 of the header
+    'dbw_monitor_exposure_composite': [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 MONITOR_OTHER_SIGNATURES = {
     'dbw_image_scores_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
     'dbw_monitor_ssim_term_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
     'dbw_monitor_masked_composite_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
     'dbw_monitor_masked_ssim_term_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'dbw_monitor_exposure_composite_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
 }
 METER_MAX_VALUES = 16                                         # DBW_METER_MAX_VALUES of include/dbw_monitor.h
 MONITOR_ABI_VERSION = header_define('dbw_monitor.h', 'DBW_MONITOR_ABI_VERSION')

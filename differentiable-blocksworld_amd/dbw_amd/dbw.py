@@ -626,6 +626,20 @@ class DifferentiableBlocksWorld(nn.Module):
             self.build_env_scene()
             self.build_blocks_scene(filter_transparent=not self.is_live('coarse_learning'))
             return self.compute_losses(inp['imgs'], None, layers=None)
+        if 'exposure' in inp:
+            # per-view exposure compensation: the fused epilogue stands aside as it does for masks, the layers are rendered
+            # and both image terms see rec = exp(g) * composite + b; validity masks combine with it
+            refusal = self._exposure_refusal()
+            if refusal is not None:
+                raise NotImplementedError(f'a batch with exposure: {refusal}')
+            if 'view_ids' not in inp:
+                raise KeyError("a batch with 'exposure' carries 'view_ids', the rows of theta of its views")
+            masks, count = inp.get('masks'), None
+            if masks is not None:
+                count = 3.0 * float(inp['mask_sum'] if 'mask_sum' in inp else masks.sum(dtype=torch.float64))      # (one host read without it)
+            fg, env = self.render_layers(inp)
+            return self.compute_losses(inp['imgs'], None, layers=(fg, env), masks=masks, mask_count=count,
+                                       exposure=(inp['exposure'], inp['view_ids'], inp.get('view_ids_host')))
         if 'masks' in inp:
             # validity masks: the fused epilogue stands aside, the layers are rendered and both image terms take the masks
             refusal = self._mask_refusal()
@@ -651,6 +665,16 @@ class DifferentiableBlocksWorld(nn.Module):
             return f'criteria {self.criterion_name} / {self.tv_type}: the masked kernels have mse and l2sq, with an rgb term'
         if self.world_size > 1:
             return 'data-parallel training needs a global valid count, which is not implemented'
+        return None
+
+    def _exposure_refusal(self):
+        """-> why this model cannot take a batch with per-view exposures, or None."""
+        if not self.decouple_rendering:
+            return 'decouple_rendering is off: the compensated reconstruction term is the decoupled composite'
+        if 'rgb' not in self.loss_weights or not self.default_criteria:
+            return f'criteria {self.criterion_name} / {self.tv_type}: the exposure kernel has mse and l2sq, with an rgb term'
+        if self.world_size > 1:
+            return 'data-parallel training: the exposure gradients are per view and the ranks do not exchange them'
         return None
 
     def _forward_fused(self, inp):
@@ -845,23 +869,36 @@ class DifferentiableBlocksWorld(nn.Module):
             value = self.perceptual_fn(imgs, rec)
         return self.loss_weights['perceptual'] * phase.late_factor(coarse) * share * value
 
-    def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None):
+    def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
         """masks (B,1,H,W) weights in [0, 1] with mask_count = 3 * their sum (a host number; computed with one host read when None): the
-        two image terms under the validity mask -- layers must be given --, the regularisers unchanged."""
+        two image terms under the validity mask -- layers must be given --, the regularisers unchanged.
+        exposure = (theta (V,6), ids (B)[, ids on the host]): the per-view exposures of DESIGN.md 6s and the batch's rows of them -- both
+        image terms see rec = exp(g) * composite + b (ops.composite_mse_exposure), with or without masks; layers must be given; the
+        regularisers do not see theta."""
         w = self.loss_weights
         dev = imgs.device
         # (the epoch's loss factors in eval mode too; view-independent regularisers: every rank computes them identically, scaled by
         # 1 / world_size so that the sum all-reduce of gradients counts them once, SURVEY.md 8e)
         ph = phase.phase_of(self, self.training)
         coarse, rs, ws = ph.coarse_epoch, ph.rs, self.world_size
-        if masks is not None:
-            refusal = self._mask_refusal() or (None if layers is not None else 'compute_losses needs the rendered layers')
+        if masks is not None or exposure is not None:
+            what, refusal = 'masks', None if masks is None else self._mask_refusal()
+            if refusal is None and exposure is not None:
+                what, refusal = 'exposure', self._exposure_refusal()
+            refusal = refusal or (None if layers is not None else 'compute_losses needs the rendered layers')
             if refusal is not None:
-                raise NotImplementedError(f'a batch with masks: {refusal}')
-            count = ops.mask_count(masks) if mask_count is None else float(mask_count)
+                raise NotImplementedError(f'a batch with {what}: {refusal}')
+            if masks is None:
+                count = float(imgs.numel() if getattr(self, '_global_count', None) is None else self._global_count)
+            else:
+                count = ops.mask_count(masks) if mask_count is None else float(mask_count)
             # composite + masked MSE as one node with two outputs (its backward: one launch fed by the gradients of both), the regularisers
             # through the regularisers-only form of ops.fused_losses, the perceptual term on the node's rec
-            rgb, rec = ops.composite_mse_masked(layers[0], layers[1], imgs, masks, ph.w_rgb, count)
+            if exposure is not None:
+                rgb, rec = ops.composite_mse_exposure(layers[0], layers[1], imgs, masks, ph.w_rgb, count, exposure[0], exposure[1],
+                                                      ids_host=exposure[2] if len(exposure) > 2 else None)
+            else:
+                rgb, rec = ops.composite_mse_masked(layers[0], layers[1], imgs, masks, ph.w_rgb, count)
             cfg = {'rgb': None, 'count': count, 'parsimony': ph.w_parsimony, 'tv': ph.w_tv, 'tv_ground_factor': ph.tv_factor,
                    'overlap': ph.w_overlap, 'overlap_consts': (float(self.ratio_block_scene), float(self.scale_min), OVERLAP_TEMPERATURE, OVERLAP_N_BLOCKS)}
             u = None

@@ -1589,6 +1589,116 @@ def composite_mse_masked(fg, env, imgs, masks, weight, count):
     return _CompositeMSEMasked.apply(fg, env, imgs, masks, float(weight) / count if count > 0 else 0.0)
 
 
+class _CompositeMSEExposure(torch.autograd.Function):
+    """(weight * sum masks (rec - imgs)^2 / count, rec) with rec = exp(g) * composite + b under the per-view exposure theta
+    as ONE node with two outputs: the forward is dbw_monitor_exposure_composite (rec and the fp64 value), the backward its image launch
+    and its finishing launch, fed by both incoming gradients; fg, env and theta receive gradients."""
+
+    @staticmethod
+    def forward(ctx, fg, env, imgs, masks, theta, ids, scale):
+        value, rec, saved = exposure_composite_fwd(fg.detach(), env.detach(), imgs, masks, theta.detach(), ids, scale)
+        ctx.set_materialize_grads(False)             # an output nobody used arrives as None, not as an image of zeros to read
+        ctx.has_masks = masks is not None
+        ctx.save_for_backward(*[t for t in saved if t is not None])
+        ctx.scale = scale
+        return value[0].to(torch.float32), rec
+
+    @staticmethod
+    def backward(ctx, g_value, g_rec):
+        saved = list(ctx.saved_tensors)
+        fg, env, imgs = saved[:3]
+        masks = saved[3] if ctx.has_masks else None
+        theta, ids = saved[-2:]
+        up = (g_value.detach().to(torch.float32).reshape(1).contiguous() if g_value is not None
+              else torch.zeros(1, dtype=torch.float32, device=fg.device))
+        g_fg, g_env, g_theta = exposure_composite_bwd(fg, env, imgs, masks, theta, ids, ctx.scale, up, None if g_rec is None else g_rec.detach())
+        return g_fg, g_env, None, None, g_theta, None, None
+
+
+def _exposure_args(fg, env, imgs, masks, theta, ids):
+    fg_c, env_c, imgs_c = _chk(fg, torch.float32, 'fg'), _chk(env, torch.float32, 'env'), _chk(imgs, torch.float32, 'imgs')
+    masks_c = None if masks is None else _chk(masks, torch.float32, 'masks')
+    theta_c, ids_c = _chk(theta, torch.float32, 'theta'), _chk(ids, torch.int32, 'ids')
+    if fg_c.dim() != 4:
+        raise ValueError(f'fg: (N,4,H,W), got {tuple(fg_c.shape)}')
+    N, _, H, W = fg_c.shape
+    if (tuple(fg_c.shape) != (N, 4, H, W) or fg_c.shape != env_c.shape or tuple(imgs_c.shape) != (N, 3, H, W)
+            or (masks_c is not None and tuple(masks_c.shape) != (N, 1, H, W))):
+        raise ValueError(f'fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) or None; got {tuple(fg_c.shape)}, {tuple(env_c.shape)}, '
+                         f'{tuple(imgs_c.shape)}, {None if masks_c is None else tuple(masks_c.shape)}')
+    if theta_c.dim() != 2 or theta_c.shape[1] != 6 or theta_c.shape[0] < 1 or tuple(ids_c.shape) != (N,):
+        raise ValueError(f'theta (V,6) with V >= 1, ids ({N},); got {tuple(theta_c.shape)}, {tuple(ids_c.shape)}')
+    return fg_c, env_c, imgs_c, masks_c, theta_c, ids_c
+
+
+def exposure_composite_fwd(fg, env, imgs, masks, theta, ids, scale):
+    """The forward of dbw_monitor_exposure_composite as it stands: fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) or None, theta (V,6)
+    fp32 and ids (N,) int32 on the GPU, scale = weight / count a host number -> (value (1,) fp64 = scale * sum masks (rec - imgs)^2,
+    rec (N,3,H,W) = exp(g) * composite + b, the inputs as the kernel read them).  Two launches on the current stream, no host read."""
+    lib = _monitor_lib()
+    fg_c, env_c, imgs_c, masks_c, theta_c, ids_c = _exposure_args(fg, env, imgs, masks, theta, ids)
+    N, _, H, W = fg_c.shape
+    dev = fg_c.device
+    rec = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+    value = torch.zeros(1, dtype=torch.float64, device=dev)
+    if N > 0:
+        ws = torch.empty(lib.dbw_monitor_exposure_composite_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
+        _lib.call('dbw_monitor_exposure_composite', _ptr(fg_c), _ptr(env_c), _ptr(imgs_c), _ptr(masks_c), _ptr(theta_c), _ptr(ids_c), N, H, W,
+                  theta_c.shape[0], float(scale), _ptr(ws), _ptr(rec), _ptr(value), 0, 0, 0, 0, 0, _stream(fg_c))
+    return value, rec, (fg_c, env_c, imgs_c, masks_c, theta_c, ids_c)
+
+
+def exposure_composite_bwd(fg, env, imgs, masks, theta, ids, scale, upstream, grad_rec=None, grad_theta=None):
+    """The backward of dbw_monitor_exposure_composite as it stands, two launches: upstream (1,) fp32 on the GPU -- the gradient with
+    respect to the value --, grad_rec (N,3,H,W) or None -- the gradient with respect to rec -- -> (grad_fg, grad_env (N,4,H,W), grad_theta
+    (V,6)).  grad_theta given: the rows ids of it are ADDED to, the others left alone; None: a table of zeros is made."""
+    lib = _monitor_lib()
+    fg, env, imgs, masks, theta, ids = _exposure_args(fg, env, imgs, masks, theta, ids)
+    N, _, H, W = fg.shape
+    up = _chk(upstream, torch.float32, 'upstream')
+    g_rec = None if grad_rec is None else _chk(grad_rec, torch.float32, 'grad_rec')
+    if up.numel() != 1 or (g_rec is not None and tuple(g_rec.shape) != (N, 3, H, W)):
+        raise ValueError('upstream: one fp32, grad_rec: (N,3,H,W)')
+    if grad_theta is None:
+        grad_theta = torch.zeros_like(theta)
+    elif grad_theta.shape != theta.shape or grad_theta.dtype != torch.float32 or not grad_theta.is_contiguous() or not grad_theta.is_cuda:
+        raise ValueError(f'grad_theta: a contiguous fp32 table of theta\'s shape {tuple(theta.shape)} on the GPU')
+    g_fg, g_env = torch.empty_like(fg), torch.empty_like(env)
+    if N > 0:
+        ws = torch.empty(lib.dbw_monitor_exposure_composite_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=fg.device)
+        _lib.call('dbw_monitor_exposure_composite', _ptr(fg), _ptr(env), _ptr(imgs), _ptr(masks), _ptr(theta), _ptr(ids), N, H, W, theta.shape[0],
+                  float(scale), _ptr(ws), 0, 0, _ptr(up), _ptr(g_rec), _ptr(g_fg), _ptr(g_env), _ptr(grad_theta), _stream(fg))
+    return g_fg, g_env, grad_theta
+
+
+def _exposure_ids(ids, N, V, ids_host=None):
+    """The batch's rows of theta as a contiguous int32 tensor.  Where the caller holds the same ids on the host (ids_host; the Trainer
+    draws them there) they are checked without a wait for the device: distinct, inside [0, V).  Without ids_host nothing is read back:
+    the kernels treat an id outside the table as theta = 0 and skip its gradient row."""
+    if ids.numel() != N:
+        raise ValueError(f'ids: one per view of the batch ({N}), got {ids.numel()}')
+    if ids_host is not None:
+        host = [int(i) for i in torch.as_tensor(ids_host).reshape(-1).tolist()]
+        if len(host) != N:
+            raise ValueError(f'ids_host: one per view of the batch ({N}), got {len(host)}')
+        if len(set(host)) != len(host):
+            raise ValueError(f'composite_mse_exposure: the view ids of a batch must be distinct, got {host}')
+        if host and (min(host) < 0 or max(host) >= V):
+            raise ValueError(f'composite_mse_exposure: view ids outside [0, {V}): {host}')
+    return ids.reshape(-1).to(torch.int32).contiguous()
+
+
+def composite_mse_exposure(fg, env, imgs, masks, weight, count, theta, ids, ids_host=None):
+    """fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) weights in [0, 1] or None (= ones), count = 3 * sum(masks) -- imgs.numel() without
+    masks -- of the GLOBAL batch as a host number, theta (V,6) the per-view exposures, ids (N) the batch's rows of theta,
+    distinct -> (weight * sum masks (rec - imgs)^2 / count: a scalar, 0 for count == 0; rec (N,3,H,W) = exp(g) * composite + b).  Both
+    outputs are differentiable in fg, env and theta; one image launch and one finishing launch compute the gradients of whatever was
+    built on the two.  ids_host: the same ids on the host, where the caller has them; the caller GUARANTEES that the two are equal."""
+    count = float(count)
+    ids = _exposure_ids(ids, fg.shape[0], theta.shape[0], ids_host).to(fg.device)
+    return _CompositeMSEExposure.apply(fg, env, imgs, masks, theta, ids, float(weight) / count if count > 0 else 0.0)
+
+
 def composite(fg, env):
     """rec = fg_rgb*mask + (1-mask)*env_rgb as an image (API-compat path for predict(); HIP forward, elementwise torch
     backward -- the training path uses composite_mse)."""

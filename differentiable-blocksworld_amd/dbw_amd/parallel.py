@@ -137,7 +137,12 @@ class ShardedTrainStep:
         if posed and self.world_size > 1:
             raise NotImplementedError('camera pose refinement under data parallelism: the pose gradients are per view and the ranks do not '
                                       'exchange them')
-        masked = masked or posed
+        # ... and a batch with per-view exposures (exposure.ExposureRefiner.attach): the term is ops.composite_mse_exposure's
+        exposed = 'exposure' in inp
+        if exposed and self.world_size > 1:
+            raise NotImplementedError('exposure compensation under data parallelism: the exposure gradients are per view and the ranks do '
+                                      'not exchange them')
+        masked = masked or posed or exposed
         self.model._global_count = self._global_count(inp['imgs'], global_count)
         dirty = None
         if (self.cstep is not None and self.model.training and inp['imgs'].shape[0] > 0 and self._fused_adam() and self.cstep.supported()

@@ -1,6 +1,6 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
-                          [--pose-refine LR] [--blocks-init points]
+                          [--pose-refine LR] [--blocks-init points] [--exposure LR]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -22,6 +22,10 @@ model.loss.perceptual_name: ssim -- or --perceptual ssim, which overrides the co
 
 training.pose_refine: {lr, start_epoch, rot, trans} -- or --pose-refine LR -- refines the camera poses of the training views beside the model
 (pose.py); the refined poses are written to <run_dir>/transforms_refined.json (custom captures) or poses_refined.npz at the end.
+
+training.exposure: {lr, start_epoch, bias, center} -- or --exposure LR -- fits a gain and an offset per colour channel and training view beside
+the model (exposure.py): both image terms see exp(g) * render + b; the fitted values are written to <run_dir>/exposures.tsv at
+the end, and the evaluation renders stay at the canonical exposure.
 
 training.blocks_init: points -- or --blocks-init points, or the mapping {oversample, min_points, n_iter, ground_margin, extent_scale} -- on a
 custom scene with a point cloud: the blocks start at the clusters of the cloud (worldfit.blocks_from_points: k-means and a PCA of every
@@ -55,6 +59,8 @@ def parse_args(argv=None):
     ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
     ap.add_argument('--pose-refine', type=float, default=None, metavar='LR',
                     help='refine the camera poses of the training views beside the model, with this learning rate (training.pose_refine.lr)')
+    ap.add_argument('--exposure', type=float, default=None, metavar='LR',
+                    help='fit a per-view exposure (gain and offset per channel) beside the model, with this learning rate (training.exposure.lr)')
     ap.add_argument('--blocks-init', choices=('points',), default=None,
                     help="'points': start the blocks at the clusters of the custom scene's point cloud (training.blocks_init)")
     ap.add_argument('--device', default='cuda:0')
@@ -86,6 +92,9 @@ def prepare_config(args):
     if getattr(args, 'pose_refine', None) is not None:
         entry = cfg.setdefault('training', {}).get('pose_refine')
         cfg['training']['pose_refine'] = dict(entry if isinstance(entry, dict) else {}, lr=args.pose_refine)
+    if getattr(args, 'exposure', None) is not None:
+        entry = cfg.setdefault('training', {}).get('exposure')
+        cfg['training']['exposure'] = dict(entry if isinstance(entry, dict) else {}, lr=args.exposure)
     if getattr(args, 'blocks_init', None) is not None and not isinstance(cfg.setdefault('training', {}).get('blocks_init'), dict):
         cfg['training']['blocks_init'] = args.blocks_init      # (a mapping in the config already asks for the points, with its options)
     return cfg

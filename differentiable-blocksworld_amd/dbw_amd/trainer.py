@@ -136,6 +136,19 @@ class Trainer:
             self.pose = PoseRefiner(self.local['imgs'].shape[0], self.local['imgs'].device, lr=self.pose_cfg['lr'],
                                     betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))), rot=self.pose_cfg['rot'],
                                     trans=self.pose_cfg['trans'])
+        # Per-view exposure compensation (training.exposure: {lr, start_epoch, bias, center}; exposure.py): absent -> nothing
+        # is built and no batch changes.  Present -> batches carry view_ids and, from start_epoch on, 'exposure' = theta; the refiner's
+        # Adam step follows the model's.
+        self.exposure, self.exposure_cfg = None, None
+        from .exposure import ExposureRefiner, parse_config as parse_exposure
+        self.exposure_cfg = parse_exposure(tr.get('exposure'))
+        if self.exposure_cfg is not None:
+            if ws > 1:
+                raise NotImplementedError('training.exposure under data parallelism: the exposure gradients are per view and the ranks do '
+                                          'not exchange them')
+            self.exposure = ExposureRefiner(self.local['imgs'].shape[0], self.local['imgs'].device, lr=self.exposure_cfg['lr'],
+                                            betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))), bias=self.exposure_cfg['bias'],
+                                            center=self.exposure_cfg['center'])
         # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
         # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
         self.mask_sums = None
@@ -149,7 +162,7 @@ class Trainer:
                 fn.cache_targets(self._perceptual_targets())
                 self.view_ids = True
         self._cached_targets = self.view_ids        # (view_ids may also be on for the pose refiner alone: no cache to keep then)
-        self.view_ids = self.view_ids or self.pose is not None
+        self.view_ids = self.view_ids or self.pose is not None or self.exposure is not None
 
     def _perceptual_targets(self):
         """What a caching criterion keeps the features of: this rank's images, times their masks where the views have them (the model calls
@@ -203,16 +216,21 @@ class Trainer:
             batch = {k: v[idx] for k, v in self.local.items()}
             if self.view_ids:
                 batch['view_ids'] = idx
-            if self.pose is not None:
-                batch['view_ids_host'] = ids                      # (the refiner checks the ids without waiting for the device)
+            if self.pose is not None or self.exposure is not None:
+                batch['view_ids_host'] = ids                      # (the refiners check the ids without waiting for the device)
             if self.mask_sums is not None:
                 batch['mask_sum'] = float(self.mask_sums[ids].sum())
             refine = self.pose is not None and self.epoch >= self.pose_cfg['start_epoch'] and idx.numel() > 0
             if refine:
                 batch = self.pose.apply(batch)
+            expose = self.exposure is not None and self.epoch >= self.exposure_cfg['start_epoch'] and idx.numel() > 0
+            if expose:
+                batch = self.exposure.attach(batch)
             last, _ = self.run_single_batch_train(batch, self.global_count(b))
             if refine:
                 self.pose.step()
+            if expose:
+                self.exposure.step()
             n_img += idx.numel()
             if rec is not None:
                 rec.after_step(self.epoch, b + 1, last, ids)
@@ -272,6 +290,10 @@ class Trainer:
                 write_refined(self.scene, self.pose, run_dir, self.local['R'], self.local['T'])
             if getattr(loader, 'dataset', None) is not None and loader.dataset is self.scene:
                 loader = _RefinedLoader(loader, *self.pose.refined(self.local['R'], self.local['T']))      # the training views: at their refined poses
+        if self.exposure is not None:
+            # (the renders below stay uncompensated, at the canonical exposure: a held-out view has no fitted row)
+            from .exposure import write_exposures
+            write_exposures(self.exposure, run_dir)
         self.model.qualitative_eval(loader, device, path=os.path.join(run_dir, 'quali_eval'), **({'parse': True} if parse else {}))
         scores = self.model.quantitative_eval(loader, device, hard_inference=True)
         with open(os.path.join(run_dir, 'final_scores.tsv'), mode='w') as f:
@@ -324,7 +346,8 @@ class Trainer:
                 'model_state': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
                 'optimizer_state': {'exp_avg': self.step_fn.exp_avg.clone(), 'exp_avg_sq': self.step_fn.exp_avg_sq.clone(),
                                     'n_steps': self.step_fn.n_steps},
-                'scheduler_state': self.scheduler.state_dict(), **({} if self.pose is None else {'pose_refine': self.pose.state_dict()})}
+                'scheduler_state': self.scheduler.state_dict(), **({} if self.pose is None else {'pose_refine': self.pose.state_dict()}),
+                **({} if self.exposure is None else {'exposure': self.exposure.state_dict()})}
 
     def load_state_dict(self, ckpt):
         self.model.load_state_dict(ckpt['model_state'])
@@ -341,3 +364,5 @@ class Trainer:
         self.model.set_cur_epoch(ckpt['epoch'])
         if self.pose is not None and 'pose_refine' in ckpt:
             self.pose.load_state_dict(ckpt['pose_refine'])
+        if self.exposure is not None and 'exposure' in ckpt:
+            self.exposure.load_state_dict(ckpt['exposure'])

@@ -98,6 +98,37 @@ size_t dbw_monitor_masked_ssim_term_workspace_bytes(int N, int H, int W);
 int dbw_monitor_masked_ssim_term(const float *target, const float *rec, const float *masks, int N, int H, int W, double count, void *workspace,
                                  float *grad, double *value, dbw_stream_t stream);
 
+/* The reconstruction term under a per-view exposure (csrc/exposure_loss.hip), added under revision 1 of this header.
+ * theta (V,6) fp32: one row (g_r, g_g, g_b, b_r, b_g, b_b) per training view of the scene; ids (N) int32: the batch's rows of theta,
+ * distinct.  With comp = fg_rgb * fg_a + (1 - fg_a) * env_rgb, the composite of dbw_composite_mse,
+ *   rec_c = exp(g_c) * comp_c + b_c        (no clamp; theta = 0: rec is the composite bit for bit)
+ * An id outside [0, V) reads as theta = 0 and its row of grad_theta is skipped: no access outside theta or grad_theta.
+ *
+ * Bytes of `workspace` that dbw_monitor_exposure_composite needs, forward or backward (six fp64 per workgroup); 0 for sizes it refuses
+ * and for N = 0. */
+size_t dbw_monitor_exposure_composite_workspace_bytes(int N, int H, int W);
+
+/* fg, env (N,4,H,W), imgs (N,3,H,W) fp32; masks (N,1,H,W) fp32 weights in [0, 1] or NULL = ones; scale = w_rgb / count from the host.
+ * Forward (grad_fg == grad_env == grad_theta == NULL): writes rec (N,3,H,W) and value[0] = scale * sum of masks * (rec - imgs)^2 as one
+ *   fp64 on the device, through per-workgroup fp64 partials in `workspace` added in index order by a second launch.  upstream and
+ *   grad_rec must be NULL.
+ * Backward (grad_fg, grad_env (N,4,H,W) and grad_theta (V,6) given; rec, value NULL): one image launch and one finishing launch.
+ *   upstream: one fp32 on the device, the gradient g of the loss with respect to value; grad_rec: (N,3,H,W) or NULL, the gradient with
+ *   respect to rec that other terms send.  rec is formed again from fg, env and theta; per pixel and channel
+ *     d'_c = (2 scale g) masks (rec_c - imgs_c) + grad_rec_c,        d_c = exp(g_c) d'_c,
+ *   grad_fg = [d * fg_a (3 channels), sum_c d_c (fg_c - env_c)], grad_env = [d * (1 - fg_a), 0] are WRITTEN, and the six sums of a view
+ *     sum_p d'_c exp(g_c) comp_c   (c = r, g, b),      sum_p d'_c   (c = r, g, b)
+ *   are ADDED to row ids[n] of grad_theta; the other rows are not touched (csrc/exposure_math.h).  A workgroup belongs to one view; the
+ *   sums are reduced in fp64 in the lane, the wave and the workgroup, the workgroups' partials of a view added in a fixed order by one
+ *   workgroup of the finishing launch.
+ * No floating-point atomics: two calls on the same inputs give the same bytes.  Rows whose W is a multiple of 4 and whose image pointers
+ * are all 16-byte aligned move as 16-byte loads and stores; any other shape element by element, same results.  value and workspace:
+ * 8-byte aligned.  N = 0: nothing is launched.  N <= 65535, V >= 1, H * W < 2^31. */
+int dbw_monitor_exposure_composite(const float *fg, const float *env, const float *imgs, const float *masks, const float *theta,
+                                   const int32_t *ids, int N, int H, int W, int V, double scale, void *workspace, float *rec, double *value,
+                                   const float *upstream, const float *grad_rec, float *grad_fg, float *grad_env, float *grad_theta,
+                                   dbw_stream_t stream);
+
 /* table: n + 2 doubles on the device; vals: HOST array of n <= DBW_METER_MAX_VALUES DEVICE pointers, each to one fp32.  One kernel:
  *   table[i] += (double)*vals[i] * weight  (i < n),   table[n] += weight,
  *   table[n + 1] = step if it is negative and any *vals[i] is not finite (the first such step stays). */
