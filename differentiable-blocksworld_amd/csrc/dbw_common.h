@@ -406,3 +406,7 @@ int dbw_check_launch(const char *what);
         }                                               \
     } while (0)
 static inline unsigned dbw_xcd_grid(long long total) { return (unsigned)(8 * ((total + 7) / 8)); }
+namespace dbw {
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }       // (a null pointer is aligned)
+static inline bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
+}  // namespace dbw

@@ -6,27 +6,25 @@
 // so a workgroup never straddles two views.  theta and the id of the workgroup's view are read once per workgroup (thread 0..5 into LDS,
 // the gains exponentiated there); an id outside [0, V) reads as theta = 0 and its gradient row is skipped.
 //
-// Forward: rec and one fp64 partial per workgroup (lane sums in fp64, the wave through fixed-order butterflies, the waves in wave order),
-// added in a fixed order by a second launch of one workgroup.  Backward: one image launch -- rec formed again from fg, env and theta,
+// Forward: rec and one fp64 partial per workgroup (lane sums in fp64, then loss_reduce.h: block_sums), added in a fixed order by a second
+// launch of one workgroup (partials_finish_kernel).  Backward: one image launch -- rec formed again from fg, env and theta,
 // grad_fg and grad_env written through the composite, the six per-view sums reduced in the lane, the wave and the workgroup to six fp64
 // partials -- and one finishing launch, a workgroup per view that adds the view's partials in a fixed order (thread t those of the
 // workgroups t, t + 256, ... in index order, then wave and workgroup as above) and adds the result to the row ids[n] of grad_theta.
 // No floating-point atomics: two calls on the same inputs give the same bytes.
 #include "dbw_common.h"
 #include "exposure_math.h"
+#include "loss_reduce.h"
 #include "../../include/dbw_monitor.h"
 
 namespace {
 
 using namespace dbw;
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / DBW_WAVE;
+constexpr int THREADS = LOSS_THREADS;
+constexpr int WAVES = LOSS_WAVES;
 constexpr int VIEW_MAX_BLOCKS = 256;                // workgroups per view, grid-stride within the view beyond that
 constexpr int MAX_VIEWS = 65535;                    // grid y
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
 
 struct ExpArgs {
     const float *fg, *env, *img, *msk, *theta, *grad_rec, *upstream;
@@ -38,48 +36,10 @@ struct ExpArgs {
     int V;
 };
 
-template <int PX>
-__device__ __forceinline__ void load_px(const float *p, float v[PX]) {
-    if constexpr (PX == 4) {
-        const float4 t = *(const float4 *)p;
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int PX>
-__device__ __forceinline__ void store_px(float *p, const float v[PX]) {
-    if constexpr (PX == 4) *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-
 int view_blocks(int H, int W, bool vec) {
     const long long units = (long long)H * W / (vec ? 4 : 1);
     const long long b = (units + THREADS - 1) / THREADS;
     return (int)(b < VIEW_MAX_BLOCKS ? b : VIEW_MAX_BLOCKS);
-}
-
-// NS sums of the workgroup: the wave through fixed-order butterflies, the waves in wave order; thread k < NS leaves with sum k
-template <int NS>
-__device__ __forceinline__ double block_sums(double (&s)[NS], double (*red)[NS]) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off, DBW_WAVE);
-    }
-    if ((tid & (DBW_WAVE - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) red[tid / DBW_WAVE][k] = s[k];
-    }
-    __syncthreads();
-    double t = 0.0;
-    if (tid < NS) {
-        t = red[0][tid];
-        for (int w = 1; w < WAVES; ++w) t += red[w][tid];
-    }
-    return t;
 }
 
 template <bool VEC, bool BWD>
@@ -107,25 +67,13 @@ __global__ void __launch_bounds__(THREADS) exposure_composite_kernel(ExpArgs A) 
     for (int k = 0; k < NS; ++k) part[k] = 0.0;
     for (long long u = (long long)blockIdx.x * THREADS + threadIdx.x; u < A.units; u += (long long)gridDim.x * THREADS) {
         const long long p = u * PX;                                        // (VEC: W % 4 == 0, the four pixels lie in one row)
-        const float *f = A.fg + n * 4 * plane + p, *e = A.env + n * 4 * plane + p, *t = A.img + n * 3 * plane + p;
         float fc[3][PX], ec[3][PX], tc[3][PX], xc[3][PX], al[PX], mk[PX];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            load_px<PX>(f + c * plane, fc[c]);
-            load_px<PX>(e + c * plane, ec[c]);
-            load_px<PX>(t + c * plane, tc[c]);
-#pragma unroll
-            for (int k = 0; k < PX; ++k) xc[c][k] = 0.f;
-            if (has_extra) load_px<PX>(A.grad_rec + n * 3 * plane + c * plane + p, xc[c]);
-        }
-        load_px<PX>(f + 3 * plane, al);
-#pragma unroll
-        for (int k = 0; k < PX; ++k) mk[k] = 1.f;
-        if (has_mask) load_px<PX>(A.msk + n * plane + p, mk);
+        load_layers_px<PX>(A.fg, A.env, A.img, A.grad_rec, A.msk, has_extra, has_mask, n, p, plane, fc, ec, tc, xc, al, mk);
         float rc[3][PX], gf[4][PX], ge[4][PX];
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
-            const float f3[3] = {fc[0][k], fc[1][k], fc[2][k]}, e3[3] = {ec[0][k], ec[1][k], ec[2][k]}, t3[3] = {tc[0][k], tc[1][k], tc[2][k]};
+            const float f3[3] = {fc[0][k], fc[1][k], fc[2][k]}, e3[3] = {ec[0][k], ec[1][k], ec[2][k]};
+            const float t3[3] = {tc[0][k], tc[1][k], tc[2][k]};
             if constexpr (BWD) {
                 const float x3[3] = {xc[0][k], xc[1][k], xc[2][k]};
                 float gf3[3], ge3[3], galpha, s6[6];
@@ -143,11 +91,7 @@ __global__ void __launch_bounds__(THREADS) exposure_composite_kernel(ExpArgs A) 
             }
         }
         if constexpr (BWD) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                store_px<PX>(A.gfg + n * 4 * plane + c * plane + p, gf[c]);
-                store_px<PX>(A.genv + n * 4 * plane + c * plane + p, ge[c]);
-            }
+            store_layer_grads_px<PX>(A.gfg, A.genv, n, p, plane, gf, ge);
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) store_px<PX>(A.rec + n * 3 * plane + c * plane + p, rc[c]);
@@ -155,16 +99,6 @@ __global__ void __launch_bounds__(THREADS) exposure_composite_kernel(ExpArgs A) 
     }
     const double total = block_sums<NS>(part, red);
     if (threadIdx.x < NS) A.partial[(n * gridDim.x + blockIdx.x) * NS + threadIdx.x] = total;
-}
-
-// value[0] = (the partials added in a fixed order) * mul: thread t adds t, t + 256, ... in index order
-__global__ void __launch_bounds__(THREADS) exposure_value_kernel(const double *__restrict__ partial, long long count, double mul,
-                                                                 double *__restrict__ value) {
-    __shared__ double red[WAVES][1];
-    double s[1] = {0.0};
-    for (long long i = threadIdx.x; i < count; i += THREADS) s[0] += partial[i];
-    const double t = block_sums<1>(s, red);
-    if (threadIdx.x == 0) value[0] = t * mul;
 }
 
 // a workgroup per view n of the batch: thread t takes the partials of the view's workgroups t, t + 256, ... in index order, the workgroup
@@ -230,6 +164,5 @@ extern "C" int dbw_monitor_exposure_composite(const float *fg, const float *env,
     else hipLaunchKernelGGL((exposure_composite_kernel<false, false>), g, b, 0, s, A);
     const int rc = dbw_check_launch("exposure_composite_kernel");
     if (rc != DBW_OK) return rc;
-    hipLaunchKernelGGL(exposure_value_kernel, dim3(1), b, 0, s, (const double *)workspace, (long long)N * blocks, scale, value);
-    return dbw_check_launch("exposure_value_kernel");
+    return partials_finish((const double *)workspace, (long long)N * blocks, scale, 1.0, value, s);
 }

@@ -110,8 +110,6 @@ __global__ void __launch_bounds__(256) frames_u8_kernel(FrameArgs A, long long g
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int dbw_export_abi_version(void) { return DBW_EXPORT_ABI_VERSION; }      // (history: include/dbw_export.h)

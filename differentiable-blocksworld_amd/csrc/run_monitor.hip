@@ -162,8 +162,6 @@ __global__ void __launch_bounds__(DBW_WAVE) meter_reset_kernel(double *__restric
     if (i == n + 1) table[i] = -1.0;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // -> the number of workgroups (0: refused), the output size and the tile counts
 long long score_tiles(int N, int H, int W, int padding, int *Hp, int *Wp, int *tiles_x, int *tiles_y) {
     if (N < 0 || H <= 0 || W <= 0 || (padding != 0 && padding != 1) || (long long)H * W >= (1LL << 31)) return 0;

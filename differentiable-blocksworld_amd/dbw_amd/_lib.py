@@ -224,7 +224,7 @@ MONITOR_SIGNATURES = {
     'dbw_meter_reset': [c_p, c_i, c_p],
     # SSIM as a loss term (csrc/ssim_term.hip), added under revision 1 of the header
     'dbw_monitor_ssim_term': [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
-    # the image terms under a validity mask (csrc/masked_loss.hip), added under revision 1 of the header
+    # the image terms under a validity mask (csrc/masked_loss.hip, csrc/ssim_term.hip), added under revision 1 of the header
     'dbw_monitor_masked_composite': [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'dbw_monitor_masked_ssim_term': [c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p, c_p],
     # the reconstruction term under a per-view exposure (csrc/exposure_loss.hip), added under revision 1 of the header

@@ -868,38 +868,31 @@ def image_scores(a, b, padding=False, return_map=False):
     return res + (m,) if return_map else res
 
 
-def ssim_term_value_grad(imgs, rec, with_grad=True):
-    """dbw_monitor_ssim_term as it stands: imgs, rec (N,3,H,W) fp32 contiguous on the GPU, N > 0 -> (value (1,) fp64 = mean(1 - SSIM) with
-    zero padding, d value / d rec (N,3,H,W) fp32 -- None without with_grad).  Two launches on the current stream, no host read."""
+def _ssim_term_call(imgs, rec, masks, count, with_grad):
+    """dbw_monitor_ssim_term (masks None) or dbw_monitor_masked_ssim_term: the checks, the outputs, the workspace and the call."""
     lib = _monitor_lib()
     a_c, b_c = _chk(imgs, torch.float32, 'imgs'), _chk(rec, torch.float32, 'rec')
     if a_c.dim() != 4 or a_c.shape[1] != 3 or a_c.shape != b_c.shape or a_c.shape[0] == 0:
         raise ValueError(f'imgs, rec: two (N,3,H,W) tensors, N > 0, got {tuple(a_c.shape)} and {tuple(b_c.shape)}')
     N, _, H, W = a_c.shape
+    name, m_args, c_args = 'dbw_monitor_ssim_term', (), ()
+    if masks is not None:
+        m_c = _chk(masks, torch.float32, 'masks')
+        if tuple(m_c.shape) != (N, 1, H, W):
+            raise ValueError(f'masks: {(N, 1, H, W)}, got {tuple(m_c.shape)}')
+        name, m_args, c_args = 'dbw_monitor_masked_ssim_term', (_ptr(m_c),), (float(count),)
     dev = a_c.device
     value = torch.empty(1, dtype=torch.float64, device=dev)
     grad = torch.empty_like(b_c) if with_grad else None
-    ws = torch.empty(lib.dbw_monitor_ssim_term_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
-    _lib.call('dbw_monitor_ssim_term', _ptr(a_c), _ptr(b_c), N, H, W, _ptr(ws), _ptr(grad), _ptr(value), _stream(a_c))
+    ws = torch.empty(getattr(lib, name + '_workspace_bytes')(N, H, W) // 8, dtype=torch.float64, device=dev)
+    _lib.call(name, _ptr(a_c), _ptr(b_c), *m_args, N, H, W, *c_args, _ptr(ws), _ptr(grad), _ptr(value), _stream(a_c))
     return value, grad
 
 
-class _SsimTerm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, imgs, rec):
-        value, grad = ssim_term_value_grad(imgs, rec.detach(), with_grad=ctx.needs_input_grad[1])
-        ctx.save_for_backward(grad)
-        return value[0].to(rec.dtype)
-
-    @staticmethod
-    def backward(ctx, g):
-        grad, = ctx.saved_tensors
-        return None, grad * g
-
-
-def _ssim_term_kernel_ok(imgs, rec):
-    return (imgs.is_cuda and rec.is_cuda and imgs.dtype == rec.dtype == torch.float32 and imgs.is_contiguous() and rec.is_contiguous()
-            and not imgs.requires_grad and imgs.dim() == 4 and imgs.shape == rec.shape and imgs.shape[1] == 3 and imgs.numel() > 0)
+def ssim_term_value_grad(imgs, rec, with_grad=True):
+    """dbw_monitor_ssim_term as it stands: imgs, rec (N,3,H,W) fp32 contiguous on the GPU, N > 0 -> (value (1,) fp64 = mean(1 - SSIM) with
+    zero padding, d value / d rec (N,3,H,W) fp32 -- None without with_grad).  Two launches on the current stream, no host read."""
+    return _ssim_term_call(imgs, rec, None, None, with_grad)
 
 
 def mask_count(masks):
@@ -911,26 +904,20 @@ def masked_ssim_term_value_grad(imgs, rec, masks, count, with_grad=True):
     """dbw_monitor_masked_ssim_term as it stands: imgs, rec (N,3,H,W), masks (N,1,H,W) fp32 contiguous on the GPU, N > 0, count a host
     number -> (value (1,) fp64 = sum masks (1 - SSIM(masks imgs, masks rec)) / count, d value / d rec (N,3,H,W) fp32 -- None without
     with_grad).  Two launches on the current stream, no host read."""
-    lib = _monitor_lib()
-    a_c, b_c, m_c = _chk(imgs, torch.float32, 'imgs'), _chk(rec, torch.float32, 'rec'), _chk(masks, torch.float32, 'masks')
-    if a_c.dim() != 4 or a_c.shape[1] != 3 or a_c.shape != b_c.shape or a_c.shape[0] == 0:
-        raise ValueError(f'imgs, rec: two (N,3,H,W) tensors, N > 0, got {tuple(a_c.shape)} and {tuple(b_c.shape)}')
-    N, _, H, W = a_c.shape
-    if tuple(m_c.shape) != (N, 1, H, W):
-        raise ValueError(f'masks: {(N, 1, H, W)}, got {tuple(m_c.shape)}')
-    dev = a_c.device
-    value = torch.empty(1, dtype=torch.float64, device=dev)
-    grad = torch.empty_like(b_c) if with_grad else None
-    ws = torch.empty(lib.dbw_monitor_masked_ssim_term_workspace_bytes(N, H, W) // 8, dtype=torch.float64, device=dev)
-    _lib.call('dbw_monitor_masked_ssim_term', _ptr(a_c), _ptr(b_c), _ptr(m_c), N, H, W, float(count), _ptr(ws), _ptr(grad), _ptr(value),
-              _stream(a_c))
-    return value, grad
+    return _ssim_term_call(imgs, rec, masks, count, with_grad)
 
 
-class _MaskedSsimTerm(torch.autograd.Function):
+class _SsimTerm(torch.autograd.Function):
+    """The term as one node, plain (masks None) or under the mask: the forward leaves the gradient beside the value where rec requires
+    one, the backward scales it by the incoming scalar."""
+
     @staticmethod
-    def forward(ctx, imgs, rec, masks, count):
-        value, grad = masked_ssim_term_value_grad(imgs, rec.detach(), masks, count, with_grad=ctx.needs_input_grad[1])
+    def forward(ctx, imgs, rec, masks=None, count=None):
+        with_grad = ctx.needs_input_grad[1]
+        if masks is None:
+            value, grad = ssim_term_value_grad(imgs, rec.detach(), with_grad=with_grad)
+        else:
+            value, grad = masked_ssim_term_value_grad(imgs, rec.detach(), masks, count, with_grad=with_grad)
         ctx.save_for_backward(grad)
         return value[0].to(rec.dtype)
 
@@ -938,6 +925,11 @@ class _MaskedSsimTerm(torch.autograd.Function):
     def backward(ctx, g):
         grad, = ctx.saved_tensors
         return None, grad * g, None, None
+
+
+def _ssim_term_kernel_ok(imgs, rec):
+    return (imgs.is_cuda and rec.is_cuda and imgs.dtype == rec.dtype == torch.float32 and imgs.is_contiguous() and rec.is_contiguous()
+            and not imgs.requires_grad and imgs.dim() == 4 and imgs.shape == rec.shape and imgs.shape[1] == 3 and imgs.numel() > 0)
 
 
 def ssim_term(imgs, rec, masks=None, count=None):
@@ -956,7 +948,7 @@ def ssim_term(imgs, rec, masks=None, count=None):
         count = float(count)
         if (_ssim_term_kernel_ok(imgs, rec) and masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
                 and not masks.requires_grad and tuple(masks.shape) == (imgs.shape[0], 1) + tuple(imgs.shape[2:])):
-            return _MaskedSsimTerm.apply(imgs, rec, masks, count)
+            return _SsimTerm.apply(imgs, rec, masks, count)
         from .metrics import ssim_map as _ssim_map
         if imgs.dim() != 4 or imgs.shape != rec.shape or masks.dim() != 4:
             raise ValueError(f'imgs, rec: two (N,C,H,W) tensors, masks (N,1,H,W); got {tuple(imgs.shape)}, {tuple(rec.shape)}, {tuple(masks.shape)}')
@@ -1519,6 +1511,37 @@ def composite_mse(fg, env, imgs, count=None):
     return _CompositeMSE.apply(fg, env, imgs, count)
 
 
+def _upstream_scalar(g_value, device):
+    """The gradient with respect to a composite's value as (1,) fp32 on the device; zero where nobody used the value."""
+    if g_value is None:
+        return torch.zeros(1, dtype=torch.float32, device=device)
+    return g_value.detach().to(torch.float32).reshape(1).contiguous()
+
+
+def _layer_args(fg, env, imgs, masks):
+    """fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) or None, fp32 on the GPU -> the four, contiguous."""
+    fg_c, env_c, imgs_c = _chk(fg, torch.float32, 'fg'), _chk(env, torch.float32, 'env'), _chk(imgs, torch.float32, 'imgs')
+    masks_c = None if masks is None else _chk(masks, torch.float32, 'masks')
+    if fg_c.dim() != 4:
+        raise ValueError(f'fg: (N,4,H,W), got {tuple(fg_c.shape)}')
+    N, _, H, W = fg_c.shape
+    if (tuple(fg_c.shape) != (N, 4, H, W) or fg_c.shape != env_c.shape or tuple(imgs_c.shape) != (N, 3, H, W)
+            or (masks_c is not None and tuple(masks_c.shape) != (N, 1, H, W))):
+        raise ValueError(f'fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W); got {tuple(fg_c.shape)}, {tuple(env_c.shape)}, '
+                         f'{tuple(imgs_c.shape)}, {None if masks_c is None else tuple(masks_c.shape)}')
+    return fg_c, env_c, imgs_c, masks_c
+
+
+def _grad_args(upstream, grad_rec, fg):
+    """upstream: one fp32 on the GPU, grad_rec: (N,3,H,W) for fg (N,4,H,W), or None -> the two, contiguous."""
+    N, _, H, W = fg.shape
+    up = _chk(upstream, torch.float32, 'upstream')
+    g_rec = None if grad_rec is None else _chk(grad_rec, torch.float32, 'grad_rec')
+    if up.numel() != 1 or (g_rec is not None and tuple(g_rec.shape) != (N, 3, H, W)):
+        raise ValueError('upstream: one fp32, grad_rec: (N,3,H,W)')
+    return up, g_rec
+
+
 class _CompositeMSEMasked(torch.autograd.Function):
     """(weight * sum masks (rec - imgs)^2 / count, rec) of the decoupled composite as ONE node with two outputs: the forward is
     dbw_monitor_masked_composite (rec and the fp64 value, fixed-order reduction), the backward ONE launch of it fed by both incoming
@@ -1535,9 +1558,8 @@ class _CompositeMSEMasked(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_value, g_rec):
         fg, env, imgs, masks = ctx.saved_tensors
-        up = (g_value.detach().to(torch.float32).reshape(1).contiguous() if g_value is not None
-              else torch.zeros(1, dtype=torch.float32, device=fg.device))
-        g_fg, g_env = masked_composite_bwd(fg, env, imgs, masks, ctx.scale, up, None if g_rec is None else g_rec.detach())
+        g_fg, g_env = masked_composite_bwd(fg, env, imgs, masks, ctx.scale, _upstream_scalar(g_value, fg.device),
+                                           None if g_rec is None else g_rec.detach())
         return g_fg, g_env, None, None, None
 
 
@@ -1546,14 +1568,8 @@ def masked_composite_fwd(fg, env, imgs, masks, scale):
     scale = weight / count a host number -> (value (1,) fp64 = scale * sum masks (rec - imgs)^2, rec (N,3,H,W), the four inputs as the
     kernel read them).  Two launches on the current stream, no host read."""
     lib = _monitor_lib()
-    fg_c, env_c = _chk(fg, torch.float32, 'fg'), _chk(env, torch.float32, 'env')
-    imgs_c, masks_c = _chk(imgs, torch.float32, 'imgs'), _chk(masks, torch.float32, 'masks')
-    if fg_c.dim() != 4:
-        raise ValueError(f'fg: (N,4,H,W), got {tuple(fg_c.shape)}')
+    fg_c, env_c, imgs_c, masks_c = _layer_args(fg, env, imgs, masks)
     N, _, H, W = fg_c.shape
-    if tuple(fg_c.shape) != (N, 4, H, W) or fg_c.shape != env_c.shape or tuple(imgs_c.shape) != (N, 3, H, W) or tuple(masks_c.shape) != (N, 1, H, W):
-        raise ValueError(f'fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W); got {tuple(fg_c.shape)}, {tuple(env_c.shape)}, '
-                         f'{tuple(imgs_c.shape)}, {tuple(masks_c.shape)}')
     dev = fg_c.device
     rec = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
     value = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -1570,10 +1586,7 @@ def masked_composite_bwd(fg, env, imgs, masks, scale, upstream, grad_rec=None):
     _monitor_lib()
     fg, env, imgs, masks = (_chk(t, torch.float32, n) for t, n in ((fg, 'fg'), (env, 'env'), (imgs, 'imgs'), (masks, 'masks')))
     N, _, H, W = fg.shape
-    up = _chk(upstream, torch.float32, 'upstream')
-    g_rec = None if grad_rec is None else _chk(grad_rec, torch.float32, 'grad_rec')
-    if up.numel() != 1 or (g_rec is not None and tuple(g_rec.shape) != (N, 3, H, W)):
-        raise ValueError('upstream: one fp32, grad_rec: (N,3,H,W)')
+    up, g_rec = _grad_args(upstream, grad_rec, fg)
     g_fg, g_env = torch.empty_like(fg), torch.empty_like(env)
     if N > 0:
         _lib.call('dbw_monitor_masked_composite', _ptr(fg), _ptr(env), _ptr(imgs), _ptr(masks), N, H, W, float(scale), 0, 0, 0, _ptr(up),
@@ -1609,23 +1622,15 @@ class _CompositeMSEExposure(torch.autograd.Function):
         fg, env, imgs = saved[:3]
         masks = saved[3] if ctx.has_masks else None
         theta, ids = saved[-2:]
-        up = (g_value.detach().to(torch.float32).reshape(1).contiguous() if g_value is not None
-              else torch.zeros(1, dtype=torch.float32, device=fg.device))
-        g_fg, g_env, g_theta = exposure_composite_bwd(fg, env, imgs, masks, theta, ids, ctx.scale, up, None if g_rec is None else g_rec.detach())
+        g_fg, g_env, g_theta = exposure_composite_bwd(fg, env, imgs, masks, theta, ids, ctx.scale, _upstream_scalar(g_value, fg.device),
+                                                      None if g_rec is None else g_rec.detach())
         return g_fg, g_env, None, None, g_theta, None, None
 
 
 def _exposure_args(fg, env, imgs, masks, theta, ids):
-    fg_c, env_c, imgs_c = _chk(fg, torch.float32, 'fg'), _chk(env, torch.float32, 'env'), _chk(imgs, torch.float32, 'imgs')
-    masks_c = None if masks is None else _chk(masks, torch.float32, 'masks')
+    fg_c, env_c, imgs_c, masks_c = _layer_args(fg, env, imgs, masks)
     theta_c, ids_c = _chk(theta, torch.float32, 'theta'), _chk(ids, torch.int32, 'ids')
-    if fg_c.dim() != 4:
-        raise ValueError(f'fg: (N,4,H,W), got {tuple(fg_c.shape)}')
-    N, _, H, W = fg_c.shape
-    if (tuple(fg_c.shape) != (N, 4, H, W) or fg_c.shape != env_c.shape or tuple(imgs_c.shape) != (N, 3, H, W)
-            or (masks_c is not None and tuple(masks_c.shape) != (N, 1, H, W))):
-        raise ValueError(f'fg, env (N,4,H,W), imgs (N,3,H,W), masks (N,1,H,W) or None; got {tuple(fg_c.shape)}, {tuple(env_c.shape)}, '
-                         f'{tuple(imgs_c.shape)}, {None if masks_c is None else tuple(masks_c.shape)}')
+    N = fg_c.shape[0]
     if theta_c.dim() != 2 or theta_c.shape[1] != 6 or theta_c.shape[0] < 1 or tuple(ids_c.shape) != (N,):
         raise ValueError(f'theta (V,6) with V >= 1, ids ({N},); got {tuple(theta_c.shape)}, {tuple(ids_c.shape)}')
     return fg_c, env_c, imgs_c, masks_c, theta_c, ids_c
@@ -1655,10 +1660,7 @@ def exposure_composite_bwd(fg, env, imgs, masks, theta, ids, scale, upstream, gr
     lib = _monitor_lib()
     fg, env, imgs, masks, theta, ids = _exposure_args(fg, env, imgs, masks, theta, ids)
     N, _, H, W = fg.shape
-    up = _chk(upstream, torch.float32, 'upstream')
-    g_rec = None if grad_rec is None else _chk(grad_rec, torch.float32, 'grad_rec')
-    if up.numel() != 1 or (g_rec is not None and tuple(g_rec.shape) != (N, 3, H, W)):
-        raise ValueError('upstream: one fp32, grad_rec: (N,3,H,W)')
+    up, g_rec = _grad_args(upstream, grad_rec, fg)
     if grad_theta is None:
         grad_theta = torch.zeros_like(theta)
     elif grad_theta.shape != theta.shape or grad_theta.dtype != torch.float32 or not grad_theta.is_contiguous() or not grad_theta.is_cuda:

@@ -1,6 +1,6 @@
 """Checker side: the host builds of the shared host+device headers of csrc/.  host_lib('icp_math') is tests/host_icp_math.cpp compiled by
-g++ into tests/_build/libhost_icp_math.so and loaded; it is compiled again whenever the .cpp or ANY header of csrc/ is newer than the .so
-(the headers include one another: every *_math.h includes raster_math.h, icp_math.h includes model_math.h), so no caller lists headers."""
+g++ into tests/_build/libhost_icp_math.so and loaded; it is compiled again whenever the .cpp or ANY header of csrc/ or of tests/ is newer
+than the .so (the headers include one another: every *_math.h includes raster_math.h, icp_math.h includes model_math.h), so no caller lists headers."""
 import ctypes
 import glob
 import os
@@ -13,7 +13,7 @@ _LIBS = {}
 
 def host_lib(stem):
     src, so = os.path.join(HERE, f'host_{stem}.cpp'), os.path.join(HERE, '_build', f'libhost_{stem}.so')
-    stale = not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in [src] + glob.glob(os.path.join(CSRC, '*.h')))
+    stale = not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in [src] + glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(HERE, '*.h')))
     if stale:
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', src, '-o', so])

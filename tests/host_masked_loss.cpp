@@ -1,9 +1,9 @@
-// Host build (g++) of the arithmetic of csrc/masked_loss.hip and of dbw_lens_valid_u8 for tests/test_host_masked_loss.py and the GPU tests:
-// the inline functions the kernels compile (csrc/loss_math.h: masked_composite_pixel; csrc/score_math.h: ssim_stats, ssim_filter,
-// ssim_deriv, ssim_loss_pixel, ssim_grad_pixel; csrc/lens_math.h: lens_valid), driven plane by plane and pixel by pixel.  Every window and
-// every gradient element sees the kernel's operations in the kernel's order, so rec and the gradients are the kernels' bit for bit; the
-// values are added in index order here, per lane and workgroup there.  With -DMASKED_LOSS_MAIN the file is a program of its own, for a
-// run under the sanitizers.
+// Host build (g++) of the arithmetic of the masked image terms (csrc/masked_loss.hip, csrc/ssim_term.hip) and of dbw_lens_valid_u8 for
+// tests/test_host_masked_loss.py and the GPU tests: the inline functions the kernels compile (csrc/loss_math.h: masked_composite_pixel;
+// csrc/score_math.h: ssim_stats, ssim_filter, ssim_deriv, ssim_loss_pixel, ssim_grad_pixel; csrc/lens_math.h: lens_valid), driven plane by
+// plane (tests/host_ssim_model.h) and pixel by pixel.  Every window and every gradient element sees the kernel's operations in the
+// kernel's order, so rec and the gradients are the kernels' bit for bit; the values are added in index order here, per lane and
+// workgroup there.  With -DMASKED_LOSS_MAIN the file is a program of its own, for a run under the sanitizers.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -11,26 +11,9 @@
 
 #include "../differentiable-blocksworld_amd/csrc/lens_math.h"
 #include "../differentiable-blocksworld_amd/csrc/loss_math.h"
-#include "../differentiable-blocksworld_amd/csrc/score_math.h"
+#include "host_ssim_model.h"
 
 using namespace dbw;
-
-namespace {
-
-// x (H,W) -> out (H,W): the zero-padded 11-tap filter along the rows (axis = 0) or the columns (axis = 1)
-void blur_axis(const SsimWindow &win, const float *x, int H, int W, int axis, float *out) {
-    for (int y = 0; y < H; ++y)
-        for (int xx = 0; xx < W; ++xx) {
-            float t[SSIM_TAPS];
-            for (int k = 0; k < SSIM_TAPS; ++k) {
-                const int yi = axis ? y - SSIM_TAPS / 2 + k : y, xi = axis ? xx : xx - SSIM_TAPS / 2 + k;
-                t[k] = yi >= 0 && yi < H && xi >= 0 && xi < W ? x[(size_t)yi * W + xi] : 0.f;
-            }
-            out[(size_t)y * W + xx] = ssim_filter(win.w, t);
-        }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -39,36 +22,7 @@ extern "C" {
 int host_masked_ssim_term(const float *a, const float *b, const float *msk, int N, int H, int W, double count, float *grad, double *value) {
     if (!a || !b || !msk || !value || N < 0 || H <= 0 || W <= 0 || !(count >= 0.0)) return -1;
     if (N == 0) return 0;
-    const SsimWindow win = ssim_window();
-    const size_t P = (size_t)H * W;
-    const double scale = count > 0.0 ? -1.0 / count : 0.0;
-    std::vector<float> ta(P), tb(P), stat(P), rows(P), m5(5 * P), d(3 * P), f(3 * P);
-    double sum = 0.0;
-    for (int plane = 0; plane < N * 3; ++plane) {
-        const float *pa = a + plane * P, *pb = b + plane * P, *pm = msk + (plane / 3) * P;
-        for (size_t i = 0; i < P; ++i) { ta[i] = pa[i] * pm[i]; tb[i] = pb[i] * pm[i]; }
-        for (int j = 0; j < 5; ++j) {
-            for (size_t i = 0; i < P; ++i) {
-                float s[5];
-                ssim_stats(ta[i], tb[i], s);
-                stat[i] = s[j];
-            }
-            blur_axis(win, stat.data(), H, W, 0, rows.data());
-            blur_axis(win, rows.data(), H, W, 1, m5.data() + j * P);
-        }
-        for (size_t i = 0; i < P; ++i) {
-            const float m[5] = {m5[i], m5[P + i], m5[2 * P + i], m5[3 * P + i], m5[4 * P + i]};
-            const SsimDeriv r = ssim_deriv(m);
-            d[i] = r.A * pm[i]; d[P + i] = r.B * pm[i]; d[2 * P + i] = r.C * pm[i];
-            sum += (double)pm[i] * ssim_loss_pixel(m);
-        }
-        if (!grad) continue;
-        for (int j = 0; j < 3; ++j) {
-            blur_axis(win, d.data() + j * P, H, W, 0, rows.data());
-            blur_axis(win, rows.data(), H, W, 1, f.data() + j * P);
-        }
-        for (size_t i = 0; i < P; ++i) grad[plane * P + i] = ssim_grad_pixel(f[i], f[P + i], f[2 * P + i], ta[i], tb[i], scale) * pm[i];
-    }
+    const double sum = host_ssim_planes<true>(a, b, msk, N, H, W, count > 0.0 ? -1.0 / count : 0.0, grad, nullptr);
     value[0] = count > 0.0 ? sum / count : 0.0;
     return 0;
 }

@@ -1,4 +1,4 @@
-"""Checker side of the masked image terms (csrc/masked_loss.hip, ops.composite_mse_masked, ops.ssim_term(masks=)): the arithmetic built for
+"""Checker side of the masked image terms (csrc/masked_loss.hip, csrc/ssim_term.hip, ops.composite_mse_masked, ops.ssim_term(masks=)): the arithmetic built for
 the host with g++ (tests/host_masked_loss.cpp), the float64 oracles, the inputs and the bars that tests/test_host_masked_loss.py (CPU) and
 tests/test_gpu_masked_loss.py hold values and gradients to.
 

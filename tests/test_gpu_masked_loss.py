@@ -1,5 +1,5 @@
 """GPU tests of the masked image terms: dbw_monitor_masked_composite and dbw_monitor_masked_ssim_term
-(csrc/masked_loss.hip) and the model, the step and the trainer with a batch that carries masks.
+(csrc/masked_loss.hip, csrc/ssim_term.hip) and the model, the step and the trainer with a batch that carries masks.
 
 Kernels.  The cases of tests/test_host_masked_loss.py -- ssim_term_ref.SHAPES x {noise, equal, black} x the masks {ones, holes, fraction,
 ring, empty}; for the composite the same masks on the same shapes and on 3x40x100, where more than one workgroup feeds the fixed-order sum

@@ -8,7 +8,9 @@ constant-block pair of tests/golden/ssim_term.npz.  Oracle: metrics.ssim_map(pad
 1e-6 * max(max|g64|, 1/M) (gradient).  Both errors are printed per case (profiles/ssim_term.md keeps a copy).  The gradient is the host
 build's (tests/host_ssim_term.cpp) bit for bit.
 
-Properties: two calls give the same bits; a null gradient gives the same value bits; the Function's backward scales by the incoming scalar;
+Properties: two calls give the same bits; a null gradient gives the same value bits; inputs 4 bytes off the 16-byte grid (the element-load
+instantiations) give the bits of the aligned call, for the plain and for the masked entry point; the Function's backward scales by the
+incoming scalar;
 imgs gets no gradient; the value is 1 - image_scores(padding=True) within 1e-6; what the kernel does not take goes through the torch formula.
 
 Model (the geometry of smoke(): 2 views of 32 x 48, 3 blocks, 4 faces per pixel, perceptual_name: ssim, perceptual_weight: 0.1): the loss
@@ -22,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import masked_loss_ref as MR
 import oracle as O
 import ssim_term_ref as TR
 import dbw_amd
@@ -55,6 +58,27 @@ def test_value_and_gradient_against_fp64(kind, shape):
     assert abs(value.item() - (1 - s.mean().item())) < 1e-6
     if kind == 'equal':
         assert value.item() == 0.0 and not grad.any()
+
+
+@pytest.mark.parametrize('shape', [(2, 16, 32), (1, 48, 96)], ids=lambda s: f'{s[0]}x3x{s[1]}x{s[2]}')
+def test_element_loads_give_the_bits_of_16_byte_loads(shape):
+    """W % 4 == 0: the aligned call takes the 16-byte loads, the same images 4 bytes off the grid the element loads.  The same tiles, the
+    same operations in the same order: the same gradient and value bits, with and without a gradient, plain and under a mask."""
+    a, b = (t.to(DEV) for t in TR.pair('noise', shape))
+    m = MR.mask('fraction', shape).to(DEV)
+    count = MR.count_of(m)
+    pad = lambda t: torch.cat([t.new_zeros(1), t.flatten()])[1:].view(t.shape)
+    assert a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and pad(b).data_ptr() % 16 == 4
+    terms = {'plain': lambda a, b, m, **k: ops.ssim_term_value_grad(a, b, **k),
+             'masked': lambda a, b, m, **k: ops.masked_ssim_term_value_grad(a, b, m, count, **k)}
+    for name, term in terms.items():
+        value, grad = term(a, b, m)
+        moved = [(pad(a), b, m), (a, pad(b), m)] + ([(a, b, pad(m))] if name == 'masked' else [])
+        for args in moved:
+            value_e, grad_e = term(*args)
+            value_e0, none = term(*args, with_grad=False)
+            assert torch.equal(grad_e, grad) and torch.equal(value_e, value), name
+            assert none is None and torch.equal(value_e0, value), name
 
 
 def test_golden_fixture(golden_dir):

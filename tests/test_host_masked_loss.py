@@ -1,4 +1,4 @@
-"""CPU tests of the masked image terms: the arithmetic csrc/masked_loss.hip compiles -- csrc/loss_math.h:
+"""CPU tests of the masked image terms: the arithmetic csrc/masked_loss.hip and csrc/ssim_term.hip compile -- csrc/loss_math.h:
 masked_composite_pixel, csrc/score_math.h under a mask -- and the predicate of dbw_lens_valid_u8 (csrc/lens_math.h: lens_valid), built for
 the host by g++ (tests/host_masked_loss.cpp) and held to float64 (tests/masked_loss_ref.py has oracles, inputs and bars).
 

@@ -1,4 +1,4 @@
-"""Times the masked image terms (csrc/masked_loss.hip) on the GPU beside what they replace, and a masked training step beside an unmasked one.
+"""Times the masked image terms (csrc/masked_loss.hip, csrc/ssim_term.hip) on the GPU beside what they replace, and a masked training step beside an unmasked one.
 
   kernels  at 4 x 3 x 300 x 400 (`--batch`), seeded inputs, a mask with a lens-like border and 30 % holes:
              masked_composite_fwd_bwd   dbw_monitor_masked_composite forward (rec + value) and its one-launch backward fed by an upstream
