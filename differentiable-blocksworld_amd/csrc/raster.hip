@@ -106,12 +106,19 @@ __global__ __launch_bounds__(256) void scene_bins_kernel(const SceneBinsArgs A) 
     // hold the long lists -- goes first, the env scene's short workgroups fill the tail)
     const SceneBinsArgs::One &G = A.sc[A.scene0 + (A.nscenes - 1 - (int)blockIdx.z)];
     const int bin = blockIdx.x, n = blockIdx.y;
+    BPROF_T(t_k0);
     bin_cell_extents(S, A.H, A.W, (bin % A.nx) * COARSE, (bin / A.nx) * COARSE);
     __syncthreads();
+    BPROF_T(t_k1);
     const int cnt = coarse_bin_block(G.bbox, G.first_idx, G.num_faces, A.H, A.W, A.nx, A.ny, G.list, G.count, G.mask, n, bin, S);
+#ifdef DBW_PROFILE_BINS
+    if (!G.cells) { BPROF_T(t_k2); if (threadIdx.x == 0) { BPROF_ADD(7, t_k2 - t_k0); BPROF_ADD(8, 1); BPROF_ADD(14, t_k1 - t_k0); } }
+#endif
     if (!G.cells) return;
     // (coarse_bin_block ends its last round with a barrier: S.ent is complete)
     cell_bin_block<true>((const FaceRec *)G.recs, G.first_idx, A.B, A.H, A.W, A.nx, A.ny, nullptr, cnt, G.cell, G.pool, G.pool_cap, G.hdr, G.rank, n, bin, S, G.dom);
+    BPROF_T(t_k3);
+    if (threadIdx.x == 0) { BPROF_ADD(7, t_k3 - t_k0); BPROF_ADD(8, 1); BPROF_ADD(14, t_k1 - t_k0); }
 }
 
 template <int KMAX, int TW, int TH>
@@ -419,6 +426,18 @@ extern "C" int dbw_rasterize_bwd(const float *face_verts, const int32_t *pix_to_
 }
 
 void dbw_set_raster_dbg(int flags) { g_raster_dbg = flags; }
+
+#ifdef DBW_PROFILE_BINS
+// tools/bins_cycles.py only: the 2 x 16 counters of raster_bin.h (the scene that goes first, then the other), optionally cleared
+extern "C" void dbw_debug_read_bins_profile(unsigned long long *out32, int reset) {
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(out32, HIP_SYMBOL(dbw::g_bprof), 32 * sizeof(unsigned long long));
+    if (reset) {
+        const unsigned long long z[32] = {0};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(dbw::g_bprof), z, sizeof(z));
+    }
+}
+#endif
 
 #ifdef DBW_DIAG
 // tools/diag only (builds with -DDBW_DIAG, tools/variants.sh): byte offsets, inside a binned workspace, of {cell-list header, cell table, work list, tile ranks, pool} and the

@@ -19,6 +19,20 @@ __device__ __forceinline__ int work_class(int c) {
     return c < 0 ? 0 : c == 0 ? 9 : c >= 64 ? 0 : c >= 48 ? 1 : c >= 32 ? 2 : c >= 24 ? 3 : c >= 16 ? 4 : c >= 12 ? 5 : c >= 8 ? 6 : c >= 4 ? 7 : 8;
 }
 
+#ifdef DBW_PROFILE_BINS
+// cycle / event accounting of a binning workgroup of scene_bins_kernel (tools/bins_cycles.py only; nothing of it in the product build):
+// s_memtime deltas of the wave that runs the stage, summed per scene of the launch (blockIdx.z: 0 = the scene that goes first, the
+// blocks).  1 coarse scan (with the wait for the view's face range), 2 masks (wave 0's chunks of entries), 3 transposition (wave
+// 0's), 4 prefix + returning atomics, 5 dom (wave 1), 6 fill (wave 0, from the barrier in front of dom), 7 whole workgroup, 8 workgroups,
+// 9 slots scanned, 10 entries, 13 bins with an empty list, 14 extents, 15 masks + transposition + the barrier behind them (wave 0)
+__device__ unsigned long long g_bprof[2 * 16];
+#define BPROF_T(x) const unsigned long long x = __builtin_readcyclecounter()
+#define BPROF_ADD(i, v) { if ((threadIdx.x & 63) == 0) atomicAdd(&g_bprof[(blockIdx.z ? 16 : 0) + (i)], (unsigned long long)(v)); }
+#else
+#define BPROF_T(x)
+#define BPROF_ADD(i, v)
+#endif
+
 constexpr int CELL_ENTRY_CAP = 1024, CELL_CHUNKS = CELL_ENTRY_CAP / 64;
 constexpr int CELL_HDR_INTS = 1 + 8 * 16;      // cell-list header: pool cursor, 8 x 16 class cursors
 
@@ -64,6 +78,8 @@ __device__ __forceinline__ int coarse_bin_block(const float4 *__restrict__ bbox,
     int *out = list + (long long)f_begin * nb + (long long)bin * nf;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int cnt = 0;
+    BPROF_T(t_c1);
+    if (wv == 0) BPROF_ADD(9, nf);
     // The rounds of a bin are a chain -- the workgroup's latency, not its work, is what the step pays for at small batches --, so: the
     // boxes of 1024 faces are requested together (a round used to start with a load every thread then waited for), and a round covers
     // 512 faces, two per thread, behind ONE pair of barriers (face order: first half waves 0..3, then second half waves 0..3).
@@ -135,6 +151,8 @@ __device__ __forceinline__ int coarse_bin_block(const float4 *__restrict__ bbox,
     }
     if (threadIdx.x == 0) count[n * nb + bin] = cnt;
     if (threadIdx.x < 2) mask[(n * nb + bin) * 2 + threadIdx.x] = S.mask[threadIdx.x];
+    BPROF_T(t_c2);
+    if (wv == 0) { BPROF_ADD(1, t_c2 - t_c1); BPROF_ADD(10, cnt); BPROF_ADD(13, cnt == 0); }
     return cnt;
 }
 
@@ -162,13 +180,20 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
     const int f_begin = first_idx[n];
     const bool too_long = cnt_all > CELL_ENTRY_CAP;
     const int cnt = too_long ? 0 : cnt_all, chunks = (cnt + 63) >> 6;
+    BPROF_T(t_f0);
     for (int ch = wv; ch < chunks; ch += 4) {
-        const int idx = ch * 64 + lane;
         unsigned mlo = 0u, mhi = 0u;
-        if (idx < cnt) {
-            const int e = STASHED ? S.ent[idx] : lst[idx];
-            const int j = e & 0xfffff, ex0 = (e >> 20) & 7, ex1 = (e >> 23) & 7, ey0 = (e >> 26) & 7, ey1 = (e >> 29) & 7;
-            if (!STASHED) S.ent[idx] = e;
+        BPROF_T(t_m0);
+        // A chunk of few entries -- the sky + ground scene: nine huge faces per bin, each reaching most of the 64 cells -- spreads the cell
+        // rows of an entry over 2, 4 or 8 lanes (lane = part * E + entry): the loop below was one lane's walk over all 64 cells, the longest
+        // link of such a bin's chain.  Same tests on the same values; the parts are ORed back into the entry's lane.
+        const int n_in = min(64, cnt - ch * 64);
+        const int sh = n_in <= 8 ? 3 : n_in <= 16 ? 2 : n_in <= 32 ? 1 : 0, E = 64 >> sh, rows = 8 >> sh;
+        const int ei = lane & (E - 1), r0 = (lane >> (6 - sh)) * rows, eidx = ch * 64 + ei;
+        if (eidx < cnt) {
+            const int e = STASHED ? S.ent[eidx] : lst[eidx];
+            const int j = e & 0xfffff, ex0 = (e >> 20) & 7, ex1 = (e >> 23) & 7, ey0 = max((e >> 26) & 7, r0), ey1 = min((e >> 29) & 7, r0 + rows - 1);
+            if (!STASHED && lane < E) S.ent[eidx] = e;
             // (by value, through 128-bit loads: every field the tile test reads sits in registers before the loop over the cells starts --
             // a reference left a dependent global load per edge test inside it)
             FaceRec r;
@@ -184,6 +209,12 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
                         if (cy < 4) mlo |= 1u << (8 * cy + cx); else mhi |= 1u << (8 * (cy - 4) + cx);
                     }
         }
+        for (int q = 1; q < (1 << sh); ++q) {          // (lanes below E end with their entry's whole mask; the others are cleared)
+            const unsigned plo = __shfl(mlo, ei + q * E, 64), phi = __shfl(mhi, ei + q * E, 64);
+            if (lane < E) { mlo |= plo; mhi |= phi; }
+        }
+        if (lane >= E) { mlo = 0u; mhi = 0u; }
+        BPROF_T(t_m1);
         unsigned long long col = 0ull;          // lane c: the entries of this chunk that touch cell c
 #pragma unroll 2
         for (int c = 0; c < 32; ++c) {
@@ -192,8 +223,11 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
             if (lane == c + 32) col = b1;
         }
         S.col[ch][lane] = col;
+        BPROF_T(t_m2);
+        if (wv == 0) { BPROF_ADD(2, t_m1 - t_m0); BPROF_ADD(3, t_m2 - t_m1); }
     }
     __syncthreads();
+    BPROF_T(t_f1);
     // per cell (wave 0, lane = cell): entries per chunk -> exclusive prefix over the chunks, total; then over the cells
     const int px = x0 + 8 * (lane & 7), py = y0 + 8 * (lane >> 3);
     const bool in_img = px < W && py < H;
@@ -244,8 +278,11 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
         // (class, and rank of the tile inside its (XCD segment, class): work_scatter_kernel turns them into the tile's place in the launch
         // order.  The class travels with the rank -- for a bin that overflowed the pool it is not the class of the stored count, -1)
         if (in_img) rank[L] = r | ((key - seg16) << WORK_RANK_BITS);
+        BPROF_T(t_f2);
+        BPROF_ADD(4, t_f2 - t_f1); BPROF_ADD(15, t_f1 - t_f0);
     }
     __syncthreads();
+    BPROF_T(t_f3);
     // dom (the env scene of the training step: a hard pass of a few huge faces): the face of a cell's list that is IN FRONT OF all the
     // others over its whole extent -- its farthest vertex nearer than every other listed face's nearest (depths are convex combinations of
     // the vertex depths, so it wins at every pixel it covers) -- and is no half of a split quad and inside the guarded range of the
@@ -277,6 +314,8 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
             }
         }
         if (in_img) dom[(long long)n * tiles + tile] = jb;
+        BPROF_T(t_f4);
+        BPROF_ADD(5, t_f4 - t_f3);
     }
     if (S.base < 0) return;
     for (int ch = wv; ch < chunks; ch += 4) {
@@ -289,6 +328,8 @@ __device__ __forceinline__ void cell_bin_block(const FaceRec *__restrict__ recs,
             bits &= bits - 1ull;
         }
     }
+    BPROF_T(t_f5);
+    if (wv == 0) BPROF_ADD(6, t_f5 - t_f3);
 }
 
 // Where the pieces of a rasteriser workspace live (raster.hip: dbw_raster_workspace_layout).  boxes = the workspace itself.
