@@ -207,9 +207,14 @@ LENS_SIGNATURES = {
     'dbw_lens_pose_chain': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     # the point cloud of a capture's depth maps (csrc/depth_cloud.hip), added under revision 1 of the header
     'dbw_lens_depth_cloud': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i64, c_p, c_p],
+    # intrinsics refinement (csrc/intrinsics_grad.hip), added under revision 1 of the header
+    'dbw_lens_intrinsics_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_i, c_p],
+    'dbw_lens_intrinsics_apply': [c_p, c_p, c_p, c_p],
+    'dbw_lens_intrinsics_chain': [c_p, c_p, c_p, c_p, c_p],
 }
 LENS_OTHER_SIGNATURES = {
     'dbw_lens_pose_grad_workspace_bytes': (c_sz, [c_i, c_i]),
+    'dbw_lens_intrinsics_grad_workspace_bytes': (c_sz, [c_i, c_i]),
     'dbw_lens_depth_cloud_workspace_bytes': (c_sz, [c_i]),
 }
 LENS_N_PARAMS = 12                                            # DBW_LENS_N_PARAMS of include/dbw_lens.h

@@ -460,7 +460,7 @@ class DifferentiableBlocksWorld(nn.Module):
         if not filter_tsp:
             n_blk = scene.faces.shape[0] - self.env_n_faces
             alpha = torch.cat([torch.ones(self.env_n_faces, device=scene.verts.device), self._alpha.repeat_interleave(self.BNF)[:n_blk]])
-        return renderer.render_packed(scene, inp['R'], inp['T'], faces_alpha=alpha)
+        return renderer.render_packed(scene, inp['R'], inp['T'], faces_alpha=alpha, Kmat=inp.get('K_live'))
 
     def render_layers(self, inp, filter_transparent=False):
         """-> fg (B,4,H,W), env (B,4,H,W): the two passes of the decoupled rendering (dbw.py:213-222)."""
@@ -468,6 +468,7 @@ class DifferentiableBlocksWorld(nn.Module):
             raise NotImplementedError('render_layers is the decoupled rendering; decouple_rendering=False renders one joined scene: render_joined')
         self._ensure_cameras(inp)
         R, T = inp['R'], inp['T']
+        K_live = inp.get('K_live')                    # intrinsics refinement: a live K in place of the renderers' frozen one
         fine = not self.is_live('coarse_learning')
         filter_tsp = filter_transparent or fine
         renderer = self.renderer_fine if fine else self.renderer
@@ -478,14 +479,14 @@ class DifferentiableBlocksWorld(nn.Module):
             side = self._side_stream = getattr(self, '_side_stream', None) or torch.cuda.Stream()
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                env = self.renderer_env.render_packed(self.build_env_scene(), R, T, lds_aggregate=True)
+                env = self.renderer_env.render_packed(self.build_env_scene(), R, T, lds_aggregate=True, Kmat=K_live)
             env.record_stream(cur)
         else:
-            env = self.renderer_env.render_packed(self.build_env_scene(), R, T, lds_aggregate=True)     # magnified textures
+            env = self.renderer_env.render_packed(self.build_env_scene(), R, T, lds_aggregate=True, Kmat=K_live)     # magnified textures
         blocks = self.build_blocks_scene(filter_transparent=filter_tsp)
         if blocks is not None:
             alpha = None if filter_tsp else self._alpha.repeat_interleave(self.BNF)   # shared by all views (== .repeat(B))
-            fg = renderer.render_packed(blocks, R, T, faces_alpha=alpha, lds_aggregate=self._blocks_decimated)
+            fg = renderer.render_packed(blocks, R, T, faces_alpha=alpha, lds_aggregate=self._blocks_decimated, Kmat=K_live)
         else:
             fg = torch.zeros_like(env)
         if self.overlap_passes:
@@ -694,7 +695,8 @@ class DifferentiableBlocksWorld(nn.Module):
             return None
         env = self.build_env_scene()
         R, T = inp['R'].float().contiguous(), inp['T'].float().contiguous()
-        Kmat = renderer.cameras.K[0].to(R.device).contiguous()
+        K_live = inp.get('K_live')                    # intrinsics refinement
+        Kmat = (renderer.cameras.K[0] if K_live is None else K_live.reshape(4, 4).float()).to(R.device).contiguous()
         alpha = None if fine else self._alpha.repeat_interleave(self.BNF)
         cfg_e = self.renderer_env._cfg(env.faces.shape[0], lds_aggregate=True, const_faces=env.const_faces)
         cfg_f = renderer._cfg(blocks.faces.shape[0], lds_aggregate=self._blocks_decimated, texbins=blocks.texbins)

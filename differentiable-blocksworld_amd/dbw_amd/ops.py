@@ -254,6 +254,24 @@ def _cam_grads(ctx, iR, g_R, g_T):
     return (g_R if ctx.needs_input_grad[iR] else None), (g_T if ctx.needs_input_grad[iR + 1] else None)
 
 
+def project_clip_bwd_k(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z_clip=0.001, perspective_correct=True, out=None):
+    """dbw_lens_intrinsics_grad: the gradient of the clipped faces with respect to the pinhole matrix the views share, -> g_K (4,4), the full
+    gradient of the matrix (row 2, which the projection never reads, is 0).  The per-slot work of project_clip_bwd, summed over the slots of
+    every view (csrc/intrinsics_grad.hip; fixed summation order, no atomics).  out=g_K: the sum is ADDED to it (the second pass over the
+    same views) and it is returned."""
+    _lib.family('lens')
+    B, V, F_ = R.shape[0], verts.shape[0], faces_i32.shape[0]
+    g_K = out if out is not None else torch.empty(4, 4, dtype=torch.float32, device=verts.device)
+    if B == 0:
+        return g_K if out is not None else g_K.zero_()
+    ws_bytes = int(_lib.load().dbw_lens_intrinsics_grad_workspace_bytes(B, F_))
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=verts.device)
+    _lib.call('dbw_lens_intrinsics_grad', _ptr(verts), _ptr(faces_i32), _ptr(R), _ptr(T), _ptr(Kmat), B, V, F_, float(eps), float(z_clip or 0.0),
+              int(perspective_correct), _ptr(cl['num_faces']), _ptr(cl['c2o']), _ptr(cl['clip_code']), _ptr(cl['clip_w']), _ptr(g_face_verts),
+              _ptr(ws), ws_bytes, _ptr(g_K), int(out is not None), _stream(verts))
+    return g_K
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # shade + blend on given fragments
 # ---------------------------------------------------------------------------------------------------------------------
@@ -408,17 +426,20 @@ class _RenderScene(torch.autograd.Function):
         fa = fa if ctx.has_alpha else None
         need_verts = ctx.needs_input_grad[0]
         need_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]        # camera pose refinement: R, T of the views
-        need_geom = need_verts or need_cam
+        need_K = ctx.needs_input_grad[6]                                     # intrinsics refinement: the K they share
+        need_geom = need_verts or need_cam or need_K
         want_dists = need_geom and cfg.sigma != 0
         want_bary = need_geom and not cfg.detach_bary
-        g_R = g_T = None
+        g_R = g_T = g_K = None
         if FUSED_BACKWARD and (ctx.tiled or (need_geom and (want_dists or want_bary))):
             g_maps, g_alpha, g_fvc = _fused_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, cfg, bg, ctx.tiled, g_img.contiguous(),
                                                 R.shape[0], None)
             g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_verts else None
             if need_cam:
                 g_R, g_T = _cam_grads(ctx, 4, *project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp))
-            return g_verts, g_maps, g_alpha, None, g_R, g_T, None, None, None, None, None, None
+            if need_K:
+                g_K = project_clip_bwd_k(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp)
+            return g_verts, g_maps, g_alpha, None, g_R, g_T, g_K, None, None, None, None, None
         if ctx.tiled:
             raise RuntimeError('tiled fragments can only be consumed by the fused backward')
         g_maps, g_alpha, g_dists, g_bary = shade_blend_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, cfg.F,
@@ -433,11 +454,15 @@ class _RenderScene(torch.autograd.Function):
             g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_verts else None
             if need_cam:
                 g_R, g_T = _cam_grads(ctx, 4, *project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp))
+            if need_K:
+                g_K = project_clip_bwd_k(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp)
         elif need_geom:
             g_verts = torch.zeros_like(verts) if need_verts else None
             if need_cam:
                 g_R, g_T = _cam_grads(ctx, 4, torch.zeros_like(R), torch.zeros_like(T))
-        return g_verts, g_maps, g_alpha, None, g_R, g_T, None, None, None, None, None, None
+            if need_K:
+                g_K = torch.zeros_like(Kmat)
+        return g_verts, g_maps, g_alpha, None, g_R, g_T, g_K, None, None, None, None, None
 
 
 _UNIFORM_LAYOUTS = {}
@@ -623,7 +648,12 @@ class _DecoupledRenderMSE(torch.autograd.Function):
             cam = project_clip_bwd_cam(ve, faces_e, R, T, Kmat, cl_e, g_fvc_e, cfg_e.eps, cfg_e.z_clip, cfg_e.persp)
             cam = project_clip_bwd_cam(vf, faces_f, R, T, Kmat, cl_f, g_fvc_f, cfg_f.eps, cfg_f.z_clip, cfg_f.persp, out=cam)
             g_R, g_T = _cam_grads(ctx, 7, *cam)
-        return (gv_e, gm_e, gv_f, gm_f, ga, None, None, g_R, g_T) + (None,) * 7
+        g_K = None
+        if ctx.needs_input_grad[9]:
+            # intrinsics refinement: env then fg into one buffer, like the pair above
+            g_K = project_clip_bwd_k(ve, faces_e, R, T, Kmat, cl_e, g_fvc_e, cfg_e.eps, cfg_e.z_clip, cfg_e.persp)
+            g_K = project_clip_bwd_k(vf, faces_f, R, T, Kmat, cl_f, g_fvc_f, cfg_f.eps, cfg_f.z_clip, cfg_f.persp, out=g_K)
+        return (gv_e, gm_e, gv_f, gm_f, ga, None, None, g_R, g_T, g_K) + (None,) * 6
 
 
 def render_decoupled_mse(env, fg, alpha, imgs, scale, R, T, Kmat, cfg_e, cfg_f, bg_e, bg_f):
@@ -1370,6 +1400,35 @@ def pose_apply(R0, T0, delta, ids, ids_host=None):
     _lib.family('lens')
     return _PoseApply.apply(_chk(R0.detach(), torch.float32, 'R0'), _chk(T0.detach(), torch.float32, 'T0'),
                             _chk(delta, torch.float32, 'delta'), ids.to(R0.device))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# intrinsics refinement (include/dbw_lens.h)
+# ---------------------------------------------------------------------------------------------------------------------
+class _IntrinsicsApply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K0, theta):
+        K1 = torch.empty_like(K0)
+        _lib.call('dbw_lens_intrinsics_apply', _ptr(K0), _ptr(theta), _ptr(K1), _stream(K0))
+        ctx.save_for_backward(K0, theta)
+        return K1
+
+    @staticmethod
+    def backward(ctx, g_K):
+        K0, theta = ctx.saved_tensors
+        g_theta = torch.empty_like(theta)
+        _lib.call('dbw_lens_intrinsics_chain', _ptr(K0), _ptr(theta), _ptr(g_K.contiguous()), _ptr(g_theta), _stream(K0))
+        return None, g_theta
+
+
+def intrinsics_apply(K0, theta):
+    """dbw_lens_intrinsics_apply / dbw_lens_intrinsics_chain as one autograd function: K0 (4,4) the pinhole matrix of the views, theta (4) =
+    (a_x, a_y, c_x, c_y) -> K' = K0 with K'[0,0] = K0[0,0] exp(a_x), K'[1,1] = K0[1,1] exp(a_y), K'[0,2] = K0[0,2] + c_x, K'[1,2] = K0[1,2] +
+    c_y (csrc/intrinsics_math.h; theta = 0 gives K0 bit for bit).  Only theta receives a gradient: K0 is data."""
+    if tuple(K0.shape) != (4, 4) or tuple(theta.shape) != (4,):
+        raise ValueError(f'intrinsics_apply: K0 (4,4), theta (4,); got {tuple(K0.shape)} and {tuple(theta.shape)}')
+    _lib.family('lens')
+    return _IntrinsicsApply.apply(_chk(K0.detach(), torch.float32, 'K0'), _chk(theta, torch.float32, 'theta'))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

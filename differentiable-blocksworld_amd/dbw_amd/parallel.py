@@ -142,7 +142,12 @@ class ShardedTrainStep:
         if exposed and self.world_size > 1:
             raise NotImplementedError('exposure compensation under data parallelism: the exposure gradients are per view and the ranks do '
                                       'not exchange them')
-        masked = masked or posed or exposed
+        # ... and a batch whose intrinsics are being refined (intrinsics.IntrinsicsRefiner.apply: K_live requires a gradient).
+        # Any live matrix stands the two step plans aside, with a gradient or without: they render with the K frozen at their set-up
+        focal = inp.get('K_live') is not None
+        if focal and self.world_size > 1:
+            raise NotImplementedError('intrinsics refinement under data parallelism: the ranks do not exchange the gradient of K')
+        masked = masked or posed or exposed or focal
         self.model._global_count = self._global_count(inp['imgs'], global_count)
         dirty = None
         if (self.cstep is not None and self.model.training and inp['imgs'].shape[0] > 0 and self._fused_adam() and self.cstep.supported()

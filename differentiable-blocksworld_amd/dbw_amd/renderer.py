@@ -183,13 +183,14 @@ class Renderer(nn.Module):
             cfg.bin_demand = self._bin_demand
         return cfg
 
-    def render_packed(self, scene, R, T, faces_alpha=None, viz_purpose=False, lds_aggregate=False):
+    def render_packed(self, scene, R, T, faces_alpha=None, viz_purpose=False, lds_aggregate=False, Kmat=None):
         """scene: PackedScene shared by the len(R) views.  lds_aggregate: hint for the backward pass (pays when neighbouring
-        pixels hit the same texels: magnified or decimated maps); results are identical either way."""
+        pixels hit the same texels: magnified or decimated maps); results are identical either way.  Kmat: a live (4,4) matrix in place of
+        cameras.K[0] (intrinsics refinement, DESIGN.md 6t: it may require a gradient)."""
         if self.cam_name != 'perspective' or self.cameras.K is None:
             raise NotImplementedError('the HIP path needs perspective cameras with an explicit NDC K: call '
                                       'update_cameras(K=...) first (dbw.py:204-208)')
-        Kmat = self.cameras.K[0].to(R.device).contiguous()
+        Kmat = (self.cameras.K[0] if Kmat is None else Kmat.reshape(4, 4).float()).to(R.device).contiguous()
         R, T = R.float().contiguous(), T.float().contiguous()
         if self.lit:
             return self._render_lit(scene, R, T, Kmat, faces_alpha, viz_purpose)

@@ -1,6 +1,6 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
-                          [--pose-refine LR] [--blocks-init points] [--exposure LR]
+                          [--pose-refine LR] [--blocks-init points] [--exposure LR] [--intrinsics-refine LR]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -22,6 +22,10 @@ model.loss.perceptual_name: ssim -- or --perceptual ssim, which overrides the co
 
 training.pose_refine: {lr, start_epoch, rot, trans} -- or --pose-refine LR -- refines the camera poses of the training views beside the model
 (pose.py); the refined poses are written to <run_dir>/transforms_refined.json (custom captures) or poses_refined.npz at the end.
+
+training.intrinsics_refine: {lr, start_epoch, focal, principal} -- or --intrinsics-refine LR -- refines the pinhole matrix the views share
+beside the model (intrinsics.py): by default one scale of both focal lengths; the evaluation renders with the refined matrix,
+which is written to <run_dir>/intrinsics_refined.yml and, for a capture without lens coefficients, into <run_dir>/transforms_refined.json.
 
 training.exposure: {lr, start_epoch, bias, center} -- or --exposure LR -- fits a gain and an offset per colour channel and training view beside
 the model (exposure.py): both image terms see exp(g) * render + b; the fitted values are written to <run_dir>/exposures.tsv at
@@ -59,6 +63,8 @@ def parse_args(argv=None):
     ap.add_argument('--no-record', action='store_true', help='no metric files, image logs or checkpoints during the run: model.pkl at the end only')
     ap.add_argument('--pose-refine', type=float, default=None, metavar='LR',
                     help='refine the camera poses of the training views beside the model, with this learning rate (training.pose_refine.lr)')
+    ap.add_argument('--intrinsics-refine', type=float, default=None, metavar='LR',
+                    help='refine the shared focal scale of the views beside the model, with this learning rate (training.intrinsics_refine.lr)')
     ap.add_argument('--exposure', type=float, default=None, metavar='LR',
                     help='fit a per-view exposure (gain and offset per channel) beside the model, with this learning rate (training.exposure.lr)')
     ap.add_argument('--blocks-init', choices=('points',), default=None,
@@ -92,6 +98,9 @@ def prepare_config(args):
     if getattr(args, 'pose_refine', None) is not None:
         entry = cfg.setdefault('training', {}).get('pose_refine')
         cfg['training']['pose_refine'] = dict(entry if isinstance(entry, dict) else {}, lr=args.pose_refine)
+    if getattr(args, 'intrinsics_refine', None) is not None:
+        entry = cfg.setdefault('training', {}).get('intrinsics_refine')
+        cfg['training']['intrinsics_refine'] = dict(entry if isinstance(entry, dict) else {}, lr=args.intrinsics_refine)
     if getattr(args, 'exposure', None) is not None:
         entry = cfg.setdefault('training', {}).get('exposure')
         cfg['training']['exposure'] = dict(entry if isinstance(entry, dict) else {}, lr=args.exposure)

@@ -149,6 +149,20 @@ class Trainer:
             self.exposure = ExposureRefiner(self.local['imgs'].shape[0], self.local['imgs'].device, lr=self.exposure_cfg['lr'],
                                             betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))), bias=self.exposure_cfg['bias'],
                                             center=self.exposure_cfg['center'])
+        # Intrinsics refinement (training.intrinsics_refine: {lr, start_epoch, focal, principal}; intrinsics.py): absent ->
+        # nothing is built and no batch changes.  Present -> from start_epoch on batches carry 'K_live', the refined K with a gradient to
+        # theta, and the refiner's Adam step follows the model's.
+        self.intrinsics, self.intrinsics_cfg = None, None
+        from .intrinsics import IntrinsicsRefiner, parse_config as parse_intrinsics
+        self.intrinsics_cfg = parse_intrinsics(tr.get('intrinsics_refine'))
+        if self.intrinsics_cfg is not None:
+            if ws > 1:
+                raise NotImplementedError('training.intrinsics_refine under data parallelism: the ranks do not exchange the gradient of K')
+            if 'K' not in views:
+                raise KeyError("training.intrinsics_refine: the views carry no 'K', the matrix to refine")
+            self.intrinsics = IntrinsicsRefiner(views['K'][0], views['imgs'].device, lr=self.intrinsics_cfg['lr'],
+                                                betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))),
+                                                focal=self.intrinsics_cfg['focal'], principal=self.intrinsics_cfg['principal'])
         # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
         # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
         self.mask_sums = None
@@ -226,11 +240,16 @@ class Trainer:
             expose = self.exposure is not None and self.epoch >= self.exposure_cfg['start_epoch'] and idx.numel() > 0
             if expose:
                 batch = self.exposure.attach(batch)
+            focal = self.intrinsics is not None and self.epoch >= self.intrinsics_cfg['start_epoch'] and idx.numel() > 0
+            if focal:
+                batch = self.intrinsics.apply(batch)
             last, _ = self.run_single_batch_train(batch, self.global_count(b))
             if refine:
                 self.pose.step()
             if expose:
                 self.exposure.step()
+            if focal:
+                self.intrinsics.step()
             n_img += idx.numel()
             if rec is not None:
                 rec.after_step(self.epoch, b + 1, last, ids)
@@ -290,6 +309,15 @@ class Trainer:
                 write_refined(self.scene, self.pose, run_dir, self.local['R'], self.local['T'])
             if getattr(loader, 'dataset', None) is not None and loader.dataset is self.scene:
                 loader = _RefinedLoader(loader, *self.pose.refined(self.local['R'], self.local['T']))      # the training views: at their refined poses
+        if self.intrinsics is not None:
+            # the refined K' replaces the frozen one on the four renderers: every render from here on sees it (scores, export, parse)
+            from .intrinsics import write_refined as write_intrinsics
+            write_intrinsics(self.scene, self.intrinsics, run_dir, self.views['imgs'].shape[2:], after_pose=self.pose is not None and self.scene is not None
+                             and getattr(self.scene, 'name', None) == 'custom')
+            K1 = self.intrinsics.refined()[None]
+            for r in (getattr(self.model, n, None) for n in ('renderer', 'renderer_fine', 'renderer_env', 'renderer_light')):
+                if r is not None:
+                    r.update_cameras(device=device, K=K1)
         if self.exposure is not None:
             # (the renders below stay uncompensated, at the canonical exposure: a held-out view has no fitted row)
             from .exposure import write_exposures
@@ -347,7 +375,8 @@ class Trainer:
                 'optimizer_state': {'exp_avg': self.step_fn.exp_avg.clone(), 'exp_avg_sq': self.step_fn.exp_avg_sq.clone(),
                                     'n_steps': self.step_fn.n_steps},
                 'scheduler_state': self.scheduler.state_dict(), **({} if self.pose is None else {'pose_refine': self.pose.state_dict()}),
-                **({} if self.exposure is None else {'exposure': self.exposure.state_dict()})}
+                **({} if self.exposure is None else {'exposure': self.exposure.state_dict()}),
+                **({} if self.intrinsics is None else {'intrinsics_refine': self.intrinsics.state_dict()})}
 
     def load_state_dict(self, ckpt):
         self.model.load_state_dict(ckpt['model_state'])
@@ -366,3 +395,5 @@ class Trainer:
             self.pose.load_state_dict(ckpt['pose_refine'])
         if self.exposure is not None and 'exposure' in ckpt:
             self.exposure.load_state_dict(ckpt['exposure'])
+        if self.intrinsics is not None and 'intrinsics_refine' in ckpt:
+            self.intrinsics.load_state_dict(ckpt['intrinsics_refine'])

@@ -4,8 +4,10 @@
  * p2 of a Nerfstudio transforms.json) into the pinhole frame the renderer assumes, before the image ingest (dbw_ingest.h) resizes them.
  * Pose: the gradient of a render with respect to each view's R and T, and the per-view 6-vector that refines a pose during training.
  * A capture whose frames have a camera each, or a fisheye lens, is rectified frame by frame into one pinhole (dbw_lens_rectify_u8).
- * Python side: dbw_amd/ops.py (undistort_u8, lens_valid_u8, rectify_u8, rectify_valid_u8, project_clip_bwd_cam, pose_apply), bound through _lib.LENS_SIGNATURES and
- * _lib.LENS_OTHER_SIGNATURES.  The arithmetic is csrc/lens_math.h and csrc/pose_math.h.
+ * Intrinsics: the gradient of a render with respect to the pinhole matrix the views share, and the 4-vector that refines it.
+ * Python side: dbw_amd/ops.py (undistort_u8, lens_valid_u8, rectify_u8, rectify_valid_u8, project_clip_bwd_cam, pose_apply,
+ * project_clip_bwd_k, intrinsics_apply), bound through _lib.LENS_SIGNATURES and
+ * _lib.LENS_OTHER_SIGNATURES.  The arithmetic is csrc/lens_math.h, csrc/pose_math.h and csrc/intrinsics_math.h.
  *
  * Conventions are those of dbw_hip.h: DEVICE pointers owned by the caller, contiguous, unless said otherwise; return 0 or a negative
  * DBW_ERR_*, the text in dbw_last_error(); arguments are validated before any launch; kernels are enqueued on `stream`, no host
@@ -99,6 +101,31 @@ int dbw_lens_pose_apply(const float *R0, const float *T0, const float *delta, co
  * and receive no gradient. */
 int dbw_lens_pose_chain(const float *R0, const float *T0, const float *delta, const int32_t *ids, int B, int V, const float *grad_R,
                         const float *grad_T, float *grad_delta, dbw_stream_t stream);
+
+/* Intrinsics refinement, added under revision 1 of this header (csrc/intrinsics_grad.hip, arithmetic: csrc/intrinsics_math.h).  Kmat (4,4)
+ * row-major is the pinhole matrix the views share: px, py, pw of a view-space point come from its rows 0, 1 and 3, row 2 is never read.
+ *
+ * dbw_lens_intrinsics_grad: the gradient of the clipped faces of B views with respect to Kmat.  The arguments up to workspace_bytes are
+ * those of dbw_lens_pose_grad; the per-slot gradient is summed over the slots j < num_faces[b] of every view into grad_K (4,4), the full
+ * gradient of the matrix (what autograd gives for it), row 2 zero.  What grad_face_verts_c holds in the other slots reaches nothing.
+ * accumulate != 0: the sum is added to what grad_K holds (a second pass), else it replaces it.  workspace:
+ * dbw_lens_intrinsics_grad_workspace_bytes(B, F) bytes on the DEVICE, 4-byte aligned, contents irrelevant.  The sum has a fixed order --
+ * slots of a chunk of 256, then view-major over the chunks in fp64 -- and no atomics: two calls give the same bits.  B >= 0 (B == 0:
+ * nothing is done), V > 0, F > 0, B <= 65535. */
+size_t dbw_lens_intrinsics_grad_workspace_bytes(int B, int F);
+int dbw_lens_intrinsics_grad(const float *verts_world, const int32_t *faces, const float *R, const float *T, const float *Kmat, int B, int V,
+                             int F, float eps, float z_clip, int perspective_correct, const int32_t *num_faces, const int32_t *c2o,
+                             const int32_t *clip_code, const float *clip_w, const float *grad_face_verts_c, void *workspace,
+                             size_t workspace_bytes, float *grad_K, int accumulate, dbw_stream_t stream);
+
+/* The refined matrix.  theta: 4 floats (a_x, a_y, c_x, c_y) on the DEVICE.  K_out = K0 except K_out[0] = K0[0] exp(a_x),
+ * K_out[5] = K0[5] exp(a_y), K_out[2] = K0[2] + c_x, K_out[6] = K0[6] + c_y: a scale of each focal length and an offset of the principal
+ * point in NDC units.  theta = 0 gives K0 bit for bit. */
+int dbw_lens_intrinsics_apply(const float *K0, const float *theta, float *K_out, dbw_stream_t stream);
+
+/* Backward of dbw_lens_intrinsics_apply with respect to theta: grad_K (4,4) of the refined matrix -> grad_theta (4), WRITTEN:
+ * (grad_K[0] K_out[0], grad_K[5] K_out[5], grad_K[2], grad_K[6]).  K0 is data and receives no gradient. */
+int dbw_lens_intrinsics_chain(const float *K0, const float *theta, const float *grad_K, float *grad_theta, dbw_stream_t stream);
 
 /* The point cloud of a capture's depth maps, added under revision 1 of this header (csrc/depth_cloud.hip, arithmetic: csrc/depth_math.h).
  * depth (N,H,W) uint16 on the DEVICE, at any 2-byte alignment: one depth map per frame, at the maps' own resolution.  cams (N rows of
