@@ -1,15 +1,14 @@
-// Intrinsics refinement arithmetic shared by the device kernels (hipcc, intrinsics_grad.hip) and the host (g++: tests/host_intrinsics_math.cpp,
+// Intrinsics refinement arithmetic shared by the device kernels (hipcc, camera_grad.hip) and the host (g++: tests/host_intrinsics_math.cpp,
 // held by tests/test_host_intrinsics_math.py to autograd of the oracle and to a float64 restatement).  DESIGN.md 6t.
 //
 // Conventions are those of camera_math.h::project: K (4,4) row-major, shared by the views,
 //   px = vx K[0] + vy K[1] + vz K[2] + K[3],  py from row 1 (K[4..7]),  pw from row 3 (K[12..15]);  row 2 (K[8..11]) is never read.
 //
-// Gradient of K.  With gpx, gpy, gpw the gradients of the three projected rows of a vertex (what camera_math.h::vertex_bwd_view forms from
+// Gradient of K.  With gpx, gpy, gpw the gradients of the three projected rows of a vertex (what camera_math.h::project_bwd forms from
 // the ndc gradient g; gpw = 0 where |pw| < eps, the clamp of the denominator), the vertex adds gpx (vx, vy, vz, 1) to g_K[0..3],
 // gpy (vx, vy, vz, 1) to g_K[4..7] and gpw (vx, vy, vz, 1) to g_K[12..15]: twelve accumulators acc[0..3], acc[4..7], acc[8..11], the full
-// gradient of the matrix (row 2 is 0).  The depth component g.z reaches the view depth alone, which K does not touch.  slot_k_grad does that
-// for the three vertices of one clipped-face slot through pose_math.h::clip_slot_bwd, the one statement of the clipping case analysis
-// outside project_clip.hip.
+// gradient of the matrix (row 2 is 0).  The depth component g.z reaches the view depth alone, which K does not touch.  KGradSink does that
+// for every vertex camera_math.h::clip_slot_walk hands it: the three vertices of one clipped-face slot, through the one clipping case analysis.
 //
 // Refinement.  theta = (a_x, a_y, c_x, c_y): K' = K0 except K'[0] = K0[0] exp(a_x), K'[5] = K0[5] exp(a_y), K'[2] = K0[2] + c_x,
 // K'[6] = K0[6] + c_y -- a scale of each focal length, an offset of the principal point in NDC units (half the shorter image side).
@@ -17,39 +16,35 @@
 // expf.  IEEE 754 only recommends exp(0) == 1, and neither of the two libraries that serve this header (the device's OCML, the host's
 // libm) states it for expf, so the identity rests on the branch and not on them.
 #pragma once
-#include "pose_math.h"
+#include "camera_math.h"
 
 namespace dbw {
 
 // ---- gradient of K --------------------------------------------------------------------------------------------------------------------
-// one vertex: acc[0..3] += gpx (vx, vy, vz, 1), acc[4..7] += gpy (..), acc[8..11] += gpw (..).  gpx, gpy, gpw: the operations of
-// vertex_bwd_view in its order.
+// one vertex: acc[0..3] += gpx (vx, vy, vz, 1), acc[4..7] += gpy (..), acc[8..11] += gpw (..)
 DBW_HD void vertex_k_grad(const float *verts, int vi, const Cam &c, float eps, f3 g, float (&acc)[12]) {
-    if (g.x == 0.f && g.y == 0.f && g.z == 0.f) return;
-    const Proj pr = project(verts + (long long)vi * 3, c, eps);
-    const float gpx = g.x / pr.denom, gpy = g.y / pr.denom;
-    const float gden = -(g.x * pr.px + g.y * pr.py) / (pr.denom * pr.denom);
-    const float ab = pr.pw < 0.f ? -pr.pw : pr.pw;
-    const float gpw = ab >= eps ? gden : 0.f;
-    acc[0] += gpx * pr.vx; acc[1] += gpx * pr.vy; acc[2] += gpx * pr.vz; acc[3] += gpx;
-    acc[4] += gpy * pr.vx; acc[5] += gpy * pr.vy; acc[6] += gpy * pr.vz; acc[7] += gpy;
-    acc[8] += gpw * pr.vx; acc[9] += gpw * pr.vy; acc[10] += gpw * pr.vz; acc[11] += gpw;
+    if (all_zero(g)) return;
+    const ProjGrad p = project_bwd(verts + (long long)vi * 3, c, eps, g);
+    const Proj &pr = p.pr;
+    acc[0] += p.gpx * pr.vx; acc[1] += p.gpx * pr.vy; acc[2] += p.gpx * pr.vz; acc[3] += p.gpx;
+    acc[4] += p.gpy * pr.vx; acc[5] += p.gpy * pr.vy; acc[6] += p.gpy * pr.vz; acc[7] += p.gpy;
+    acc[8] += p.gpw * pr.vx; acc[9] += p.gpw * pr.vy; acc[10] += p.gpw * pr.vz; acc[11] += p.gpw;
 }
+
+// the sink of camera_math.h::clip_slot_walk that sums the gradient of K over the vertices it is handed
+struct KGradSink {
+    const float *verts;
+    const Cam &c;
+    float eps;
+    float (&acc)[12];
+    DBW_HD void operator()(int, int vi, f3 g) const { vertex_k_grad(verts, vi, c, eps, g, acc); }
+};
 
 // one clipped-face slot of one view: g = the nine gradient components of its three vertices, vi0..vi2 = the mesh face's vertex indices
 DBW_HD void slot_k_grad(const float *verts, int vi0, int vi1, int vi2, const Cam &c, float eps, float zc, int persp, int cd, float w2, float w3,
                         const float (&g)[9], float (&acc)[12]) {
-    const f3 ga{g[0], g[1], g[2]}, gb{g[3], g[4], g[5]}, gc{g[6], g[7], g[8]};
-    f3 q0{0.f, 0.f, 0.f}, q1 = q0, q2 = q0;
-    if (cd >= 0) {
-        q0 = project(verts + (long long)vi0 * 3, c, eps).ndc; q1 = project(verts + (long long)vi1 * 3, c, eps).ndc;
-        q2 = project(verts + (long long)vi2 * 3, c, eps).ndc;
-    }
-    f3 gv0, gv1, gv2;
-    clip_slot_bwd(cd, q0, q1, q2, zc, persp, w2, w3, ga, gb, gc, gv0, gv1, gv2);
-    vertex_k_grad(verts, vi0, c, eps, gv0, acc);
-    vertex_k_grad(verts, vi1, c, eps, gv1, acc);
-    vertex_k_grad(verts, vi2, c, eps, gv2, acc);
+    const float cw2[2] = {w2, w3};
+    clip_slot_walk(verts, vi0, vi1, vi2, c, eps, zc, persp, cd, cw2, g, KGradSink{verts, c, eps, acc});
 }
 
 // ---- refinement -----------------------------------------------------------------------------------------------------------------------

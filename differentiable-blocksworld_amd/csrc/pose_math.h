@@ -1,11 +1,11 @@
-// Camera pose refinement arithmetic shared by the device kernels (hipcc, pose_grad.hip) and the host (g++: tests/host_pose_math.cpp, held
+// Camera pose refinement arithmetic shared by the device kernels (hipcc, camera_grad.hip) and the host (g++: tests/host_pose_math.cpp, held
 // by tests/test_host_pose_math.py to autograd of the oracle and to a float64 restatement).  DESIGN.md 6o.
 //
 // Conventions are those of camera_math.h::project: row vectors, v = X.R + T, R row-major, v_c = sum_r X_r R[3r + c] + T_c.
 //
-// Gradient of a view's camera.  With gview the view-space gradient of a vertex (camera_math.h::vertex_bwd_view), the vertex adds gview to
-// g_T and X_r * gview_c to g_R[3r + c].  slot_cam_grad does that for the three vertices of one clipped-face slot, through the clipping
-// case analysis of project_clip_bwd_body (restated here: that body stays as it is).
+// Gradient of a view's camera.  With gview the view-space gradient of a vertex (camera_math.h::view_grad), the vertex adds gview to g_T
+// and X_r * gview_c to g_R[3r + c].  CamGradSink does that for every vertex camera_math.h::clip_slot_walk hands it: the three vertices of one
+// clipped-face slot, through the one clipping case analysis.
 //
 // Refinement.  A view's 6-vector delta = (w, tau) perturbs the camera in its own frame: v' = v.E(w) + tau, hence R' = R.E, T' = T.E + tau.
 // E = I + a K + b K^2 with th = |w|, a = sin th / th, b = (1 - cos th) / th^2 and
@@ -22,39 +22,11 @@ namespace dbw {
 constexpr float POSE_SERIES_T = 0.0625f;     // th < 0.25
 
 // ---- gradient of a view's camera ------------------------------------------------------------------------------------------------------
-// the gradients of the three ORIGINAL vertices' ndc positions (slots of the mesh face) from those of one clipped-face slot's three
-// vertices ga, gb, gc.  cd < 0: the face was not clipped.  Otherwise i1 = cd & 3 is the slot of p1 in the original face, kind = cd >> 2
-// says which clipped triangle this is ((p4, p5, p1), (p4, p2, p5), (p5, p2, p3)); q0..q2 = the projected original vertices (read only
-// for a clipped face); w2, w3 = the detached weights of p4 on p1-p2 and p5 on p1-p3.
-DBW_HD void clip_slot_bwd(int cd, f3 q0, f3 q1, f3 q2, float zc, int persp, float w2, float w3, f3 ga, f3 gb, f3 gc, f3 &gv0, f3 &gv1, f3 &gv2) {
-    if (cd < 0) { gv0 = ga; gv1 = gb; gv2 = gc; return; }
-    const int i1 = cd & 3, kind = cd >> 2;
-    // vertex roles rotated by i1 with selects (runtime indexing would put the arrays in scratch memory)
-    const f3 P1 = i1 == 0 ? q0 : (i1 == 1 ? q1 : q2), P2 = i1 == 0 ? q1 : (i1 == 1 ? q2 : q0), P3 = i1 == 0 ? q2 : (i1 == 1 ? q0 : q1);
-    f3 g1{0.f, 0.f, 0.f}, g2{0.f, 0.f, 0.f}, g3{0.f, 0.f, 0.f};
-    if (kind == 0) {          // (p4, p5, p1)
-        clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2);
-        clip_point_bwd(P1, P3, zc, persp, w3, gb, g1, g3);
-        g1.x += gc.x; g1.y += gc.y; g1.z += gc.z;
-    } else if (kind == 1) {   // (p4, p2, p5)
-        clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2);
-        g2.x += gb.x; g2.y += gb.y; g2.z += gb.z;
-        clip_point_bwd(P1, P3, zc, persp, w3, gc, g1, g3);
-    } else {                  // (p5, p2, p3)
-        clip_point_bwd(P1, P3, zc, persp, w3, ga, g1, g3);
-        g2.x += gb.x; g2.y += gb.y; g2.z += gb.z;
-        g3.x += gc.x; g3.y += gc.y; g3.z += gc.z;
-    }
-    gv0 = i1 == 0 ? g1 : (i1 == 1 ? g3 : g2);
-    gv1 = i1 == 0 ? g2 : (i1 == 1 ? g1 : g3);
-    gv2 = i1 == 0 ? g3 : (i1 == 1 ? g2 : g1);
-}
-
 // one vertex: acc[0..8] += X_r * gview_c (g_R, row-major), acc[9..11] += gview (g_T)
 DBW_HD void vertex_cam_grad(const float *verts, int vi, const Cam &c, float eps, f3 g, float (&acc)[12]) {
-    if (g.x == 0.f && g.y == 0.f && g.z == 0.f) return;
-    const f3 gv = vertex_bwd_view(verts, vi, c, eps, g);
+    if (all_zero(g)) return;
     const float *X = verts + (long long)vi * 3;
+    const f3 gv = view_grad(project_bwd(X, c, eps, g), c, g);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         acc[r * 3] += X[r] * gv.x; acc[r * 3 + 1] += X[r] * gv.y; acc[r * 3 + 2] += X[r] * gv.z;
@@ -62,20 +34,20 @@ DBW_HD void vertex_cam_grad(const float *verts, int vi, const Cam &c, float eps,
     acc[9] += gv.x; acc[10] += gv.y; acc[11] += gv.z;
 }
 
+// the sink of camera_math.h::clip_slot_walk that sums a view's camera gradient over the vertices it is handed
+struct CamGradSink {
+    const float *verts;
+    const Cam &c;
+    float eps;
+    float (&acc)[12];
+    DBW_HD void operator()(int, int vi, f3 g) const { vertex_cam_grad(verts, vi, c, eps, g, acc); }
+};
+
 // one clipped-face slot of one view: g = the nine gradient components of its three vertices, vi0..vi2 = the mesh face's vertex indices
 DBW_HD void slot_cam_grad(const float *verts, int vi0, int vi1, int vi2, const Cam &c, float eps, float zc, int persp, int cd, float w2, float w3,
                           const float (&g)[9], float (&acc)[12]) {
-    const f3 ga{g[0], g[1], g[2]}, gb{g[3], g[4], g[5]}, gc{g[6], g[7], g[8]};
-    f3 q0{0.f, 0.f, 0.f}, q1 = q0, q2 = q0;
-    if (cd >= 0) {
-        q0 = project(verts + (long long)vi0 * 3, c, eps).ndc; q1 = project(verts + (long long)vi1 * 3, c, eps).ndc;
-        q2 = project(verts + (long long)vi2 * 3, c, eps).ndc;
-    }
-    f3 gv0, gv1, gv2;
-    clip_slot_bwd(cd, q0, q1, q2, zc, persp, w2, w3, ga, gb, gc, gv0, gv1, gv2);
-    vertex_cam_grad(verts, vi0, c, eps, gv0, acc);
-    vertex_cam_grad(verts, vi1, c, eps, gv1, acc);
-    vertex_cam_grad(verts, vi2, c, eps, gv2, acc);
+    const float cw2[2] = {w2, w3};
+    clip_slot_walk(verts, vi0, vi1, vi2, c, eps, zc, persp, cd, cw2, g, CamGradSink{verts, c, eps, acc});
 }
 
 // ---- refinement -----------------------------------------------------------------------------------------------------------------------

@@ -116,42 +116,10 @@ __device__ __forceinline__ void project_clip_bwd_body(
             f = c2o[o];
             const int cd = code[o];
             vi[0] = faces[f * 3]; vi[1] = faces[f * 3 + 1]; vi[2] = faces[f * 3 + 2];
-            f3 gv[3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            const f3 ga{g[0], g[1], g[2]}, gb{g[3], g[4], g[5]}, gc{g[6], g[7], g[8]};
-            if (cd < 0) {
-                gv[0] = ga; gv[1] = gb; gv[2] = gc;
-            } else {
-                const int i1 = cd & 3, kind = cd >> 2;
-                // vertex roles rotated by i1 with selects (runtime indexing would put the arrays in scratch memory)
-                const f3 q0 = project(verts + (long long)vi[0] * 3, cam, eps).ndc, q1 = project(verts + (long long)vi[1] * 3, cam, eps).ndc,
-                         q2 = project(verts + (long long)vi[2] * 3, cam, eps).ndc;
-                const f3 P1 = i1 == 0 ? q0 : (i1 == 1 ? q1 : q2), P2 = i1 == 0 ? q1 : (i1 == 1 ? q2 : q0),
-                         P3 = i1 == 0 ? q2 : (i1 == 1 ? q0 : q1);
-                const float w2 = cw[o * 2], w3 = cw[o * 2 + 1];
-                f3 g1{0.f, 0.f, 0.f}, g2{0.f, 0.f, 0.f}, g3{0.f, 0.f, 0.f};
-                if (kind == 0) {          // (p4, p5, p1)
-                    clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2);
-                    clip_point_bwd(P1, P3, zc, persp, w3, gb, g1, g3);
-                    g1.x += gc.x; g1.y += gc.y; g1.z += gc.z;
-                } else if (kind == 1) {   // (p4, p2, p5)
-                    clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2);
-                    g2.x += gb.x; g2.y += gb.y; g2.z += gb.z;
-                    clip_point_bwd(P1, P3, zc, persp, w3, gc, g1, g3);
-                } else {                  // (p5, p2, p3)
-                    clip_point_bwd(P1, P3, zc, persp, w3, ga, g1, g3);
-                    g2.x += gb.x; g2.y += gb.y; g2.z += gb.z;
-                    g3.x += gc.x; g3.y += gc.y; g3.z += gc.z;
-                }
-                gv[0] = i1 == 0 ? g1 : (i1 == 1 ? g3 : g2);
-                gv[1] = i1 == 0 ? g2 : (i1 == 1 ? g1 : g3);
-                gv[2] = i1 == 0 ? g3 : (i1 == 1 ? g2 : g1);
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if (gv[i].x != 0.f || gv[i].y != 0.f || gv[i].z != 0.f) {
-                    const f3 w = vertex_bwd(verts, vi[i], cam, eps, gv[i]);
-                    gw[i * 3] = w.x; gw[i * 3 + 1] = w.y; gw[i * 3 + 2] = w.z;
-                }
+            clip_slot_walk(verts, vi[0], vi[1], vi[2], cam, eps, zc, persp, cd, cw + o * 2, g, [&](int i, int v, f3 gv) {
+                const f3 w = vertex_bwd(verts, v, cam, eps, gv);
+                gw[i * 3] = w.x; gw[i * 3 + 1] = w.y; gw[i * 3 + 2] = w.z;
+            });
         }
         const unsigned long long am = __ballot(act);
         if (am == 0ull) continue;

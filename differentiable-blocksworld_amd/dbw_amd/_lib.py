@@ -201,13 +201,13 @@ LENS_SIGNATURES = {
     # frames with a camera each rectified to one pinhole (csrc/lens_rectify.hip), added under revision 1 of the header
     'dbw_lens_rectify_u8': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     'dbw_lens_rectify_valid_u8': [c_i, c_i, c_i, c_p, c_p, c_p, c_p],
-    # camera pose refinement (csrc/pose_grad.hip), added under revision 1 of the header
+    # camera pose refinement (csrc/camera_grad.hip), added under revision 1 of the header
     'dbw_lens_pose_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_i, c_p],
     'dbw_lens_pose_apply': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     'dbw_lens_pose_chain': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     # the point cloud of a capture's depth maps (csrc/depth_cloud.hip), added under revision 1 of the header
     'dbw_lens_depth_cloud': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i64, c_p, c_p],
-    # intrinsics refinement (csrc/intrinsics_grad.hip), added under revision 1 of the header
+    # intrinsics refinement (csrc/camera_grad.hip), added under revision 1 of the header
     'dbw_lens_intrinsics_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_i, c_p],
     'dbw_lens_intrinsics_apply': [c_p, c_p, c_p, c_p],
     'dbw_lens_intrinsics_chain': [c_p, c_p, c_p, c_p, c_p],

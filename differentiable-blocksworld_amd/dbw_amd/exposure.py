@@ -9,10 +9,11 @@ import os
 import torch
 
 from . import ops
+from .refine import FlatRefiner, parse_entry
 
 
-class ExposureRefiner:
-    """theta (V,6) of a scene's V training views, its gradient and the two Adam moments as flat fp32 buffers on `device`.
+class ExposureRefiner(FlatRefiner):
+    """theta (V,6) of a scene's V training views, its gradient and the two Adam moments as flat fp32 buffers on `device` (refine.FlatRefiner).
     attach(batch) -> the batch with 'exposure' = theta (batch['view_ids']: its rows, distinct; 'view_ids_host', where the batch carries it,
     rides along and spares the check of the ids a wait for the device); the backward of the step leaves d loss / d theta in `grad`;
     step() is dense Adam over all V rows like torch.optim.Adam on the tensor (rows of views outside the batch have zero gradient, their
@@ -21,69 +22,40 @@ class ExposureRefiner:
     and the centring fixes it without a hyperparameter.
     adam_fn: a stand-in for ops.adam_step_ with the same signature (tests on CPU tensors: the kernel has no CPU form)."""
 
+    SAVED = ('bias', 'center')
+
     def __init__(self, n_views, device, lr=1e-3, betas=(0.9, 0.999), bias=True, center=True, eps=1e-8, adam_fn=None):
-        self.n_views, self.lr, self.betas, self.eps = int(n_views), float(lr), tuple(betas), float(eps)
+        self.n_views = int(n_views)
         self.bias, self.center = bool(bias), bool(center)
-        self.flat = torch.zeros(self.n_views * 6, dtype=torch.float32, device=device)
-        self.grad = torch.zeros_like(self.flat)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.theta = self.flat.view(self.n_views, 6).requires_grad_(True)
-        self.theta.grad = self.grad.view(self.n_views, 6)        # the backward accumulates straight into the flat buffer (parallel.FlatParams)
-        self.n_steps = 0
-        self.adam_fn = adam_fn or ops.adam_step_
+        super().__init__((self.n_views, 6), device, lr, betas, eps, adam_fn)
+        self.theta = self._param()
 
     def attach(self, batch):
         if 'view_ids' not in batch:
             raise KeyError("ExposureRefiner.attach: the batch carries no 'view_ids' (the rows of theta of its views)")
         return dict(batch, exposure=self.theta)
 
-    def step(self):
+    def _mask_grad(self):
         if not self.bias:
             self.grad.view(self.n_views, 6)[:, 3:].zero_()
-        self.n_steps += 1
-        with torch.no_grad():
-            self.adam_fn(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.n_steps, self.betas, self.eps)
-            if self.center and self.n_views > 0:
-                t = self.flat.view(self.n_views, 6)
-                t.sub_(t.mean(0, keepdim=True))
-        self.grad.zero_()                                        # (enqueued behind the update: nothing waits for it)
+
+    def _after_update(self):
+        if self.center and self.n_views > 0:
+            t = self.flat.view(self.n_views, 6)
+            t.sub_(t.mean(0, keepdim=True))
 
     def gains_biases(self):
         """-> (gains exp(g) (V,3), biases (V,3)) on the host, float64."""
         t = self.flat.detach().view(self.n_views, 6).cpu().double()
         return t[:, :3].exp(), t[:, 3:].clone()
 
-    def state_dict(self):
-        return {'theta': self.flat.detach().clone(), 'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'n_steps': self.n_steps,
-                'lr': self.lr, 'bias': self.bias, 'center': self.center}
-
-    def load_state_dict(self, state):
-        if state['theta'].numel() != self.flat.numel():
-            raise ValueError(f"exposure: a state of {state['theta'].numel() // 6} views for a refiner of {self.n_views}")
-        with torch.no_grad():
-            self.flat.copy_(state['theta'].reshape(-1))
-            self.exp_avg.copy_(state['exp_avg'].reshape(-1))
-            self.exp_avg_sq.copy_(state['exp_avg_sq'].reshape(-1))
-        self.n_steps = int(state['n_steps'])
-        self.grad.zero_()
+    def _state_mismatch(self, numel):
+        return f"exposure: a state of {numel // 6} views for a refiner of {self.n_views}"
 
 
 def parse_config(entry):
     """training.exposure of a config -> dict(lr, start_epoch, bias, center), or None where the key is absent / null / false."""
-    if entry is None or entry is False:
-        return None
-    if entry is True:
-        entry = {}
-    if not isinstance(entry, dict):
-        entry = {'lr': float(entry)}
-    unknown = set(entry) - {'lr', 'start_epoch', 'bias', 'center'}
-    if unknown:
-        raise ValueError(f'training.exposure: unknown keys {sorted(unknown)} (lr, start_epoch, bias, center)')
-    out = {'lr': float(entry.get('lr', 1e-3)), 'start_epoch': int(entry.get('start_epoch', 0)), 'bias': bool(entry.get('bias', True)),
-           'center': bool(entry.get('center', True))}
-    if not out['lr'] > 0:
-        raise ValueError(f"training.exposure.lr must be positive, got {out['lr']}")
-    return out
+    return parse_entry('exposure', entry, 1e-3, {'bias': (True, bool), 'center': (True, bool)})
 
 
 def write_exposures(refiner, run_dir, names=None):

@@ -16,12 +16,13 @@ import numpy as np
 import torch
 
 from . import ops
+from .refine import FlatRefiner, parse_entry
 
 FOCAL_MODES = ('shared', 'separate', False)
 
 
-class IntrinsicsRefiner:
-    """theta (4) of a scene's shared K0 (4,4), its gradient and the two Adam moments as flat fp32 buffers on `device`, like pose.PoseRefiner.
+class IntrinsicsRefiner(FlatRefiner):
+    """theta (4) of a scene's shared K0 (4,4), its gradient and the two Adam moments as flat fp32 buffers on `device` (refine.FlatRefiner).
     apply(batch) -> the batch with 'K_live' = ops.intrinsics_apply(K0, theta); the backward of the step leaves d loss / d theta in `grad`;
     step() is Adam on the four numbers and then clears `grad`.  focal: 'shared' -- one scale for both focal lengths: g_a_y is added into
     g_a_x before the step and a_x copied to a_y after it, so the two stay equal bit for bit --, 'separate', or False (both stay 0);
@@ -29,27 +30,23 @@ class IntrinsicsRefiner:
     adam_fn / apply_fn: stand-ins for ops.adam_step_ / ops.intrinsics_apply with the same signatures (tests on CPU tensors: the kernels have
     no CPU form)."""
 
+    SAVED = ('focal', 'principal', 'K0')
+
     def __init__(self, K0, device, lr=1e-4, betas=(0.9, 0.999), focal='shared', principal=False, eps=1e-8, adam_fn=None, apply_fn=None):
         if focal is True:
             focal = 'shared'
         if focal not in FOCAL_MODES:
             raise ValueError(f"focal: 'shared', 'separate' or False, got {focal!r}")
-        self.lr, self.betas, self.eps = float(lr), tuple(betas), float(eps)
         self.focal, self.principal = focal, bool(principal)
         self.K0 = torch.as_tensor(K0, dtype=torch.float32).reshape(-1, 4, 4)[0].detach().clone().contiguous().to(device)
-        self.flat = torch.zeros(4, dtype=torch.float32, device=device)
-        self.grad = torch.zeros_like(self.flat)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.theta = self.flat.view(4).requires_grad_(True)
-        self.theta.grad = self.grad.view(4)                      # the backward accumulates straight into the flat buffer
-        self.n_steps = 0
-        self.adam_fn = adam_fn or ops.adam_step_
+        super().__init__((4,), device, lr, betas, eps, adam_fn)
+        self.theta = self._param()
         self.apply_fn = apply_fn or ops.intrinsics_apply
 
     def apply(self, batch):
         return dict(batch, K_live=self.apply_fn(self.K0, self.theta))
 
-    def step(self):
+    def _mask_grad(self):
         g = self.grad
         if self.focal == 'shared':
             g[0:1] += g[1:2]
@@ -58,52 +55,28 @@ class IntrinsicsRefiner:
             g[0:2].zero_()
         if not self.principal:
             g[2:4].zero_()
-        self.n_steps += 1
-        with torch.no_grad():
-            self.adam_fn(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.n_steps, self.betas, self.eps)
-            if self.focal == 'shared':
-                self.flat[1:2].copy_(self.flat[0:1])
-        self.grad.zero_()                                        # (enqueued behind the update: nothing waits for it)
+
+    def _after_update(self):
+        if self.focal == 'shared':
+            self.flat[1:2].copy_(self.flat[0:1])
 
     def refined(self):
         """K' (4,4), detached."""
         with torch.no_grad():
             return self.apply_fn(self.K0, self.theta.detach()).detach()
 
-    def state_dict(self):
-        return {'theta': self.flat.detach().clone(), 'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'n_steps': self.n_steps,
-                'lr': self.lr, 'focal': self.focal, 'principal': self.principal, 'K0': self.K0.clone()}
-
-    def load_state_dict(self, state):
-        if state['theta'].numel() != 4:
-            raise ValueError(f"intrinsics_refine: a state of {state['theta'].numel()} numbers, theta has 4")
-        with torch.no_grad():
-            self.flat.copy_(state['theta'].reshape(-1))
-            self.exp_avg.copy_(state['exp_avg'].reshape(-1))
-            self.exp_avg_sq.copy_(state['exp_avg_sq'].reshape(-1))
-        self.n_steps = int(state['n_steps'])
-        self.grad.zero_()
+    def _state_mismatch(self, numel):
+        return f"intrinsics_refine: a state of {numel} numbers, theta has 4"
 
 
 def parse_config(entry):
     """training.intrinsics_refine of a config -> dict(lr, start_epoch, focal, principal), or None where the key is absent / null / false."""
-    if entry is None or entry is False:
-        return None
-    if entry is True:
-        entry = {}
-    if not isinstance(entry, dict):
-        entry = {'lr': float(entry)}
-    unknown = set(entry) - {'lr', 'start_epoch', 'focal', 'principal'}
-    if unknown:
-        raise ValueError(f'training.intrinsics_refine: unknown keys {sorted(unknown)} (lr, start_epoch, focal, principal)')
-    focal = entry.get('focal', 'shared')
-    focal = 'shared' if focal is True else (False if focal is None else focal)
-    if focal not in FOCAL_MODES:
-        raise ValueError(f"training.intrinsics_refine.focal: 'shared', 'separate' or false, got {focal!r}")
-    out = {'lr': float(entry.get('lr', 1e-4)), 'start_epoch': int(entry.get('start_epoch', 0)), 'focal': focal, 'principal': bool(entry.get('principal', False))}
-    if not out['lr'] > 0:
-        raise ValueError(f"training.intrinsics_refine.lr must be positive, got {out['lr']}")
-    return out
+    def focal_mode(focal):
+        focal = 'shared' if focal is True else (False if focal is None else focal)
+        if focal not in FOCAL_MODES:
+            raise ValueError(f"training.intrinsics_refine.focal: 'shared', 'separate' or false, got {focal!r}")
+        return focal
+    return parse_entry('intrinsics_refine', entry, 1e-4, {'focal': ('shared', focal_mode), 'principal': (False, bool)})
 
 
 def pixels(K, size):

@@ -233,19 +233,26 @@ def project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z
     return g
 
 
-def project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z_clip=0.001, perspective_correct=True, out=None):
-    """dbw_lens_pose_grad: the gradient of the clipped faces with respect to each view's camera, -> (g_R (B,3,3), g_T (B,3)).  The same
-    per-slot work as project_clip_bwd, summed over the slots of a view instead of over the views (csrc/pose_grad.hip; fixed summation
-    order, no atomics).  out=(g_R, g_T): the sums are ADDED to these (the second pass over the same views) and the pair is returned."""
+def _camera_grad(fn, outs, accumulate, verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps, z_clip, perspective_correct):
+    """The call behind project_clip_bwd_cam and project_clip_bwd_k (csrc/camera_grad.hip): `fn` with its workspace, writing the tensors
+    `outs`, or adding to them where `accumulate`."""
     _lib.family('lens')
     B, V, F_ = R.shape[0], verts.shape[0], faces_i32.shape[0]
+    ws_bytes = int(getattr(_lib.load(), fn + '_workspace_bytes')(B, F_))
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=verts.device)
+    _lib.call(fn, _ptr(verts), _ptr(faces_i32), _ptr(R), _ptr(T), _ptr(Kmat), B, V, F_, float(eps), float(z_clip or 0.0),
+              int(perspective_correct), _ptr(cl['num_faces']), _ptr(cl['c2o']), _ptr(cl['clip_code']), _ptr(cl['clip_w']), _ptr(g_face_verts),
+              _ptr(ws), ws_bytes, *[_ptr(t) for t in outs], int(accumulate), _stream(verts))
+
+
+def project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z_clip=0.001, perspective_correct=True, out=None):
+    """dbw_lens_pose_grad: the gradient of the clipped faces with respect to each view's camera, -> (g_R (B,3,3), g_T (B,3)).  The same
+    per-slot work as project_clip_bwd, summed over the slots of a view instead of over the views (csrc/camera_grad.hip; fixed summation
+    order, no atomics).  out=(g_R, g_T): the sums are ADDED to these (the second pass over the same views) and the pair is returned."""
+    B = R.shape[0]
     g_R, g_T = out if out is not None else (torch.empty(B, 3, 3, dtype=torch.float32, device=verts.device),
                                             torch.empty(B, 3, dtype=torch.float32, device=verts.device))
-    ws_bytes = int(_lib.load().dbw_lens_pose_grad_workspace_bytes(B, F_))
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=verts.device)
-    _lib.call('dbw_lens_pose_grad', _ptr(verts), _ptr(faces_i32), _ptr(R), _ptr(T), _ptr(Kmat), B, V, F_, float(eps), float(z_clip or 0.0),
-              int(perspective_correct), _ptr(cl['num_faces']), _ptr(cl['c2o']), _ptr(cl['clip_code']), _ptr(cl['clip_w']), _ptr(g_face_verts),
-              _ptr(ws), ws_bytes, _ptr(g_R), _ptr(g_T), int(out is not None), _stream(verts))
+    _camera_grad('dbw_lens_pose_grad', (g_R, g_T), out is not None, verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps, z_clip, perspective_correct)
     return g_R, g_T
 
 
@@ -257,18 +264,12 @@ def _cam_grads(ctx, iR, g_R, g_T):
 def project_clip_bwd_k(verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps=1e-8, z_clip=0.001, perspective_correct=True, out=None):
     """dbw_lens_intrinsics_grad: the gradient of the clipped faces with respect to the pinhole matrix the views share, -> g_K (4,4), the full
     gradient of the matrix (row 2, which the projection never reads, is 0).  The per-slot work of project_clip_bwd, summed over the slots of
-    every view (csrc/intrinsics_grad.hip; fixed summation order, no atomics).  out=g_K: the sum is ADDED to it (the second pass over the
+    every view (csrc/camera_grad.hip; fixed summation order, no atomics).  out=g_K: the sum is ADDED to it (the second pass over the
     same views) and it is returned."""
-    _lib.family('lens')
-    B, V, F_ = R.shape[0], verts.shape[0], faces_i32.shape[0]
     g_K = out if out is not None else torch.empty(4, 4, dtype=torch.float32, device=verts.device)
-    if B == 0:
+    if R.shape[0] == 0:
         return g_K if out is not None else g_K.zero_()
-    ws_bytes = int(_lib.load().dbw_lens_intrinsics_grad_workspace_bytes(B, F_))
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=verts.device)
-    _lib.call('dbw_lens_intrinsics_grad', _ptr(verts), _ptr(faces_i32), _ptr(R), _ptr(T), _ptr(Kmat), B, V, F_, float(eps), float(z_clip or 0.0),
-              int(perspective_correct), _ptr(cl['num_faces']), _ptr(cl['c2o']), _ptr(cl['clip_code']), _ptr(cl['clip_w']), _ptr(g_face_verts),
-              _ptr(ws), ws_bytes, _ptr(g_K), int(out is not None), _stream(verts))
+    _camera_grad('dbw_lens_intrinsics_grad', (g_K,), out is not None, verts, faces_i32, R, T, Kmat, cl, g_face_verts, eps, z_clip, perspective_correct)
     return g_K
 
 

@@ -11,12 +11,13 @@ import numpy as np
 import torch
 
 from . import ops
+from .refine import FlatRefiner, parse_entry
 
 FLIP = np.array([-1.0, 1.0, -1.0])            # dataset.CustomScene: OpenGL camera axes -> the renderer's (PyTorch3D's)
 
 
-class PoseRefiner:
-    """delta (V,6) of a scene's V training views, its gradient and the two Adam moments as flat fp32 buffers on `device`.
+class PoseRefiner(FlatRefiner):
+    """delta (V,6) of a scene's V training views, its gradient and the two Adam moments as flat fp32 buffers on `device` (refine.FlatRefiner).
     apply(batch) -> the batch with R, T refined through ops.pose_apply (batch['view_ids']: the rows, distinct; 'view_ids_host', where the
     batch carries it, is the same on the host and spares the check a wait for the device -- whoever builds the batch guarantees that the
     two are equal, ops.pose_apply does not compare them); the backward of the step
@@ -25,16 +26,14 @@ class PoseRefiner:
     adam_fn / apply_fn: stand-ins for ops.adam_step_ / ops.pose_apply with the same signatures (tests on CPU tensors: the kernels have no
     CPU form)."""
 
+    STATE_KEY = 'delta'
+    SAVED = ('rot', 'trans')
+
     def __init__(self, n_views, device, lr=1e-4, betas=(0.9, 0.999), rot=True, trans=True, eps=1e-8, adam_fn=None, apply_fn=None):
-        self.n_views, self.lr, self.betas, self.eps = int(n_views), float(lr), tuple(betas), float(eps)
+        self.n_views = int(n_views)
         self.rot, self.trans = bool(rot), bool(trans)
-        self.flat = torch.zeros(self.n_views * 6, dtype=torch.float32, device=device)
-        self.grad = torch.zeros_like(self.flat)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.delta = self.flat.view(self.n_views, 6).requires_grad_(True)
-        self.delta.grad = self.grad.view(self.n_views, 6)        # the backward accumulates straight into the flat buffer (parallel.FlatParams)
-        self.n_steps = 0
-        self.adam_fn = adam_fn or ops.adam_step_
+        super().__init__((self.n_views, 6), device, lr, betas, eps, adam_fn)
+        self.delta = self._param()
         self.apply_fn = apply_fn or ops.pose_apply
 
     def apply(self, batch):
@@ -44,16 +43,12 @@ class PoseRefiner:
         R, T = self.apply_fn(batch['R'], batch['T'], self.delta, batch['view_ids'], **extra)
         return dict(batch, R=R, T=T)
 
-    def step(self):
+    def _mask_grad(self):
         g = self.grad.view(self.n_views, 6)
         if not self.rot:
             g[:, :3].zero_()
         if not self.trans:
             g[:, 3:].zero_()
-        self.n_steps += 1
-        with torch.no_grad():
-            self.adam_fn(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.n_steps, self.betas, self.eps)
-        self.grad.zero_()                                        # (enqueued behind the update: nothing waits for it)
 
     def refined(self, R0, T0):
         """All V refined poses from the V given ones (in the order of delta's rows), detached."""
@@ -62,37 +57,13 @@ class PoseRefiner:
             R, T = self.apply_fn(R0, T0, self.delta.detach(), ids)
         return R, T
 
-    def state_dict(self):
-        return {'delta': self.flat.detach().clone(), 'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'n_steps': self.n_steps,
-                'lr': self.lr, 'rot': self.rot, 'trans': self.trans}
-
-    def load_state_dict(self, state):
-        if state['delta'].numel() != self.flat.numel():
-            raise ValueError(f"pose_refine: a state of {state['delta'].numel() // 6} views for a refiner of {self.n_views}")
-        with torch.no_grad():
-            self.flat.copy_(state['delta'].reshape(-1))
-            self.exp_avg.copy_(state['exp_avg'].reshape(-1))
-            self.exp_avg_sq.copy_(state['exp_avg_sq'].reshape(-1))
-        self.n_steps = int(state['n_steps'])
-        self.grad.zero_()
+    def _state_mismatch(self, numel):
+        return f"pose_refine: a state of {numel // 6} views for a refiner of {self.n_views}"
 
 
 def parse_config(entry):
     """training.pose_refine of a config -> dict(lr, start_epoch, rot, trans), or None where the key is absent / null / false."""
-    if entry is None or entry is False:
-        return None
-    if entry is True:
-        entry = {}
-    if not isinstance(entry, dict):
-        entry = {'lr': float(entry)}
-    unknown = set(entry) - {'lr', 'start_epoch', 'rot', 'trans'}
-    if unknown:
-        raise ValueError(f'training.pose_refine: unknown keys {sorted(unknown)} (lr, start_epoch, rot, trans)')
-    out = {'lr': float(entry.get('lr', 1e-4)), 'start_epoch': int(entry.get('start_epoch', 0)), 'rot': bool(entry.get('rot', True)),
-           'trans': bool(entry.get('trans', True))}
-    if not out['lr'] > 0:
-        raise ValueError(f"training.pose_refine.lr must be positive, got {out['lr']}")
-    return out
+    return parse_entry('pose_refine', entry, 1e-4, {'rot': (True, bool), 'trans': (True, bool)})
 
 
 def _rodrigues64(w):

@@ -102,7 +102,7 @@ int dbw_lens_pose_apply(const float *R0, const float *T0, const float *delta, co
 int dbw_lens_pose_chain(const float *R0, const float *T0, const float *delta, const int32_t *ids, int B, int V, const float *grad_R,
                         const float *grad_T, float *grad_delta, dbw_stream_t stream);
 
-/* Intrinsics refinement, added under revision 1 of this header (csrc/intrinsics_grad.hip, arithmetic: csrc/intrinsics_math.h).  Kmat (4,4)
+/* Intrinsics refinement, added under revision 1 of this header (csrc/camera_grad.hip, arithmetic: csrc/intrinsics_math.h).  Kmat (4,4)
  * row-major is the pinhole matrix the views share: px, py, pw of a view-space point come from its rows 0, 1 and 3, row 2 is never read.
  *
  * dbw_lens_intrinsics_grad: the gradient of the clipped faces of B views with respect to Kmat.  The arguments up to workspace_bytes are

@@ -37,34 +37,20 @@ int host_project_clip(const float *verts, const int *faces, const float *R, cons
     return 0;
 }
 
-// the backward of one view: gverts (V,3) += d (sum fvc * g) / d verts, the way project_clip_bwd_kernel does it per clipped slot
+// the backward of one view: gverts (V,3) += d (sum fvc * g) / d verts, through the slot walk project_clip_bwd_kernel compiles
 int host_project_clip_bwd(const float *verts, const int *faces, const float *R, const float *T, const float *Kmat, int b, int F, float eps,
                           float zc, int persp, int n, const int *c2o, const int *code, const float *cw, const float *g, float *gverts) {
     Cam cam;
     load_cam(R, T, Kmat, b, cam);
     for (int j = 0; j < n; ++j) {
         const long long o = (long long)b * 2 * F + j;
-        const int f = c2o[o], cd = code[o];
-        const int vi[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-        const f3 ga{g[o * 9], g[o * 9 + 1], g[o * 9 + 2]}, gb{g[o * 9 + 3], g[o * 9 + 4], g[o * 9 + 5]}, gc{g[o * 9 + 6], g[o * 9 + 7], g[o * 9 + 8]};
-        f3 gv[3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-        if (cd < 0) { gv[0] = ga; gv[1] = gb; gv[2] = gc; }
-        else {
-            const int i1 = cd & 3, kind = cd >> 2;
-            f3 q[3];
-            for (int i = 0; i < 3; ++i) q[i] = project(verts + (long long)vi[i] * 3, cam, eps).ndc;
-            const f3 P1 = q[i1], P2 = q[(i1 + 1) % 3], P3 = q[(i1 + 2) % 3];
-            const float w2 = cw[o * 2], w3 = cw[o * 2 + 1];
-            f3 g1{0.f, 0.f, 0.f}, g2{0.f, 0.f, 0.f}, g3{0.f, 0.f, 0.f};
-            if (kind == 0) { clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2); clip_point_bwd(P1, P3, zc, persp, w3, gb, g1, g3); g1.x += gc.x; g1.y += gc.y; g1.z += gc.z; }
-            else if (kind == 1) { clip_point_bwd(P1, P2, zc, persp, w2, ga, g1, g2); g2.x += gb.x; g2.y += gb.y; g2.z += gb.z; clip_point_bwd(P1, P3, zc, persp, w3, gc, g1, g3); }
-            else { clip_point_bwd(P1, P3, zc, persp, w3, ga, g1, g3); g2.x += gb.x; g2.y += gb.y; g2.z += gb.z; g3.x += gc.x; g3.y += gc.y; g3.z += gc.z; }
-            gv[i1] = g1; gv[(i1 + 1) % 3] = g2; gv[(i1 + 2) % 3] = g3;
-        }
-        for (int i = 0; i < 3; ++i) {
-            const f3 w = vertex_bwd(verts, vi[i], cam, eps, gv[i]);
-            gverts[vi[i] * 3] += w.x; gverts[vi[i] * 3 + 1] += w.y; gverts[vi[i] * 3 + 2] += w.z;
-        }
+        const int f = c2o[o];
+        float g9[9];
+        for (int i = 0; i < 9; ++i) g9[i] = g[o * 9 + i];
+        clip_slot_walk(verts, faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2], cam, eps, zc, persp, code[o], cw + o * 2, g9, [&](int, int vi, f3 gv) {
+            const f3 w = vertex_bwd(verts, vi, cam, eps, gv);
+            gverts[vi * 3] += w.x; gverts[vi * 3 + 1] += w.y; gverts[vi * 3 + 2] += w.z;
+        });
     }
     return 0;
 }

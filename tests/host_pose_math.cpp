@@ -1,4 +1,4 @@
-// Checker-side build of the camera pose refinement arithmetic (differentiable-blocksworld_amd/csrc/pose_math.h, the header pose_grad.hip
+// Checker-side build of the camera pose refinement arithmetic (differentiable-blocksworld_amd/csrc/pose_math.h, the header camera_grad.hip
 // compiles) for the host.  tests/test_host_pose_math.py holds the camera gradient to autograd of the oracle and to the existing vertex
 // backward, and the Rodrigues forward / backward to a float64 restatement, without a GPU; tests/test_gpu_pose.py holds the kernels to this
 // build.  With -DPOSE_MATH_MAIN the file is a program of its own (its main walks the same cases on exactly sized heap buffers) for
@@ -10,14 +10,14 @@
 #include <vector>
 
 #include "../differentiable-blocksworld_amd/csrc/pose_math.h"
+#include "host_slot_loop.h"
 
 using namespace dbw;
 
 extern "C" {
 
-// dbw_lens_pose_grad for B views, slot by slot in fp32: gR (B,3,3), gT (B,3) written.  abs_terms (B,12) or null: per component the sum of
-// the |terms| of the sum (a term = what one vertex of one slot adds), for the bound of an fp32 sum in the tests; with it n_terms (B): the
-// number of terms of view b's sums (vertices whose gradient is not all zero: the others add nothing).
+// dbw_lens_pose_grad for B views, slot by slot in fp32: gR (B,3,3), gT (B,3) written.  abs_terms (B,12) or null, with it n_terms (B): the
+// bookkeeping of host_slot_loop.h, per view.
 int host_pose_grad(const float *verts, const int *faces, const float *R, const float *T, const float *Kmat, int B, int F, float eps, float zc,
                    int persp, const int *num_faces, const int *c2o, const int *code, const float *cw, const float *g, float *gR, float *gT,
                    double *abs_terms, int *n_terms) {
@@ -25,31 +25,8 @@ int host_pose_grad(const float *verts, const int *faces, const float *R, const f
         Cam cam;
         load_cam(R, T, Kmat, b, cam);
         float acc[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int j = 0; j < num_faces[b]; ++j) {
-            const long long o = (long long)b * 2 * F + j;
-            float g9[9];
-            bool any = false;
-            for (int i = 0; i < 9; ++i) { g9[i] = g[o * 9 + i]; any |= (g9[i] != 0.f); }
-            if (!any) continue;
-            const int f = c2o[o];
-            float one[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            slot_cam_grad(verts, faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2], cam, eps, zc, persp, code[o], cw[o * 2], cw[o * 2 + 1], g9, acc);
-            if (abs_terms) {
-                // the terms of this slot, vertex by vertex: the same calls with one vertex's gradient at a time
-                const f3 ga{g9[0], g9[1], g9[2]}, gb{g9[3], g9[4], g9[5]}, gc{g9[6], g9[7], g9[8]};
-                f3 q[3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-                if (code[o] >= 0)
-                    for (int i = 0; i < 3; ++i) q[i] = project(verts + (long long)faces[f * 3 + i] * 3, cam, eps).ndc;
-                f3 gv[3];
-                clip_slot_bwd(code[o], q[0], q[1], q[2], zc, persp, cw[o * 2], cw[o * 2 + 1], ga, gb, gc, gv[0], gv[1], gv[2]);
-                for (int i = 0; i < 3; ++i) {
-                    if (n_terms && (gv[i].x != 0.f || gv[i].y != 0.f || gv[i].z != 0.f)) ++n_terms[b];
-                    for (int c = 0; c < 12; ++c) one[c] = 0.f;
-                    vertex_cam_grad(verts, faces[f * 3 + i], cam, eps, gv[i], one);
-                    for (int c = 0; c < 12; ++c) abs_terms[b * 12 + c] += std::fabs((double)one[c]);
-                }
-            }
-        }
+        host_view_slots<CamGradSink>(verts, faces, cam, b, F, eps, zc, persp, num_faces[b], c2o, code, cw, g, acc, abs_terms ? abs_terms + b * 12 : nullptr,
+                                     n_terms ? n_terms + b : nullptr, nullptr);
         for (int c = 0; c < 9; ++c) gR[b * 9 + c] = acc[c];
         for (int c = 0; c < 3; ++c) gT[b * 3 + c] = acc[9 + c];
     }

@@ -37,7 +37,7 @@ def sanitized_program():
     os.makedirs(out, exist_ok=True)
     src, exe = os.path.join(HERE, 'host_pose_math.cpp'), os.path.join(out, 'host_pose_math_san')
     csrc = os.path.join(HERE, '..', 'differentiable-blocksworld_amd', 'csrc')
-    deps = [src] + [os.path.join(csrc, h) for h in ('pose_math.h', 'camera_math.h', 'raster_math.h')]
+    deps = [src, os.path.join(HERE, 'host_slot_loop.h')] + [os.path.join(csrc, h) for h in ('pose_math.h', 'camera_math.h', 'raster_math.h')]
     if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in deps):
         subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
                                '-DPOSE_MATH_MAIN', src, '-o', exe])

@@ -1,4 +1,4 @@
-"""CPU tests of the intrinsics refinement arithmetic: csrc/intrinsics_math.h, the header csrc/intrinsics_grad.hip compiles,
+"""CPU tests of the intrinsics refinement arithmetic: csrc/intrinsics_math.h, the header csrc/camera_grad.hip compiles,
 built for the host by g++ (tests/host_intrinsics_math.cpp).  The gradient of the clipped faces with respect to K against autograd of the
 oracle's transform_to_ndc + clip_faces on a scene where every clipping case occurs, and against a float64 sum over the vertex backward's
 own intermediate quantities; the parameterisation and its chain rule against a float64 restatement; the same file once as a program of its

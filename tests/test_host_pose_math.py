@@ -1,4 +1,4 @@
-"""CPU tests of the camera pose refinement arithmetic: csrc/pose_math.h, the header csrc/pose_grad.hip compiles, built for
+"""CPU tests of the camera pose refinement arithmetic: csrc/pose_math.h, the header csrc/camera_grad.hip compiles, built for
 the host by g++ (tests/host_pose_math.cpp).  The gradient of the clipped faces with respect to R and T against autograd of the oracle's
 transform_to_ndc + clip_faces on a scene where every clipping case occurs, and against the existing vertex backward; the Rodrigues forward
 and backward against a float64 restatement; the same file once as a program of its own under -fsanitize=address,undefined.

@@ -1,8 +1,8 @@
-"""Times the intrinsics refinement (csrc/intrinsics_grad.hip, dbw_amd/intrinsics.py) on the GPU.
+"""Times the intrinsics refinement (csrc/camera_grad.hip, dbw_amd/intrinsics.py) on the GPU.
 
   kernels  the blocks of bench.py's workload (`--blocks`, default 10 and 80: 800 / 6,400 faces, 1,600 / 12,800 clipped-face slots) seen from
            `--views` cameras (default 49: config 2), a random gradient on every slot:
-             intrinsics_grad    dbw_lens_intrinsics_grad (intrinsics_grad_kernel + intrinsics_finish_kernel), workspace allocated once
+             intrinsics_grad    dbw_lens_intrinsics_grad (camera_partials_kernel<KGradSink> + intrinsics_finish_kernel), workspace allocated once
              pose_grad          dbw_lens_pose_grad on the same inputs: the same per-slot work, summed per view
              project_clip_bwd   dbw_project_clip_bwd on the same inputs: the same per-slot work, summed over the views
              apply_chain        dbw_lens_intrinsics_apply + dbw_lens_intrinsics_chain

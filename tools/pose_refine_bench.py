@@ -1,8 +1,8 @@
-"""Times the camera pose refinement (csrc/pose_grad.hip, dbw_amd/pose.py) on the GPU.
+"""Times the camera pose refinement (csrc/camera_grad.hip, dbw_amd/pose.py) on the GPU.
 
   kernels  the blocks of bench.py's workload (`--blocks`, default 10: 6,400 faces, 12.8 k clipped-face slots) seen from `--views` cameras
            (default 49: config 2), a random gradient on every slot:
-             pose_grad          dbw_lens_pose_grad (pose_grad_kernel + pose_finish_kernel), workspace allocated once
+             pose_grad          dbw_lens_pose_grad (camera_partials_kernel<CamGradSink> + pose_finish_kernel), workspace allocated once
              project_clip_bwd   dbw_project_clip_bwd on the same inputs: the same per-slot work, summed over the views instead
              pose_apply_chain   dbw_lens_pose_apply + dbw_lens_pose_chain for the same views
            `inner` calls between two device synchronisations per repeat, the legs alternated, the median and the spread over `--repeats`.
