@@ -147,11 +147,16 @@ EVAL_SIGNATURES = {
     'dbw_eval_plane_fit': [c_p, c_i64, c_i, c_i, c_f, c_i64, c_p, c_p, c_f, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     # k-means with per-cluster PCA (csrc/cluster_fit.hip), added under revision 1 of the header
     'dbw_eval_cluster_fit': [c_p, c_i64, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    # the surface term (csrc/surface_term.hip), added under revision 1 of the header
+    'dbw_eval_surface_fwd': [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_d, c_f, c_f, c_i, c_p, c_p, c_p, c_p],
+    'dbw_eval_surface_bwd': [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_f, c_f, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
 }
 EVAL_OTHER_SIGNATURES = {
     'dbw_eval_plane_workspace_bytes': (c_sz, [c_i64, c_i]),
     'dbw_eval_cluster_workspace_bytes': (c_sz, [c_i64, c_i]),
+    'dbw_eval_surface_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i]),
 }
+EVAL_SURFACE_SEGMENT = header_define('dbw_eval.h', 'DBW_EVAL_SURFACE_SEGMENT')
 EVAL_PLANE_ORTHOGONAL, EVAL_PLANE_VERTICAL = 0, 1             # DBW_EVAL_PLANE_* of include/dbw_eval.h
 EVAL_ABI_VERSION = header_define('dbw_eval.h', 'DBW_EVAL_ABI_VERSION')
 

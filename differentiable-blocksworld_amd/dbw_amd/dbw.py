@@ -44,6 +44,40 @@ _CRITERIA = {'mse': F.mse_loss, 'l2': F.mse_loss, 'l1': F.l1_loss, 'huber': F.sm
 _TV_NORMS = {'l1': lambda t: t.abs().sum(-1), 'l2': lambda t: safe_pow(t.pow(2).sum(-1), 0.5), 'l2sq': lambda t: t.pow(2).sum(-1)}
 
 
+SURFACE_KEYS = ('points', 'tau', 'back', 'ground', 'start_epoch', 'max_cloud')
+SURFACE_DEFAULTS = {'points': 16384, 'tau': 0.1, 'back': 0.5, 'ground': True, 'start_epoch': 1, 'max_cloud': 262144}
+SURFACE_THIN_SEED = 20240917        # the permutation that thins a cloud above max_cloud
+
+
+def parse_surface_config(entry):
+    """model.loss.surface -> {points, tau, back, ground, start_epoch, max_cloud} with the defaults filled in; unknown keys are refused.
+    points: cloud points drawn per step (0: all of them, in order); tau: the truncation distance; back: the weight of the direction from
+    the block vertices to the cloud; ground: whether the ground's faces are part of the surface; start_epoch: the first epoch with the term;
+    max_cloud: a larger cloud is thinned to this many points when it is set.  The defaults are design choices in the normalised frame, where
+    the cameras sit in [-1, 1]^3 -- a tenth of the rig's half-extent as the reach of a point, 16384 points as a step's sample, the back
+    direction at half weight because a block's unobserved sides have no points to answer to -- and NOT measured values."""
+    from collections.abc import Mapping
+    if entry is None:
+        entry = {}
+    if not isinstance(entry, Mapping):
+        raise ValueError(f"model.loss.surface: a mapping of {', '.join(SURFACE_KEYS)}, got {entry!r}")
+    bad = [k for k in entry if k not in SURFACE_KEYS]
+    if bad:
+        raise ValueError(f"model.loss.surface.{bad[0]}: not one of {', '.join(SURFACE_KEYS)}")
+    o = dict(SURFACE_DEFAULTS, **entry)
+    o.update(points=int(o['points']), tau=float(o['tau']), back=float(o['back']), ground=bool(o['ground']), start_epoch=int(o['start_epoch']),
+             max_cloud=int(o['max_cloud']))
+    if o['points'] < 0 or o['points'] > (1 << 24):
+        raise ValueError(f"model.loss.surface.points: in [0, 2^24], got {o['points']}")
+    if not (0 < o['tau'] < float('inf')):
+        raise ValueError(f"model.loss.surface.tau: positive, got {o['tau']}")
+    if not (0 <= o['back'] < float('inf')):
+        raise ValueError(f"model.loss.surface.back: non-negative, got {o['back']}")
+    if not (1 <= o['max_cloud'] <= (1 << 24)):
+        raise ValueError(f"model.loss.surface.max_cloud: in [1, 2^24], got {o['max_cloud']}")
+    return o
+
+
 class DifferentiableBlocksWorld(nn.Module):
     name = 'dbw'
 
@@ -229,6 +263,9 @@ class DifferentiableBlocksWorld(nn.Module):
         weights = {'rgb': kwargs.pop('rgb_weight', 1.0), 'perceptual': kwargs.pop('perceptual_weight', 0),
                    'parsimony': kwargs.pop('parsimony_weight', 0), 'scale': kwargs.pop('scale_weight', 0),
                    'tv': kwargs.pop('tv_weight', 0), 'overlap': kwargs.pop('overlap_weight', 0)}
+        # the surface term, last: the names and the order of every config without it stay what they were
+        weights['surface'] = kwargs.pop('surface_weight', 0)
+        self.surface_cfg = parse_surface_config(kwargs.pop('surface', None))
         name = kwargs.pop('name', 'mse')
         # loss.py:22, dbw.py:155,163: 'lpips' (a third-party network: set_perceptual) or 'ssim', the built-in term (metrics.SSIMTerm)
         self.perceptual_name = kwargs.pop('perceptual_name', 'lpips')
@@ -273,7 +310,7 @@ class DifferentiableBlocksWorld(nn.Module):
     def release_graph(self):
         """Drop the tensors cached by the last forward (they keep its autograd graph -- and the parameters' AccumulateGrad
         nodes, which are bound to the stream they were created on -- alive)."""
-        for n in ('_alpha', '_alpha_full', '_blocks_maps', '_bkg_maps', '_ground_maps', '_keep_mask'):
+        for n in ('_alpha', '_alpha_full', '_blocks_maps', '_bkg_maps', '_ground_maps', '_keep_mask', '_surface_ground_v', '_surface_block_v'):
             if hasattr(self, n):
                 setattr(self, n, None)
 
@@ -342,6 +379,8 @@ class DifferentiableBlocksWorld(nn.Module):
         S_w, R_w, T_w = self._world_consts()
         ph = phase.phase_of(self, self.training)
         ground_v = ops.posed_mesh(self.R_6d_ground, self.T_ground, self._ground_base, S_w, R_w, T_w)
+        if 'surface' in self.loss_weights:
+            self._surface_ground_v = ground_v       # the surface term reads the render's own vertices (compute_losses)
         bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, ph.decim_env)
         g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, ph.decim_env)
         verts = torch.cat([self.sky_world_verts(), ground_v], 0)
@@ -380,11 +419,15 @@ class DifferentiableBlocksWorld(nn.Module):
                     self._alpha = self._alpha[mask_i32.bool()]
         maps_all, self._blocks_maps = ops.texture_prep(self.textures, ph.decim_blocks)
         self._keep_mask = keep
+        if 'surface' in self.loss_weights:
+            self._surface_block_v = None
         if nb == 0:
             return None
         S_w, R_w, T_w = self._world_consts()
         verts = ops.sq_blocks(self.sq_eps, self.S, self.R_6d, self.T, self._trig, keep, nb, self.ratio_block_scene,
                               self.scale_min, S_w, R_w, T_w, dense=not self.sync_free)
+        if 'surface' in self.loss_weights:
+            self._surface_block_v = verts
         maps = maps_all if (keep is None or self.sync_free) else maps_all[keep.bool()]
         F_ = nb * self.BNF
         # (a view of the full table: its row 0 announces all n_blocks rows, which stay readable behind the nb rows in use)
@@ -502,7 +545,8 @@ class DifferentiableBlocksWorld(nn.Module):
 
         @contextlib.contextmanager
         def ctx():
-            names = ('_alpha', '_alpha_full', '_blocks_maps', '_bkg_maps', '_ground_maps', '_keep_mask', '_blocks_decimated')
+            names = ('_alpha', '_alpha_full', '_blocks_maps', '_bkg_maps', '_ground_maps', '_keep_mask', '_blocks_decimated', '_surface_ground_v',
+                     '_surface_block_v')
             saved = {n: getattr(self, n) for n in names if hasattr(self, n)}
             sf, nz, on = self.sync_free, self._noise_override, self.opacity_noise
             self.sync_free = False
@@ -871,13 +915,99 @@ class DifferentiableBlocksWorld(nn.Module):
             value = self.perceptual_fn(imgs, rec)
         return self.loss_weights['perceptual'] * phase.late_factor(coarse) * share * value
 
+    # ------------------------------------------------------------------------------------------------ the surface term
+    @torch.no_grad()
+    def set_surface_points(self, points):
+        """The capture's cloud (N,3), in the normalised frame of R, T and of the posed meshes, for the surface term: kept as a non-persistent
+        buffer (a checkpoint does not carry it: the cloud is rebuilt from the scene).  More than surface.max_cloud points are thinned to the
+        first max_cloud of a seeded permutation; points with a non-finite coordinate are dropped."""
+        p = torch.as_tensor(points).detach().to(device=self.alpha_logit.device, dtype=torch.float32).reshape(-1, 3)
+        p = p[torch.isfinite(p).all(1)]
+        cap = self.surface_cfg['max_cloud']
+        if p.shape[0] > cap:
+            perm = torch.randperm(p.shape[0], generator=torch.Generator().manual_seed(SURFACE_THIN_SEED))[:cap]
+            p = p[perm.to(p.device)]
+        if p.shape[0] == 0:
+            raise ValueError('set_surface_points: no finite point')
+        self._buffers.pop('_surface_points', None)
+        self.register_buffer('_surface_points', p.contiguous(), persistent=False)
+        return p.shape[0]
+
+    def _surface_tables(self, nb, ground, dev):
+        """Constant tables of the term for `nb` packed blocks: faces (F,3) int32 into [ground vertices, block vertices], the groups' face
+        offsets, each vertex's row of the opacities (-1 on the ground), a one for the ground's entry of group_keep.  The faces index the
+        vertices by construction (asserted once, here, on the host)."""
+        key = (nb, ground, str(dev))
+        cache = self.__dict__.setdefault('_surface_table_cache', {})
+        if key not in cache:
+            nvb, nv = self._bkg_verts.shape[0], self._block_nv
+            gf = (self._env_faces[self._n_bkg_faces:].cpu() - nvb) if ground else torch.zeros(0, 3, dtype=torch.int32)
+            ngv = self._ground_base.shape[0] if ground else 0
+            bf = self._block_faces_all[:nb * self.BNF].cpu() + ngv
+            faces = torch.cat([gf, bf], 0).to(torch.int32).contiguous()
+            fg = torch.tensor(([0, len(gf)] if ground else [0]) + [len(gf) + (k + 1) * self.BNF for k in range(nb)], dtype=torch.int32)
+            vg = torch.cat([torch.full((ngv,), -1), torch.arange(nb).repeat_interleave(nv)]).to(torch.int32)
+            assert faces.numel() and 0 <= int(faces.min()) and int(faces.max()) < len(vg)
+            cache[key] = (faces.to(dev), fg.to(dev), vg.to(dev), torch.ones(1, dtype=torch.int32, device=dev))
+        return cache[key]
+
+    def _surface_term(self, dev):
+        """weight * the term on the vertex tensors the last build_env_scene / build_blocks_scene produced (no second sq_blocks launch)."""
+        c, wgt = self.surface_cfg, float(self.loss_weights['surface'])
+        if self.world_size > 1:
+            raise NotImplementedError('the surface term under data parallelism: every rank would add the whole term, and the ranks do not '
+                                      'share out its points')
+        pts = getattr(self, '_surface_points', None)
+        if pts is None:
+            raise RuntimeError('surface_weight > 0 needs the capture\'s point cloud: model.set_surface_points(points) (train.py feeds '
+                               'scene.cloud() of a custom scene)')
+        if self.cur_epoch + 1 < c['start_epoch'] or not self.training:
+            # (before start_epoch; and in eval mode: the term is a training signal, an evaluation neither pays for the nearest-neighbour search
+            # over the cloud nor counts the term in its L_tot -- loss_surface is then 0)
+            return torch.zeros((), device=dev)
+        ground_v = getattr(self, '_surface_ground_v', None) if c['ground'] else None
+        block_v = getattr(self, '_surface_block_v', None)
+        if c['ground'] and ground_v is None:
+            raise RuntimeError('the surface term reads the vertices of the scene the forward built: call the model, not compute_losses alone')
+        if ground_v is None and block_v is None:          # no face left: every point is at tau
+            return torch.full((), wgt * c['tau'] ** 2, device=dev)
+        nb = 0 if block_v is None else block_v.reshape(-1, self._block_nv, 3).shape[0]
+        faces, face_group, vert_group, one = self._surface_tables(nb, ground_v is not None, dev)
+        parts = [v.reshape(-1, 3) for v in (ground_v, block_v) if v is not None]
+        verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        keep = self._keep_mask if (self.sync_free and nb) else None
+        if keep is not None and ground_v is not None:
+            keep = torch.cat([one, keep.to(torch.int32)])
+        back = c['back'] if nb else 0.0
+        step = getattr(self, '_rng_step', None)
+        if step is None:                                  # a model stepped by hand: its own count of training losses
+            step = self.__dict__.setdefault('_surface_calls', 0)
+            self._surface_calls = step + 1
+        return ops.surface_term(pts, verts.float().contiguous(), faces, face_group, None if keep is None else keep.contiguous(),
+                                self._alpha.float().contiguous() if nb else None, vert_group, n_points=min(c['points'], 1 << 24), tau=c['tau'],
+                                back=back, seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=int(step),
+                                weight=wgt, back_count=float(self.n_blocks * self._block_nv))
+
     def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
+        """The loss dict of _image_and_regulariser_losses (same arguments), plus -- with surface_weight > 0 -- the surface term
+        on the vertices of the scene the forward built (zero in eval mode and before surface.start_epoch); without the weight no line of it
+        runs."""
+        losses = self._image_and_regulariser_losses(imgs, rec, layers=layers, rgb_value=rgb_value, masks=masks, mask_count=mask_count, exposure=exposure)
+        if 'surface' in self.loss_weights:
+            total = losses.pop('total')
+            losses['surface'] = self._surface_term(imgs.device)
+            losses['total'] = total + losses['surface']
+        return losses
+
+    def _image_and_regulariser_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
         """masks (B,1,H,W) weights in [0, 1] with mask_count = 3 * their sum (a host number; computed with one host read when None): the
         two image terms under the validity mask -- layers must be given --, the regularisers unchanged.
         exposure = (theta (V,6), ids (B)[, ids on the host]): the per-view exposures of DESIGN.md 6s and the batch's rows of them -- both
         image terms see rec = exp(g) * composite + b (ops.composite_mse_exposure), with or without masks; layers must be given; the
         regularisers do not see theta."""
         w = self.loss_weights
+        if 'surface' in w:
+            w = {k: v for k, v in w.items() if k != 'surface'}       # (compute_losses adds that term)
         dev = imgs.device
         # (the epoch's loss factors in eval mode too; view-independent regularisers: every rank computes them identically, scaled by
         # 1 / world_size so that the sum all-reduce of gradients counts them once, SURVEY.md 8e)

@@ -1075,3 +1075,93 @@ def cluster_points(points, k, n_iter=20, init=None):
     k, n_iter, init = _cluster_args(points, k, n_iter, init)
     o = cluster_fit(points.detach().to(torch.float32).contiguous(), k, n_iter, init)
     return ClusterResult(o['centres'], o['labels'], o['counts'], o['mean'], o['cov'], o['evals'], o['axes'], o['info'][0], o['info'][1], o['info'][2])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the surface term
+def _closest_on_faces(p, tri):
+    """p (n,3), tri (F,3,3) -> (d2 (n,F), bary (n,F,3)): per face the projection onto its plane where that lies inside, else the nearest of
+    the clamped projections onto its sides (a face without area: its sides) -- the definition csrc/surface_math.h implements, in p's dtype."""
+    a, b, c = tri[None, :, 0], tri[None, :, 1], tri[None, :, 2]
+    e1, e2, q = b - a, c - a, p[:, None, :] - a
+    n = torch.linalg.cross(e1, e2)
+    nn = (n * n).sum(-1)
+    ok = nn > 0
+    den = torch.where(ok, nn, torch.ones_like(nn))
+    u = (torch.linalg.cross(q, e2.expand_as(q)) * n).sum(-1) / den
+    v = (torch.linalg.cross(e1.expand_as(q), q) * n).sum(-1) / den
+    inside = ok & (u >= 0) & (v >= 0) & (u + v <= 1)
+
+    def at(u_, v_):
+        r = q - (u_[..., None] * e1 + v_[..., None] * e2)
+        return (r * r).sum(-1)
+
+    def seg(q0, d):
+        dd = (d * d).sum(-1)
+        t = (q0 * d).sum(-1) / torch.where(dd > 0, dd, torch.ones_like(dd))
+        return torch.where(dd > 0, t, torch.zeros_like(t)).clamp(0, 1)
+
+    s1, s2, s3 = seg(q, e1), seg(q - e1, e2 - e1), seg(q - e2, -e2)
+    zero = torch.zeros_like(s1)
+    cands = [(s1, zero), (1 - s2, s2), (zero, 1 - s3)]
+    d_side = torch.stack([at(*c_) for c_ in cands], 0)
+    j = d_side.argmin(0)
+    us = torch.stack([c_[0] for c_ in cands], 0).gather(0, j[None])[0]
+    vs = torch.stack([c_[1] for c_ in cands], 0).gather(0, j[None])[0]
+    u, v = torch.where(inside, u, us), torch.where(inside, v, vs)
+    return at(u, v), torch.stack([1 - u - v, u, v], -1)
+
+
+def surface_draw(seed, step, n_points, n_cloud):
+    """The cloud indices a step draws (csrc/surface_math.h: surface_draw_index), on the host: word 0 of Philox4x32-10 with counter
+    (i, 2, step) and key seed, mod the cloud's size -> (n_points,) int64."""
+    i = np.arange(int(n_points), dtype=np.uint64)
+    c = [i, np.full_like(i, 2), np.full_like(i, int(step) & 0xffffffff), np.full_like(i, int(step) >> 32)]
+    k = [np.uint64(int(seed) & 0xffffffff), np.uint64((int(seed) >> 32) & 0xffffffff)]
+    m32 = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k[0]) & m32, p1 & m32, ((p0 >> np.uint64(32)) ^ c[3] ^ k[1]) & m32, p0 & m32]
+        k = [(k[0] + np.uint64(0x9E3779B9)) & m32, (k[1] + np.uint64(0xBB67AE85)) & m32]
+    return torch.from_numpy((c[0] % np.uint64(int(n_cloud))).astype(np.int64))
+
+
+def surface_term_torch(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, *, n_points, tau, back, seed, step, weight,
+                       back_count=None, chunk=1024):
+    """ops.surface_term in torch, in the dtype of verts, on any device: the readable statement of DESIGN.md 6u, the timing baseline of
+    tools/surface_bench.py and, in float64, the gradient reference of the tests.  Autograd gives the envelope gradient by itself: the
+    closest point is differentiated through the barycentrics of the winning face, and their derivative is orthogonal to p - c or clamped.
+    To keep exactly the stated gradient (-2 b_m (p - c), 2 a_k (x_v - nn)) the barycentrics and the nearest neighbours are detached."""
+    dt, dev = verts.dtype, verts.device
+    P = points.to(device=dev, dtype=dt)
+    N, V = P.shape[0], verts.shape[0]
+    idx = surface_draw(seed, step, n_points, N).to(dev) if n_points else torch.arange(N, device=dev)
+    fk = torch.ones(faces.shape[0], dtype=torch.bool, device=dev)
+    if group_keep is not None:
+        G = face_group.numel() - 1
+        counts = (face_group[1:] - face_group[:-1]).to(torch.int64)
+        fk = torch.repeat_interleave(group_keep.to(torch.bool), counts, output_size=faces.shape[0]) if G else fk
+    fid = fk.nonzero().flatten()
+    fc = faces.to(torch.int64)[fid]
+    t2 = float(tau) ** 2
+    total = verts.new_zeros(())
+    p_all = P[idx]
+    for s in range(0, p_all.shape[0], chunk):
+        p = p_all[s:s + chunk]
+        with torch.no_grad():
+            d2, bary = _closest_on_faces(p, verts.detach()[fc])
+            j = d2.argmin(1)
+            b = bary[torch.arange(len(j), device=dev), j]
+        c = (b[..., None] * verts[fc[j]]).sum(1)
+        d2 = ((p - c) ** 2).sum(-1)
+        total = total + torch.where(d2 < t2, d2, torch.full_like(d2, t2)).sum()
+    value = total / p_all.shape[0]
+    if back > 0:
+        sel = (vert_group >= 0).nonzero().flatten()
+        x = verts[sel]
+        with torch.no_grad():
+            nn_i = torch.cat([((x[s:s + chunk, None, :].detach() - P[None]) ** 2).sum(-1).argmin(1) for s in range(0, x.shape[0], chunk)])
+        d2 = ((x - P[nn_i]) ** 2).sum(-1)
+        rho = torch.where(d2 < t2, d2, torch.full_like(d2, t2))
+        bc = float(back_count) if back_count is not None else float(sel.numel())        # (n_blocks * BNV: the block vertices)
+        value = value + float(back) * (vert_alpha.to(dt)[vert_group[sel].to(torch.int64)] * rho).sum() / bc
+    return float(weight) * value

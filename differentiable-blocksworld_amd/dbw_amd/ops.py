@@ -1966,3 +1966,123 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), e
     """In-place fused Adam on flat fp32 buffers (torch.optim.Adam defaults; optimizer.py:6-18)."""
     _lib.call('dbw_adam_step', _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr), float(betas[0]),
               float(betas[1]), float(eps), int(step), _stream(param))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the surface term (DESIGN.md 6u)
+def _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count):
+    for t, dt, name in ((points, torch.float32, 'points'), (verts, torch.float32, 'verts'), (faces, torch.int32, 'faces'),
+                        (face_group, torch.int32, 'face_group'), (group_keep, torch.int32, 'group_keep'), (vert_alpha, torch.float32, 'vert_alpha'),
+                        (vert_group, torch.int32, 'vert_group')):
+        if t is not None:
+            _chk(t, dt, name)
+            if not t.is_contiguous():
+                raise RuntimeError(f'surface term: {name} must be contiguous')
+    if points.dim() != 2 or points.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f'surface term: points (N,3), verts (V,3), faces (F,3) expected, got {tuple(points.shape)}, {tuple(verts.shape)}, {tuple(faces.shape)}')
+    N, V, F_, G = points.shape[0], verts.shape[0], faces.shape[0], face_group.numel() - 1
+    if group_keep is not None and group_keep.numel() != G:
+        raise ValueError(f'surface term: group_keep has {group_keep.numel()} entries for {G} groups')
+    if vert_group is not None and vert_group.numel() != V:
+        raise ValueError(f'surface term: vert_group has {vert_group.numel()} entries for {V} vertices')
+    if back > 0 and (vert_alpha is None or vert_group is None):
+        raise ValueError('surface term: back > 0 needs vert_alpha and vert_group')
+    A = 0 if vert_alpha is None else vert_alpha.numel()
+    M = int(n_points) if n_points else N
+    bc = 1.0
+    if back > 0:
+        # the definition's n_blocks * BNV.  Without the constant it is counted: the vertices that belong to a block -- one host read, which
+        # a caller inside a training step avoids by passing back_count (the model does)
+        bc = float(back_count) if back_count is not None else float(int((vert_group >= 0).sum()))
+        if not bc > 0:
+            raise ValueError('surface term: back > 0 needs block vertices (vert_group >= 0) or a positive back_count')
+    return N, V, F_, G, A, M, bc
+
+
+def surface_workspace(M, F_, V, G, segment, device):
+    nbytes = _lib.family('eval').dbw_eval_surface_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
+    if nbytes == 0:
+        raise ValueError(f'surface term: sizes M={M}, F={F_}, V={V}, G={G}, segment={segment} are refused (include/dbw_eval.h)')
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+
+
+def surface_records(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, *, n_points, tau, back, seed, step, back_count=None,
+                    cull=True, segment=0, faces_host=None):
+    """dbw_eval_surface_fwd on device tensors, arguments as in include/dbw_eval.h -> (records (M,4) int32: d2 bits, face, u bits, v bits;
+    value (2,) float64: the forward mean and the back mean; the workspace, which surface_grads reads).  back_count: the constant
+    n_blocks * vertices per block (default: the vertices with vert_group >= 0, counted with one host read).  faces_host: an int32 CPU copy of faces, checked against V before the launch.  Everything is
+    enqueued on the current stream; nothing is read by the host."""
+    N, V, F_, G, A, M, bc = _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count)
+    dev = points.device
+    ws = surface_workspace(M, F_, V, G, segment, dev)
+    records = torch.empty(M, 4, dtype=torch.int32, device=dev)
+    value = torch.empty(2, dtype=torch.float64, device=dev)
+    if faces_host is not None and (faces_host.dtype != torch.int32 or faces_host.is_cuda or not faces_host.is_contiguous() or faces_host.shape != faces.shape):
+        raise ValueError('surface term: faces_host is a contiguous int32 CPU copy of faces')
+    with torch.cuda.device(dev):
+        _lib.family('eval')
+        _lib.call('dbw_eval_surface_fwd', _ptr(points), N, int(n_points or 0), int(seed), int(step), _ptr(verts), V, _ptr(faces), _ptr(faces_host), F_,
+                  _ptr(face_group), _ptr(group_keep), G, _ptr(vert_alpha), _ptr(vert_group), A, bc, float(tau), float(back), int(bool(cull)),
+                  _ptr(ws), _ptr(records), _ptr(value), _stream(points))
+    return records, value, ws
+
+
+def surface_grads(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, records, workspace, *, n_points, tau, back, seed, step,
+                  weight, grad_out=None, back_count=None, segment=0):
+    """dbw_eval_surface_bwd on what surface_records left (same arguments, same segment) -> (grad_verts (V,3), grad_alpha (A,) or None), fp32,
+    written whole.  grad_out: a one-element fp32 device tensor that multiplies both, or None."""
+    N, V, F_, G, A, M, bc = _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count)
+    dev = points.device
+    # the backward's partials are the last part of the workspace and grow with the number of segments: a workspace that surface_records
+    # sized for another segment length may be too small, and the kernels do not know its size
+    need = _lib.family('eval').dbw_eval_surface_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
+    if need == 0 or workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
+        raise ValueError(f'surface term: the workspace has {workspace.numel() * workspace.element_size()} bytes, segment={segment} needs {need}: '
+                         'give surface_records the same segment')
+    if tuple(records.shape) != (M, 4) or records.dtype != torch.int32 or not records.is_contiguous():
+        raise ValueError(f'surface term: records (M,4) int32 of surface_records expected, got {tuple(records.shape)} {records.dtype}')
+    if grad_out is not None:
+        _chk(grad_out, torch.float32, 'grad_out')
+    g_verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    g_alpha = torch.empty(A, dtype=torch.float32, device=dev) if A else None
+    with torch.cuda.device(dev):
+        _lib.family('eval')
+        _lib.call('dbw_eval_surface_bwd', _ptr(points), N, int(n_points or 0), int(seed), int(step), _ptr(verts), V, _ptr(faces), F_, G, _ptr(vert_alpha),
+                  _ptr(vert_group), A, bc, float(tau), float(back), float(weight), _ptr(grad_out), int(segment), _ptr(records), _ptr(workspace),
+                  _ptr(g_verts), _ptr(g_alpha), _stream(points))
+    return g_verts, g_alpha
+
+
+class _SurfaceTerm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, vert_alpha, points, faces, face_group, group_keep, vert_group, kw):
+        v = verts.detach().contiguous()
+        a = None if vert_alpha is None else vert_alpha.detach().contiguous()
+        records, value, ws = surface_records(points, v, faces, face_group, group_keep, a, vert_group, n_points=kw['n_points'], tau=kw['tau'],
+                                             back=kw['back'], seed=kw['seed'], step=kw['step'], back_count=kw['back_count'], segment=kw['segment'])
+        ctx.kw = kw
+        ctx.save_for_backward(v, a, points, faces, face_group, group_keep, vert_group, records, ws)
+        return ((value[0] + kw['back'] * value[1]) * kw['weight']).to(torch.float32)        # (fp64 on the device, rounded once)
+
+    @staticmethod
+    def backward(ctx, g):
+        v, a, points, faces, face_group, group_keep, vert_group, records, ws = ctx.saved_tensors
+        kw = ctx.kw
+        g_verts, g_alpha = surface_grads(points, v, faces, face_group, group_keep, a, vert_group, records, ws, n_points=kw['n_points'], tau=kw['tau'],
+                                         back=kw['back'], seed=kw['seed'], step=kw['step'], weight=kw['weight'],
+                                         grad_out=g.detach().reshape(1).to(torch.float32).contiguous(), back_count=kw['back_count'], segment=kw['segment'])
+        return g_verts, (g_alpha if (a is not None and ctx.needs_input_grad[1]) else None), None, None, None, None, None, None
+
+
+def surface_term(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, *, n_points, tau, back, seed, step, weight, back_count=None,
+                 segment=0):
+    """The surface term of DESIGN.md 6u as ONE autograd node:
+        weight * [ (1/M) sum_i rho(d2(p_i, S)) + back * (1/back_count) sum_v a_k(v) rho(|x_v - nn_P(x_v)|^2) ],   rho(d2) = min(d2, tau^2)
+    -> the fp32 scalar of the fp64 value; gradients to verts (V,3) and to vert_alpha (A,).  points (N,3): the cloud; n_points draws a step
+    (0: all points in order), taken inside the kernels from (seed, step); faces (F,3) int32 in the groups face_group (G+1), of which
+    group_keep (G, int32 or None) drops some; vert_group (V) int32: the row of vert_alpha of a block vertex, -1 for any other vertex;
+    back_count: n_blocks * vertices per block (default: the vertices with vert_group >= 0, counted with one host read).  Parts: surface_records, surface_grads."""
+    if back_count is None and back > 0 and vert_group is not None:
+        back_count = float(int((vert_group >= 0).sum()))
+    kw = dict(n_points=int(n_points or 0), tau=float(tau), back=float(back), seed=int(seed), step=int(step), weight=float(weight),
+              back_count=back_count, segment=int(segment))
+    return _SurfaceTerm.apply(verts, vert_alpha, points, faces, face_group, group_keep, vert_group, kw)

@@ -165,6 +165,7 @@ class ShardedTrainStep:
                     losses = self.native(inp, self.model._global_count, zero_grad=self.params.zero_grad)
             else:
                 self.params.zero_grad()
+                self.model._rng_step = self.n_steps     # (the counter of the step's random numbers, as in _c_iteration: the surface term's draw)
                 losses = self.model(inp, labels)
                 losses['total'].backward()
             dirty = ops.ARENA.end_step(self.params.flat.device) if (native and self._fused_adam()) else None

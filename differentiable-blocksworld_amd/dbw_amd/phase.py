@@ -101,4 +101,6 @@ def fast_path_refusal(model, renderer=None):
         return 'a fused / tiled / uv-fragment kernel is switched off (ops)'
     if m.blocks_n_faces >= (1 << 20) or m.n_blocks + 2 >= (1 << 11):
         return 'too many faces or maps for the packed face | map word'
+    if 'surface' in m.loss_weights:
+        return 'a surface term'
     return None

@@ -1,6 +1,6 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
-                          [--pose-refine LR] [--blocks-init points] [--exposure LR] [--intrinsics-refine LR]
+                          [--pose-refine LR] [--blocks-init points] [--exposure LR] [--intrinsics-refine LR] [--surface WEIGHT]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -38,7 +38,11 @@ cluster, on the device) and no longer at random poses; how many were seeded is p
 
 dataset.cloud: depth -- or the mapping {source: depth, unit, range, grid, bound, stride, edge, min_count} -- on a custom scene whose frames
 ship depth maps and no .ply: the cloud both fits above use is made from the depth maps (ops.depth_cloud), its size is
-printed and it is written to <run_dir>/depth_cloud.ply."""
+printed and it is written to <run_dir>/depth_cloud.ply.
+
+model.loss.surface_weight -- or --surface WEIGHT -- with model.loss.surface: {points, tau, back, ground, start_epoch, max_cloud} on a custom
+scene with a point cloud: the surface term keeps the blocks on the cloud during training, loss_surface is a column of
+train_metrics.tsv.  The steps then take the general path (the one-call C step stands aside, as for masks)."""
 import argparse
 import os
 import sys
@@ -69,6 +73,8 @@ def parse_args(argv=None):
                     help='fit a per-view exposure (gain and offset per channel) beside the model, with this learning rate (training.exposure.lr)')
     ap.add_argument('--blocks-init', choices=('points',), default=None,
                     help="'points': start the blocks at the clusters of the custom scene's point cloud (training.blocks_init)")
+    ap.add_argument('--surface', type=float, default=None, metavar='WEIGHT',
+                    help="keep the blocks on the custom scene's point cloud: the weight of the surface term (model.loss.surface_weight)")
     ap.add_argument('--device', default='cuda:0')
     return ap.parse_args(argv)
 
@@ -104,6 +110,8 @@ def prepare_config(args):
     if getattr(args, 'exposure', None) is not None:
         entry = cfg.setdefault('training', {}).get('exposure')
         cfg['training']['exposure'] = dict(entry if isinstance(entry, dict) else {}, lr=args.exposure)
+    if getattr(args, 'surface', None) is not None:
+        cfg.setdefault('model', {}).setdefault('loss', {})['surface_weight'] = args.surface
     if getattr(args, 'blocks_init', None) is not None and not isinstance(cfg.setdefault('training', {}).get('blocks_init'), dict):
         cfg['training']['blocks_init'] = args.blocks_init      # (a mapping in the config already asks for the points, with its options)
     return cfg
@@ -217,6 +225,27 @@ def resolve_blocks_init(cfg, scene, model, device, run_dir=None, start=None):
     return init
 
 
+def resolve_surface(scene, model, device):
+    """model.loss.surface_weight > 0: the model gets the scene's cloud (scene.cloud: the .ply or the depth cloud) for the surface term
+     and the number of points it keeps is printed -> that number, or None without the weight.  A custom scene without a cloud is
+    refused with the scene's own words, and so are the DTU / BlendedMVS scenes: their cloud is the ground truth the scores are computed
+    against.  A resumed run comes here too: a checkpoint does not carry the cloud."""
+    if 'surface' not in getattr(model, 'loss_weights', {}):
+        return None
+    if scene.name != 'custom':
+        raise SystemExit(f"model.loss.surface_weight is for custom scenes: the cloud of a '{scene.name}' scene is the ground truth its scores are "
+                         'computed against')
+    try:
+        points = scene.cloud(device)
+    except ValueError as e:
+        raise SystemExit(f'model.loss.surface_weight: {e}') from e
+    n = model.set_surface_points(points)
+    c = model.surface_cfg
+    print(f"surface: weight {model.loss_weights['surface']:g} on {n} of {len(points)} points, {c['points'] or n} a step, tau {c['tau']:g}, "
+          f"back {c['back']:g}, from epoch {c['start_epoch']}")
+    return n
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = prepare_config(args)
@@ -242,6 +271,7 @@ def main(argv=None):
     resolve_world_frame(cfg, train, args.device, run_dir, start.get('resume'))
     model = create_model(cfg, train.img_size).to(args.device).train()
     resolve_blocks_init(cfg, train, model, args.device, run_dir, start.get('resume') or start.get('pretrained'))
+    resolve_surface(train, model, args.device)
     if 'perceptual' in model.loss_weights and model.perceptual_name != 'ssim':     # (ssim: the model installed its built-in term)
         from .lpips_vgg import LPIPSVGG
         net = LPIPSVGG()

@@ -163,6 +163,10 @@ class Trainer:
             self.intrinsics = IntrinsicsRefiner(views['K'][0], views['imgs'].device, lr=self.intrinsics_cfg['lr'],
                                                 betas=tuple((tr.get('optimizer') or {}).get('betas', (0.9, 0.999))),
                                                 focal=self.intrinsics_cfg['focal'], principal=self.intrinsics_cfg['principal'])
+        # The surface term (model.loss.surface_weight) is one term on the whole cloud: every rank would add all of it
+        if 'surface' in getattr(model, 'loss_weights', {}) and ws > 1:
+            raise NotImplementedError('model.loss.surface_weight under data parallelism: every rank would add the whole term, and the ranks '
+                                      'do not share out its points')
         # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
         # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
         self.mask_sums = None

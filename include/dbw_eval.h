@@ -91,6 +91,41 @@ int dbw_eval_cluster_fit(const float *points, int64_t N, int K, const float *ini
                          int32_t *labels, int32_t *counts, double *mean, double *cov, double *evals, double *axes, int32_t *info,
                          dbw_stream_t stream);
 
+/* The surface term (csrc/surface_term.hip, arithmetic csrc/surface_math.h), added under revision 1 of this header: a capture's
+ * point cloud against the posed meshes, in the frame of both.
+ *   value[0] = (1/M) sum_i rho(d2(p_i, S)),  value[1] = (1/back_count) sum_v a_{k(v)} rho(|x_v - nn(x_v)|^2),  rho(d2) = min(d2, tau^2), fp64.
+ *   points (N,3) fp32, the cloud.  n_points > 0: M = n_points draws, draw i is cloud index step_random(seed, step, stream 2, i).x mod N
+ *     (csrc/rng_math.h), taken inside the kernels; n_points == 0: M = N, all points in order.
+ *   verts (V,3) fp32, faces (F,3) int32 into them, in G groups of consecutive faces: face_group (G+1) int32, ascending from 0 to F -- the
+ *     caller's contract, like faces < V when faces_host (a HOST copy of faces, or NULL) is not offered: the kernels clamp both, so nothing
+ *     outside the arrays is read, but the result then belongs to another mesh.  group_keep (G) int32 or NULL: a group with 0 is no part of S.
+ *   d2(p, S) = |p - c|^2, c the closest point of S: per face the projection onto its plane where that lies inside, else the nearest of the
+ *     clamped projections onto its sides; a face of zero area is its sides, of zero length its point.  Of equal d2 the lowest face wins.
+ *   records (M) of 16 bytes, 16-byte aligned: d2 fp32, face int32, u, v fp32 with c = (1-u-v) v0 + u v1 + v v2.  A point without any kept
+ *     face: face -1, d2 NaN (counted as tau^2).
+ *   back > 0: x_v are the vertices with 0 <= vert_group[v] < A, a = vert_alpha (A) fp32, nn the exact nearest cloud point (dbw_nn_points'
+ *     search); back_count the constant n_blocks * vertices per block.  back == 0: value[1] = 0, vert_alpha / vert_group may be NULL.
+ *   cull (0 | 1): skip a group whose box is farther than every running best of a wave; records and value do not depend on it.
+ * dbw_eval_surface_bwd, on the records and the workspace that dbw_eval_surface_fwd left for the same arguments: with
+ *   L = weight * (value[0] + back * value[1]),  grad_verts (V,3) fp32 = grad_out[0] * dL/dverts (-2 b_m (p - c) / M per record inside tau;
+ *   2 a_k (x_v - nn) back / back_count per block vertex inside tau), grad_alpha (A) fp32 or NULL = grad_out[0] * dL/da (the sum of the block's
+ *   rho).  grad_out: one fp32 on the device, or NULL (= 1).  Both outputs are written whole.  No floating-point atomics: records are walked in
+ *   segments of `segment` (0: DBW_EVAL_SURFACE_SEGMENT; else in [64, 2^20]) in index order, the segments added in order.
+ * 1 <= N < 2^31, 1 <= M <= 2^24, 1 <= F <= 2^20, 1 <= V <= 2^21, 1 <= G <= 4096, 0 <= A <= V, tau > 0, back >= 0.  workspace:
+ * dbw_eval_surface_workspace_bytes(M, F, V, G, segment) bytes (0: sizes refused), 16-byte aligned, kept untouched between the two calls;
+ * `segment` is the one dbw_eval_surface_bwd will be given: its partials, one row per segment, are the last part of the workspace, and
+ * the entry points do not know the workspace's size (ops.surface_grads checks it). */
+#define DBW_EVAL_SURFACE_SEGMENT 1024
+size_t dbw_eval_surface_workspace_bytes(int64_t M, int F, int V, int G, int segment);
+int dbw_eval_surface_fwd(const float *points, int64_t N, int64_t n_points, int64_t seed, int64_t step, const float *verts, int V,
+                         const int32_t *faces, const int32_t *faces_host, int F, const int32_t *face_group, const int32_t *group_keep, int G,
+                         const float *vert_alpha, const int32_t *vert_group, int A, double back_count, float tau, float back, int cull,
+                         void *workspace, void *records, double *value, dbw_stream_t stream);
+int dbw_eval_surface_bwd(const float *points, int64_t N, int64_t n_points, int64_t seed, int64_t step, const float *verts, int V,
+                         const int32_t *faces, int F, int G, const float *vert_alpha, const int32_t *vert_group, int A, double back_count,
+                         float tau, float back, float weight, const float *grad_out, int segment, const void *records, void *workspace,
+                         float *grad_verts, float *grad_alpha, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
