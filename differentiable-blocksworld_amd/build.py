@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['util.hip', 'raster.hip', 'project_clip.hip', 'shade_blend.hip', 'render_fused.hip', 'texture.hip', 'model_ops.hip', 'train_step.hip', 'lpips_head.hip',
            'nn_search.hip', 'render_lit.hip', 'frame_export.hip', 'image_ingest.hip', 'lens_undistort.hip', 'lens_rectify.hip', 'run_monitor.hip', 'icp_align.hip', 'scene_parse.hip',
-           'plane_fit.hip', 'ssim_term.hip', 'masked_loss.hip', 'camera_grad.hip', 'cluster_fit.hip', 'depth_cloud.hip', 'exposure_loss.hip', 'surface_term.hip']
+           'plane_fit.hip', 'ssim_term.hip', 'masked_loss.hip', 'camera_grad.hip', 'cluster_fit.hip', 'depth_cloud.hip', 'exposure_loss.hip', 'surface_term.hip',
+           'freespace_term.hip']
 OUT = os.path.join(HERE, 'dbw_amd', 'libdbw_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-munsafe-fp-atomics',
          '-fno-gpu-flush-denormals-to-zero', '-Wall', '-Wno-unused-function']

@@ -92,6 +92,19 @@ __global__ void __launch_bounds__(DEPTH_BLOCK) depth_accumulate_kernel(DepthArgs
     }
 }
 
+// The depth rays (dbw_lens_depth_rays): the accumulate kernel's layout -- one thread per selected pixel, the frame in blockIdx.z, camera and
+// pose rows by value --, one 16-byte record a pixel: the ray's end and its frame, or zeros and -1 where there is no measurement.
+__global__ void __launch_bounds__(DEPTH_BLOCK) depth_rays_kernel(DepthArgs A, int frame0, const uint16_t *__restrict__ depth, float4 *__restrict__ rays) {
+    const long long p = (long long)blockIdx.x * DEPTH_BLOCK + threadIdx.x;
+    const int n = blockIdx.z;                                       // (gridDim.z == A.n)
+    const long long px = (long long)A.Hs * A.Ws;
+    if (p >= px) return;
+    const int i = (int)(p / A.Ws) * A.stride, j = (int)(p % A.Ws) * A.stride;
+    float e[3] = {0.0f, 0.0f, 0.0f};
+    const bool ok = depth_ray_end(depth + (long long)n * A.rule.H * A.rule.W, A.rule, lens_cam(A.cams[n]), lens_target(A.target), A.poses[n], i, j, e);
+    rays[(long long)n * px + p] = ok ? make_float4(e[0], e[1], e[2], __int_as_float(frame0 + n)) : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+}
+
 // The exclusive scan of one int per thread over a block of THREADS (a multiple of 64); *total: the block's sum.  lds: THREADS / 64 + 1 ints.
 template <int THREADS>
 __device__ __forceinline__ int block_scan(int v, int *lds, int *total) {
@@ -262,4 +275,49 @@ extern "C" int dbw_lens_depth_cloud(const uint16_t *depth, int N, int H, int W, 
     hipLaunchKernelGGL(depth_emit_kernel, dim3((unsigned)L.n_tiles), dim3(DEPTH_BLOCK), 0, s, (const DepthCell *)cells, L.n_cells, (uint32_t)min_count,
                        (const int *)tiles, B, points, counts, (long long)capacity);
     return dbw_check_launch("depth_emit_kernel");
+}
+
+extern "C" int dbw_lens_depth_rays(const uint16_t *depth, int N, int H, int W, const float *cams, const float *target, const float *poses, int d_min,
+                                   int d_max, int stride, int edge_permille, void *rays, dbw_stream_t stream) {
+    DBW_REQUIRE(depth && cams && target && poses && rays, "null pointer");
+    DBW_REQUIRE((uintptr_t)rays % 16 == 0, "rays are not 16-byte aligned");
+    DBW_REQUIRE((uintptr_t)depth % 2 == 0, "depth: misaligned pointer");
+    DBW_REQUIRE(N >= 1, "N below 1");
+    DBW_REQUIRE(H >= 1 && W >= 1, "H, W below 1");
+    DBW_REQUIRE((long long)H * W < (1LL << 29), "H * W must be below 2^29");
+    DBW_REQUIRE(stride >= 1, "stride below 1");
+    DBW_REQUIRE(d_max <= 65535, "d_max above 65535");
+    DBW_REQUIRE(d_min >= 1 && d_min <= d_max, "d_min must be in [1, d_max]");
+    DBW_REQUIRE(edge_permille >= 0 && edge_permille <= 1000, "edge_permille must be in [0, 1000]");
+    const int Hs = (H + stride - 1) / stride, Ws = (W + stride - 1) / stride;
+    DBW_REQUIRE((long long)N * Hs * Ws < (1LL << 31), "N * ceil(H / stride) * ceil(W / stride) must be below 2^31");
+    for (int k = 0; k < 4; ++k) DBW_REQUIRE(target[k] - target[k] == 0.0f, "target: a value that is not finite");
+    DBW_REQUIRE(target[2] > 0.0f && target[3] > 0.0f, "target: a reciprocal focal length that is not positive");
+    for (long long n = 0; n < N; ++n) {
+        const float *row = cams + n * LENS_RECT_N_PARAMS, *pose = poses + n * DEPTH_POSE_N;
+        for (int k = 0; k < LENS_RECT_N_PARAMS; ++k) DBW_REQUIRE(row[k] - row[k] == 0.0f, "cams: a value that is not finite");
+        DBW_REQUIRE(row[0] == (float)LENS_RECT_PINHOLE || row[0] == (float)LENS_RECT_FISHEYE, "cams: a model id that is neither 0 nor 1");
+        DBW_REQUIRE(row[1] > 0.0f && row[2] > 0.0f, "cams: a focal length that is not positive");
+        for (int k = 0; k < DEPTH_POSE_N; ++k) DBW_REQUIRE(pose[k] - pose[k] == 0.0f, "poses: a value that is not finite");
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    DepthArgs A;
+    A.Hs = Hs; A.Ws = Ws; A.stride = stride;
+    A.rule.H = H; A.rule.W = W; A.rule.G = 1; A.rule.d_min = d_min; A.rule.d_max = d_max; A.rule.edge_permille = edge_permille;
+    A.pad[0] = A.pad[1] = 0;
+    for (int k = 0; k < 4; ++k) { A.target[k] = target[k]; A.box[k] = 0.0f; }
+    const long long frame = (long long)H * W, px = (long long)Hs * Ws;
+    for (int n0 = 0; n0 < N; n0 += DEPTH_GROUP) {
+        const int n = N - n0 < DEPTH_GROUP ? N - n0 : DEPTH_GROUP;
+        A.n = n;
+        for (int f = 0; f < DEPTH_GROUP; ++f) {
+            for (int k = 0; k < LENS_RECT_N_PARAMS; ++k) A.cams[f][k] = f < n ? cams[(long long)(n0 + f) * LENS_RECT_N_PARAMS + k] : 0.0f;
+            for (int k = 0; k < DEPTH_POSE_N; ++k) A.poses[f][k] = f < n ? poses[(long long)(n0 + f) * DEPTH_POSE_N + k] : 0.0f;
+        }
+        hipLaunchKernelGGL(depth_rays_kernel, dim3((unsigned)((px + DEPTH_BLOCK - 1) / DEPTH_BLOCK), 1, (unsigned)n), dim3(DEPTH_BLOCK), 0, s, A, n0,
+                           depth + n0 * frame, (float4 *)rays + n0 * px);
+        if (const int rc = dbw_check_launch("depth_rays_kernel")) return rc;
+    }
+    return 0;
 }

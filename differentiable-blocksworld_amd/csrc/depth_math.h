@@ -72,6 +72,37 @@ DBW_HD int depth_sample(const uint16_t *frame, const DepthRule &D, const LensCam
     return ((q[0] >> DEPTH_SUB_BITS) * D.G + (q[1] >> DEPTH_SUB_BITS)) * D.G + (q[2] >> DEPTH_SUB_BITS);
 }
 
+// The depth ray of target pixel (i, j) of one frame (dbw_lens_depth_rays): p[3] is the world point exactly as depth_sample
+// forms p_a -- the same operations in the same order, the lens through lens_rect_source, the nearest source pixel -- and the result is
+// false where depth_sample returns DEPTH_DROPPED (lens, range, edge rule; D.G is not read) or where a coordinate of p is not finite.  The
+// box is not applied: a far end is still evidence of free space in front of it.
+DBW_HD bool depth_ray_end(const uint16_t *frame, const DepthRule &D, const LensCam &C, const LensTarget &T, const float *pose, int i, int j,
+                          float *p) {
+    float u, v;
+    lens_rect_source(C, T, i, j, &u, &v);
+    const float fu = __builtin_floorf(u + 0.5f), fv = __builtin_floorf(v + 0.5f);
+    if (!(fu >= 0.0f && fu <= (float)(D.W - 1) && fv >= 0.0f && fv <= (float)(D.H - 1))) return false;
+    const int sx = (int)fu, sy = (int)fv;
+    const uint16_t *s = frame + ((long long)sy * D.W + sx);
+    const int d = (int)s[0];
+    if (d < D.d_min || d > D.d_max) return false;
+    if (D.edge_permille > 0) {
+        if (sx > 0 && depth_jump(d, (int)s[-1], D.edge_permille)) return false;
+        if (sx < D.W - 1 && depth_jump(d, (int)s[1], D.edge_permille)) return false;
+        if (sy > 0 && depth_jump(d, (int)s[-D.W], D.edge_permille)) return false;
+        if (sy < D.H - 1 && depth_jump(d, (int)s[D.W], D.edge_permille)) return false;
+    }
+    const float x = ((float)j + 0.5f - T.cx0) * T.inv_fx0, y = ((float)i + 0.5f - T.cy0) * T.inv_fy0;
+    const float z = (float)d;
+    const float cx = x * z, cy = y * z;
+    bool finite = true;
+    for (int a = 0; a < 3; ++a) {
+        p[a] = ((pose[3 * a] * cx + pose[3 * a + 1] * cy) + pose[3 * a + 2] * z) + pose[9 + a];
+        finite = finite && (p[a] - p[a] == 0.0f);
+    }
+    return finite;
+}
+
 // One coordinate of a cell's point: the mean of its samples' q (each at the middle of its step) back in the world frame.
 DBW_HD float depth_point(unsigned long long sum, uint32_t count, float lo, float inv_step) {
     const double n = (double)count;

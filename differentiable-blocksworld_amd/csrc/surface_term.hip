@@ -28,6 +28,7 @@
 #include "dbw_common.h"
 #include "loss_reduce.h"
 #include "nn_search.h"
+#include "surface_box.h"
 #include "surface_math.h"
 #include "../../include/dbw_eval.h"
 
@@ -268,6 +269,13 @@ __global__ __launch_bounds__(SF_BLOCK) void surface_alpha_kernel(const float *__
 }
 
 }  // namespace
+
+// the box launch for the other term that walks the same gathered faces (csrc/freespace_term.hip): tri (F, 12 floats), boxes (G, 8 floats)
+int dbw_surface_box_launch(const float *verts, int V, const int32_t *faces, int F, const int32_t *face_group, const int32_t *group_keep, int G,
+                           float *tri, float *boxes, hipStream_t stream) {
+    hipLaunchKernelGGL(surface_box_kernel, dim3((unsigned)G), dim3(SF_BLOCK), 0, stream, verts, V, faces, F, face_group, group_keep, tri, boxes);
+    return dbw_check_launch("surface_box_kernel");
+}
 
 extern "C" size_t dbw_eval_surface_workspace_bytes(int64_t M, int F, int V, int G, int segment) {
     return surface_sizes_ok(M, F, V, G, segment) ? surface_layout(M, F, V, G, segment).total : 0;

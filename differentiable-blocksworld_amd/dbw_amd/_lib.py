@@ -150,13 +150,19 @@ EVAL_SIGNATURES = {
     # the surface term (csrc/surface_term.hip), added under revision 1 of the header
     'dbw_eval_surface_fwd': [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_d, c_f, c_f, c_i, c_p, c_p, c_p, c_p],
     'dbw_eval_surface_bwd': [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_f, c_f, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    # the free-space term (csrc/freespace_term.hip), added under revision 1 of the header
+    'dbw_eval_freespace_fwd': [c_p, c_p, c_p, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_i, c_p, c_p, c_p,
+                               c_p],
+    'dbw_eval_freespace_bwd': [c_p, c_p, c_p, c_i64, c_i, c_i64, c_i64, c_i64, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_f, c_f, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
 }
 EVAL_OTHER_SIGNATURES = {
     'dbw_eval_plane_workspace_bytes': (c_sz, [c_i64, c_i]),
     'dbw_eval_cluster_workspace_bytes': (c_sz, [c_i64, c_i]),
     'dbw_eval_surface_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i]),
+    'dbw_eval_freespace_workspace_bytes': (c_sz, [c_i64, c_i, c_i, c_i, c_i]),
 }
 EVAL_SURFACE_SEGMENT = header_define('dbw_eval.h', 'DBW_EVAL_SURFACE_SEGMENT')
+EVAL_FREESPACE_SEGMENT = header_define('dbw_eval.h', 'DBW_EVAL_FREESPACE_SEGMENT')
 EVAL_PLANE_ORTHOGONAL, EVAL_PLANE_VERTICAL = 0, 1             # DBW_EVAL_PLANE_* of include/dbw_eval.h
 EVAL_ABI_VERSION = header_define('dbw_eval.h', 'DBW_EVAL_ABI_VERSION')
 
@@ -212,6 +218,8 @@ LENS_SIGNATURES = {
     'dbw_lens_pose_chain': [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     # the point cloud of a capture's depth maps (csrc/depth_cloud.hip), added under revision 1 of the header
     'dbw_lens_depth_cloud': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i64, c_p, c_p],
+    # the depth rays of a capture (csrc/depth_cloud.hip), added under revision 1 of the header
+    'dbw_lens_depth_rays': [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
     # intrinsics refinement (csrc/camera_grad.hip), added under revision 1 of the header
     'dbw_lens_intrinsics_grad': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_i, c_p],
     'dbw_lens_intrinsics_apply': [c_p, c_p, c_p, c_p],

@@ -645,6 +645,7 @@ class CustomScene(_Scene):
             self.pc_gt = torch.from_numpy(points @ F[:3, :3].T + F[:3, 3]).float()
 
         self.cloud_info, self._clouds, self._depth = None, {}, None
+        self.rays_info, self._rays = None, {}
         if self.cloud_options is not None:
             self._depth = self._depth_setup(path, meta, frames, c2w, F, (h, w))
 
@@ -700,6 +701,41 @@ class CustomScene(_Scene):
             self.cloud_info = {'points': info[0], 'samples': info[1], 'outside': info[2], 'frames': len(D['files'])}
         pts = self._clouds[key]
         return pts if device is None else pts.to(device)
+
+    def rays(self, device=None):
+        """The capture's depth rays for the free-space term, in the normalised frame R, T live in, on `device` (None: the CPU)
+        -> (ends (Nr,3) float32, frame (Nr,) int32, origins (Nf,3) float32): ray j runs from origins[frame[j]], the centre of the camera of the
+        j-th ray's depth map (the pose rows' t), to ends[j], the measured surface point -- every depth sample that cloud() would take before
+        its cube, with the same range, stride and edge rule (ops.depth_rays on a cuda device, ops.depth_rays_host otherwise; the valid
+        records compacted once, order kept).  Built on first use and kept per device; rays_info then holds {rays, samples, frames}.  The
+        rays use the capture's poses as loaded.  ValueError for a scene without cloud='depth': a .ply carries no visibility."""
+        if self._depth is None:
+            raise ValueError(f"'{self.tag}': no depth rays (dataset.cloud: depth, with a depth_file_path on the frames of transforms.json): a "
+                             'point cloud from a file does not say where it was seen from')
+        dev = None if device is None else torch.device(device)
+        host = dev is None or dev.type == 'cpu'
+        key = 'cpu' if host else str(dev)
+        if key not in self._rays:
+            D = self._depth
+            depth = np.stack([read_depth_png(f) for f in D['files']])
+            args = (depth, D['cams'], D['target'], D['poses'])
+            kw = {k: D[k] for k in ('d_range', 'stride', 'edge')}
+            rec = torch.from_numpy(ops.depth_rays_host(*args, **kw)) if host else ops.depth_rays(*args, device=dev, **kw)
+            ends, frame = ops.depth_rays_compact(rec)
+            origins = torch.from_numpy(np.ascontiguousarray(D['poses'][:, 9:12])).to(ends.device)
+            self._rays[key] = (ends, frame, origins)
+            self.rays_info = {'rays': int(ends.shape[0]), 'samples': int(rec.numel() // 4), 'frames': len(D['files'])}
+        out = self._rays[key]
+        return out if device is None else tuple(t.to(device) for t in out)
+
+    def release_rays(self, device=None):
+        """Drop the copy of rays() kept for `device` (None: every copy): a caller that has taken what it needs -- the model thins the rays to
+        its own buffers -- gives the memory back; rays() builds them again when asked."""
+        if device is None:
+            self._rays.clear()
+        else:
+            dev = torch.device(device)
+            self._rays.pop('cpu' if dev.type == 'cpu' else str(dev), None)
 
     def _depth_setup(self, path, meta, frames, c2w, F, size):
         """What cloud() hands ops.depth_cloud: the depth files and, per frame that has one, the camera row at the depth maps' resolution

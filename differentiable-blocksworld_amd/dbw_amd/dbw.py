@@ -78,6 +78,41 @@ def parse_surface_config(entry):
     return o
 
 
+FREESPACE_KEYS = ('rays', 'tau', 'margin', 'ground', 'start_epoch', 'max_rays')
+FREESPACE_DEFAULTS = {'rays': 16384, 'tau': 0.1, 'margin': 0.02, 'ground': True, 'start_epoch': 1, 'max_rays': 1048576}
+FREESPACE_THIN_SEED = 20241020      # the permutation that thins the rays above max_rays
+
+
+def parse_freespace_config(entry):
+    """model.loss.freespace -> {rays, tau, margin, ground, start_epoch, max_rays} with the defaults filled in; unknown keys are refused.
+    rays: depth rays drawn per step (0: all of them, in order); tau: where the penalty of a hit in front of the measured surface turns from
+    quadratic to linear; margin: how far in front of the measured surface a hit goes unpunished (depth noise); ground: whether the ground's
+    faces can stop a ray; start_epoch: the first epoch with the term; max_rays: more rays are thinned to this many when they are set.  The
+    defaults are design choices in the normalised frame, where the cameras sit in [-1, 1]^3 -- a tenth of the rig's half-extent as the
+    quadratic reach, a fifth of that as the depth maps' slack, 16384 rays as a step's sample, as the surface term draws points -- and NOT
+    measured values."""
+    from collections.abc import Mapping
+    if entry is None:
+        entry = {}
+    if not isinstance(entry, Mapping):
+        raise ValueError(f"model.loss.freespace: a mapping of {', '.join(FREESPACE_KEYS)}, got {entry!r}")
+    bad = [k for k in entry if k not in FREESPACE_KEYS]
+    if bad:
+        raise ValueError(f"model.loss.freespace.{bad[0]}: not one of {', '.join(FREESPACE_KEYS)}")
+    o = dict(FREESPACE_DEFAULTS, **entry)
+    o.update(rays=int(o['rays']), tau=float(o['tau']), margin=float(o['margin']), ground=bool(o['ground']), start_epoch=int(o['start_epoch']),
+             max_rays=int(o['max_rays']))
+    if o['rays'] < 0 or o['rays'] > (1 << 24):
+        raise ValueError(f"model.loss.freespace.rays: in [0, 2^24], got {o['rays']}")
+    if not (0 < o['tau'] < float('inf')):
+        raise ValueError(f"model.loss.freespace.tau: positive, got {o['tau']}")
+    if not (0 <= o['margin'] < float('inf')):
+        raise ValueError(f"model.loss.freespace.margin: non-negative, got {o['margin']}")
+    if not (1 <= o['max_rays'] <= (1 << 24)):
+        raise ValueError(f"model.loss.freespace.max_rays: in [1, 2^24], got {o['max_rays']}")
+    return o
+
+
 class DifferentiableBlocksWorld(nn.Module):
     name = 'dbw'
 
@@ -266,6 +301,9 @@ class DifferentiableBlocksWorld(nn.Module):
         # the surface term, last: the names and the order of every config without it stay what they were
         weights['surface'] = kwargs.pop('surface_weight', 0)
         self.surface_cfg = parse_surface_config(kwargs.pop('surface', None))
+        # the free-space term, after it for the same reason
+        weights['freespace'] = kwargs.pop('freespace_weight', 0)
+        self.freespace_cfg = parse_freespace_config(kwargs.pop('freespace', None))
         name = kwargs.pop('name', 'mse')
         # loss.py:22, dbw.py:155,163: 'lpips' (a third-party network: set_perceptual) or 'ssim', the built-in term (metrics.SSIMTerm)
         self.perceptual_name = kwargs.pop('perceptual_name', 'lpips')
@@ -287,6 +325,11 @@ class DifferentiableBlocksWorld(nn.Module):
         if self.perceptual_name == 'ssim' and 'perceptual' in self.loss_weights:
             from .metrics import SSIMTerm
             self.perceptual_fn = SSIMTerm()
+
+    @property
+    def _keeps_scene_verts(self):
+        """whether compute_losses has a term on the posed vertices (the surface term, the free-space term)"""
+        return 'surface' in self.loss_weights or 'freespace' in self.loss_weights
 
     def set_perceptual(self, fn):
         """fn(imgs, rec) -> scalar, e.g. lpips.LPIPS(net='vgg') with normalize=True (loss.py:32-40).  Replaces the built-in term that
@@ -379,8 +422,8 @@ class DifferentiableBlocksWorld(nn.Module):
         S_w, R_w, T_w = self._world_consts()
         ph = phase.phase_of(self, self.training)
         ground_v = ops.posed_mesh(self.R_6d_ground, self.T_ground, self._ground_base, S_w, R_w, T_w)
-        if 'surface' in self.loss_weights:
-            self._surface_ground_v = ground_v       # the surface term reads the render's own vertices (compute_losses)
+        if self._keeps_scene_verts:
+            self._surface_ground_v = ground_v       # the surface and free-space terms read the render's own vertices (compute_losses)
         bkg_maps, self._bkg_maps = ops.texture_prep(self.texture_bkg, ph.decim_env)
         g_maps, self._ground_maps = ops.texture_prep(self.texture_ground, ph.decim_env)
         verts = torch.cat([self.sky_world_verts(), ground_v], 0)
@@ -419,14 +462,14 @@ class DifferentiableBlocksWorld(nn.Module):
                     self._alpha = self._alpha[mask_i32.bool()]
         maps_all, self._blocks_maps = ops.texture_prep(self.textures, ph.decim_blocks)
         self._keep_mask = keep
-        if 'surface' in self.loss_weights:
+        if self._keeps_scene_verts:
             self._surface_block_v = None
         if nb == 0:
             return None
         S_w, R_w, T_w = self._world_consts()
         verts = ops.sq_blocks(self.sq_eps, self.S, self.R_6d, self.T, self._trig, keep, nb, self.ratio_block_scene,
                               self.scale_min, S_w, R_w, T_w, dense=not self.sync_free)
-        if 'surface' in self.loss_weights:
+        if self._keeps_scene_verts:
             self._surface_block_v = verts
         maps = maps_all if (keep is None or self.sync_free) else maps_all[keep.bool()]
         F_ = nb * self.BNF
@@ -988,15 +1031,85 @@ class DifferentiableBlocksWorld(nn.Module):
                                 back=back, seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=int(step),
                                 weight=wgt, back_count=float(self.n_blocks * self._block_nv))
 
+    # ------------------------------------------------------------------------------------------------ the free-space term
+    @torch.no_grad()
+    def set_freespace_rays(self, ends, frame, origins):
+        """The capture's depth rays for the free-space term, in the normalised frame of R, T and of the posed meshes: ray j runs from
+        origins[frame[j]] (a camera centre) to ends[j] (the measured surface point).  Kept as non-persistent buffers (a checkpoint does not
+        carry them: the rays are rebuilt from the scene).  Rays with a non-finite coordinate, or a frame outside the table, are dropped; more
+        than freespace.max_rays are thinned to the first max_rays of a seeded permutation -> the number kept."""
+        dev = self.alpha_logit.device
+        p = torch.as_tensor(ends).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
+        f = torch.as_tensor(frame).detach().to(device=dev).reshape(-1).to(torch.int64)
+        o = torch.as_tensor(origins).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
+        if f.shape[0] != p.shape[0]:
+            raise ValueError(f'set_freespace_rays: {f.shape[0]} frames for {p.shape[0]} ends')
+        ok = torch.isfinite(p).all(1) & (f >= 0) & (f < o.shape[0])
+        ok &= torch.isfinite(o).all(1)[f.clamp(0, max(o.shape[0] - 1, 0))] if o.shape[0] else torch.zeros_like(ok)
+        p, f = p[ok], f[ok]
+        cap = self.freespace_cfg['max_rays']
+        if p.shape[0] > cap:
+            perm = torch.randperm(p.shape[0], generator=torch.Generator().manual_seed(FREESPACE_THIN_SEED))[:cap].to(dev)
+            p, f = p[perm], f[perm]
+        if p.shape[0] == 0:
+            raise ValueError('set_freespace_rays: no finite ray')
+        for n, t in (('_freespace_ends', p.contiguous()), ('_freespace_frame', f.to(torch.int32).contiguous()), ('_freespace_origins', o.contiguous())):
+            self._buffers.pop(n, None)
+            self.register_buffer(n, t, persistent=False)
+        return p.shape[0]
+
+    def _freespace_term(self, dev):
+        """weight * the term on the vertex tensors the last build_env_scene / build_blocks_scene produced (no second sq_blocks launch)."""
+        c, wgt = self.freespace_cfg, float(self.loss_weights['freespace'])
+        if self.world_size > 1:
+            raise NotImplementedError('the free-space term under data parallelism: every rank would add the whole term, and the ranks do not '
+                                      'share out its rays')
+        ends = getattr(self, '_freespace_ends', None)
+        if ends is None:
+            raise RuntimeError('freespace_weight > 0 needs the capture\'s depth rays: model.set_freespace_rays(ends, frame, origins) (train.py '
+                               'feeds scene.rays() of a custom scene with depth maps)')
+        if self.cur_epoch + 1 < c['start_epoch'] or not self.training:
+            # (before start_epoch; and in eval mode: the term is a training signal, an evaluation does not count it in its L_tot)
+            return torch.zeros((), device=dev)
+        ground_v = getattr(self, '_surface_ground_v', None) if c['ground'] else None
+        block_v = getattr(self, '_surface_block_v', None)
+        if c['ground'] and ground_v is None:
+            raise RuntimeError('the free-space term reads the vertices of the scene the forward built: call the model, not compute_losses alone')
+        if ground_v is None and block_v is None:          # no face left: no ray is stopped
+            return torch.zeros((), device=dev)
+        nb = 0 if block_v is None else block_v.reshape(-1, self._block_nv, 3).shape[0]
+        faces, face_group, _, one = self._surface_tables(nb, ground_v is not None, dev)
+        key = ('group_alpha', nb, ground_v is not None, str(dev))
+        cache = self.__dict__.setdefault('_surface_table_cache', {})
+        if key not in cache:
+            cache[key] = torch.tensor(([-1] if ground_v is not None else []) + list(range(nb)), dtype=torch.int32, device=dev)
+        parts = [v.reshape(-1, 3) for v in (ground_v, block_v) if v is not None]
+        verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        keep = self._keep_mask if (self.sync_free and nb) else None
+        if keep is not None and ground_v is not None:
+            keep = torch.cat([one, keep.to(torch.int32)])
+        step = getattr(self, '_rng_step', None)
+        if step is None:                                  # a model stepped by hand: its own count of training losses
+            step = self.__dict__.setdefault('_freespace_calls', 0)
+            self._freespace_calls = step + 1
+        return ops.freespace_term(ends, self._freespace_frame, self._freespace_origins, verts.float().contiguous(), faces, face_group,
+                                  None if keep is None else keep.contiguous(), cache[key], self._alpha.float().contiguous() if nb else None,
+                                  n_rays=min(c['rays'], 1 << 24), tau=c['tau'], margin=c['margin'],
+                                  seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=int(step), weight=wgt)
+
     def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
         """The loss dict of _image_and_regulariser_losses (same arguments), plus -- with surface_weight > 0 -- the surface term
-        on the vertices of the scene the forward built (zero in eval mode and before surface.start_epoch); without the weight no line of it
-        runs."""
+        and -- with freespace_weight > 0 -- the free-space term, both on the vertices of the scene the forward built (zero in
+        eval mode and before their start_epoch); without a weight no line of its term runs."""
         losses = self._image_and_regulariser_losses(imgs, rec, layers=layers, rgb_value=rgb_value, masks=masks, mask_count=mask_count, exposure=exposure)
         if 'surface' in self.loss_weights:
             total = losses.pop('total')
             losses['surface'] = self._surface_term(imgs.device)
             losses['total'] = total + losses['surface']
+        if 'freespace' in self.loss_weights:                # (DESIGN.md 6v: the same shape, after it)
+            total = losses.pop('total')
+            losses['freespace'] = self._freespace_term(imgs.device)
+            losses['total'] = total + losses['freespace']
         return losses
 
     def _image_and_regulariser_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
@@ -1006,8 +1119,8 @@ class DifferentiableBlocksWorld(nn.Module):
         image terms see rec = exp(g) * composite + b (ops.composite_mse_exposure), with or without masks; layers must be given; the
         regularisers do not see theta."""
         w = self.loss_weights
-        if 'surface' in w:
-            w = {k: v for k, v in w.items() if k != 'surface'}       # (compute_losses adds that term)
+        if 'surface' in w or 'freespace' in w:
+            w = {k: v for k, v in w.items() if k not in ('surface', 'freespace')}       # (compute_losses adds those terms)
         dev = imgs.device
         # (the epoch's loss factors in eval mode too; view-independent regularisers: every rank computes them identically, scaled by
         # 1 / world_size so that the sum all-reduce of gradients counts them once, SURVEY.md 8e)

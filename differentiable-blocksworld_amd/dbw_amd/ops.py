@@ -1350,6 +1350,84 @@ def depth_cloud_host(depth, cams, target, poses, lo, hi, grid=128, d_range=(1, 6
     return out + ([len(rows), n_in, n_out],) if return_info else out
 
 
+def _depth_ray_args(shape, cams, target, poses, d_range, stride, edge):
+    cams, target, poses, _, _, d_min, d_max, stride, permille, _ = _depth_args(shape, cams, target, poses, 0.0, 1.0, 1, d_range, stride, edge, 1)
+    return cams, target, poses, d_min, d_max, stride, permille
+
+
+def depth_rays(depth, cams, target, poses, d_range=(1, 65535), stride=1, edge=0.0, device=None):
+    """dbw_lens_depth_rays: (N,H,W) 16-bit depth maps -> the dense record array (N, ceil(H/stride), ceil(W/stride), 4) int32 on depth's device:
+    the three fp32 words of the ray's end -- the world point exactly as ops.depth_cloud forms it before its cube -- and the frame, -1 (after
+    three zeros) where there is no measurement (lens, range, edge rule, a coordinate that is not finite).  Arguments as ops.depth_cloud's,
+    without the grid and the cube.  Nothing is read by the host; ops.depth_rays_compact keeps the valid records."""
+    _lib.family('lens')
+    if isinstance(depth, np.ndarray):
+        if depth.dtype != np.uint16:
+            raise TypeError(f'depth: a numpy array of uint16, got {depth.dtype}')
+        depth = torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(device or 'cuda')
+    if depth.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)):
+        raise TypeError(f'depth: torch.int16 holding the 16 bits (or torch.uint16), got {depth.dtype}')
+    if not depth.is_cuda:
+        raise RuntimeError('depth_rays runs on the GPU (ops.depth_rays_host is the numpy path)')
+    depth = depth.contiguous()
+    cams, target, poses, d_min, d_max, stride, permille = _depth_ray_args(depth.shape, cams, target, poses, d_range, stride, edge)
+    N, H, W = depth.shape
+    Hs, Ws = -(-H // stride), -(-W // stride)
+    if N * Hs * Ws >= 1 << 31:
+        raise ValueError(f'{N * Hs * Ws} samples: below 2^31 a call')
+    rays = torch.empty(N, Hs, Ws, 4, dtype=torch.int32, device=depth.device)
+    _lib.call('dbw_lens_depth_rays', _ptr(depth), N, H, W, cams.ctypes.data, target.ctypes.data, poses.ctypes.data, d_min, d_max, stride, permille,
+              _ptr(rays), _stream(depth))
+    return rays
+
+
+def depth_rays_host(depth, cams, target, poses, d_range=(1, 65535), stride=1, edge=0.0):
+    """ops.depth_rays in numpy, for a run without a GPU: -> (N, Hs, Ws, 4) int32 as a numpy array, the same bytes as the kernel
+    (csrc/depth_math.h depth_ray_end operation by operation in float32)."""
+    F = np.float32
+    if torch.is_tensor(depth):
+        depth = depth.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+    depth = np.ascontiguousarray(depth)
+    if depth.dtype != np.uint16:
+        raise TypeError(f'depth: uint16, got {depth.dtype}')
+    cams, target, poses, d_min, d_max, stride, permille = _depth_ray_args(depth.shape, cams, target, poses, d_range, stride, edge)
+    N, H, W = depth.shape
+    i, j = np.meshgrid(np.arange(0, H, stride), np.arange(0, W, stride), indexing='ij')
+    Hs, Ws = i.shape
+    i, j = i.reshape(-1), j.reshape(-1)
+    out = np.zeros((N, Hs * Ws, 4), np.int32)
+    with np.errstate(all='ignore'):
+        for n in range(N):
+            x, y, u, v = _lens_rect_source32(cams[n], target, i, j)
+            fu, fv = np.floor(u + F(0.5)), np.floor(v + F(0.5))
+            keep = (fu >= F(0.0)) & (fu <= F(W - 1)) & (fv >= F(0.0)) & (fv <= F(H - 1))                     # (False for a NaN)
+            sx, sy = np.where(keep, fu, F(0.0)).astype(np.int64), np.where(keep, fv, F(0.0)).astype(np.int64)
+            frame = depth[n].astype(np.int64)
+            d = frame[sy, sx]
+            keep &= (d >= d_min) & (d <= d_max)
+            if permille > 0:
+                for inside, ny, nx in ((sx > 0, sy, sx - 1), (sx < W - 1, sy, sx + 1), (sy > 0, sy - 1, sx), (sy < H - 1, sy + 1, sx)):
+                    nb = frame[np.clip(ny, 0, H - 1), np.clip(nx, 0, W - 1)]
+                    keep &= ~(inside & ((nb == 0) | (1000 * np.abs(d - nb) > permille * d)))
+            z = d.astype(F)
+            cx, cy = x * z, y * z
+            A = poses[n]
+            p = np.stack([((A[3 * a] * cx + A[3 * a + 1] * cy) + A[3 * a + 2] * z) + A[9 + a] for a in range(3)], 1).astype(F)
+            keep &= np.isfinite(p).all(1)
+            out[n, :, :3] = np.where(keep[:, None], p, F(0.0)).view(np.int32)
+            out[n, :, 3] = np.where(keep, n, -1)
+    return out.reshape(N, Hs, Ws, 4)
+
+
+def depth_rays_compact(rays):
+    """The valid records of ops.depth_rays / depth_rays_host, order kept -> (ends (Nr,3) float32, frame (Nr,) int32), torch tensors on the
+    records' device: one boolean mask, taken once when a scene is loaded, not on the step path."""
+    r = torch.as_tensor(rays).reshape(-1, 4)
+    keep = r[:, 3] >= 0
+    r = r[keep]
+    return r[:, :3].contiguous().view(torch.float32), r[:, 3].contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # camera pose refinement (include/dbw_lens.h, DESIGN.md 6o)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -2086,3 +2164,195 @@ def surface_term(points, verts, faces, face_group, group_keep, vert_alpha, vert_
     kw = dict(n_points=int(n_points or 0), tau=float(tau), back=float(back), seed=int(seed), step=int(step), weight=float(weight),
               back_count=back_count, segment=int(segment))
     return _SurfaceTerm.apply(verts, vert_alpha, points, faces, face_group, group_keep, vert_group, kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the free-space term
+FREESPACE_STREAM = 3        # csrc/freespace_math.h
+FREESPACE_GRAZE = 2.0 ** -16
+
+
+def _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, n_rays):
+    for t, dt, name in ((ends, torch.float32, 'ends'), (frame, torch.int32, 'frame'), (origins, torch.float32, 'origins'), (verts, torch.float32, 'verts'),
+                        (faces, torch.int32, 'faces'), (face_group, torch.int32, 'face_group'), (group_keep, torch.int32, 'group_keep'),
+                        (group_alpha, torch.int32, 'group_alpha'), (vert_alpha, torch.float32, 'vert_alpha')):
+        if t is not None:
+            _chk(t, dt, name)
+            if not t.is_contiguous():
+                raise RuntimeError(f'free-space term: {name} must be contiguous')
+    if (ends.dim() != 2 or ends.shape[1] != 3 or origins.dim() != 2 or origins.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3
+            or faces.dim() != 2 or faces.shape[1] != 3):
+        raise ValueError(f'free-space term: ends (Nr,3), origins (Nf,3), verts (V,3), faces (F,3) expected, got {tuple(ends.shape)}, '
+                         f'{tuple(origins.shape)}, {tuple(verts.shape)}, {tuple(faces.shape)}')
+    Nr, Nf, V, F_, G = ends.shape[0], origins.shape[0], verts.shape[0], faces.shape[0], face_group.numel() - 1
+    if frame.numel() != Nr:
+        raise ValueError(f'free-space term: frame has {frame.numel()} entries for {Nr} rays')
+    if group_keep is not None and group_keep.numel() != G:
+        raise ValueError(f'free-space term: group_keep has {group_keep.numel()} entries for {G} groups')
+    if group_alpha.numel() != G:
+        raise ValueError(f'free-space term: group_alpha has {group_alpha.numel()} entries for {G} groups')
+    A = 0 if vert_alpha is None else vert_alpha.numel()
+    M = int(n_rays) if n_rays else Nr
+    return Nr, Nf, V, F_, G, A, M
+
+
+def freespace_workspace(M, F_, V, G, segment, device):
+    nbytes = _lib.family('eval').dbw_eval_freespace_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
+    if nbytes == 0:
+        raise ValueError(f'free-space term: sizes M={M}, F={F_}, V={V}, G={G}, segment={segment} are refused (include/dbw_eval.h)')
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+
+
+def freespace_records(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, *, n_rays, tau, margin, seed, step,
+                      cull=False, segment=0, faces_host=None, layout=0):
+    """dbw_eval_freespace_fwd on device tensors, arguments as in include/dbw_eval.h -> (records (M,4) int32: t bits, face, u bits, v bits;
+    value (1,) float64: the mean of a psi; the workspace, which freespace_grads reads).  faces_host: an int32 CPU copy of faces, checked
+    against V before the launch.  cull: the slab test per group, off by default -- in the default layout it costs a few percent more than it
+    saves (profiles/freespace_term.md), and without it the records hold for any mesh, not only under the condition of DESIGN.md 6v.
+    layout: the forward's schedule (0: the default; 1: a workgroup per 256 rays walks every face; 2: a grid
+    of ray tiles x face chunks with an integer atomic minimum) -- the same bytes.  Everything is enqueued on the current stream; nothing is
+    read by the host."""
+    Nr, Nf, V, F_, G, A, M = _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, n_rays)
+    dev = ends.device
+    ws = freespace_workspace(M, F_, V, G, segment, dev)
+    records = torch.empty(M, 4, dtype=torch.int32, device=dev)
+    value = torch.empty(1, dtype=torch.float64, device=dev)
+    if faces_host is not None and (faces_host.dtype != torch.int32 or faces_host.is_cuda or not faces_host.is_contiguous() or faces_host.shape != faces.shape):
+        raise ValueError('free-space term: faces_host is a contiguous int32 CPU copy of faces')
+    with torch.cuda.device(dev):
+        _lib.family('eval')
+        _lib.call('dbw_eval_freespace_fwd', _ptr(ends), _ptr(frame), _ptr(origins), Nr, Nf, int(n_rays or 0), int(seed), int(step), _ptr(verts), V,
+                  _ptr(faces), _ptr(faces_host), F_, _ptr(face_group), _ptr(group_keep), _ptr(group_alpha), G, _ptr(vert_alpha), A, float(tau),
+                  float(margin), int(bool(cull)), int(layout), _ptr(ws), _ptr(records), _ptr(value), _stream(ends))
+    return records, value, ws
+
+
+def freespace_grads(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, records, workspace, *, n_rays, tau, margin,
+                    seed, step, weight, grad_out=None, segment=0):
+    """dbw_eval_freespace_bwd on what freespace_records left (same arguments, same segment) -> (grad_verts (V,3), grad_alpha (A,) or None),
+    fp32, written whole.  grad_out: a one-element fp32 device tensor that multiplies both, or None."""
+    Nr, Nf, V, F_, G, A, M = _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, n_rays)
+    dev = ends.device
+    # (as for the surface term: the backward's partials are the last part of the workspace and grow with the number of segments)
+    need = _lib.family('eval').dbw_eval_freespace_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
+    if need == 0 or workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
+        raise ValueError(f'free-space term: the workspace has {workspace.numel() * workspace.element_size()} bytes, segment={segment} needs {need}: '
+                         'give freespace_records the same segment')
+    if tuple(records.shape) != (M, 4) or records.dtype != torch.int32 or not records.is_contiguous():
+        raise ValueError(f'free-space term: records (M,4) int32 of freespace_records expected, got {tuple(records.shape)} {records.dtype}')
+    if grad_out is not None:
+        _chk(grad_out, torch.float32, 'grad_out')
+    g_verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    g_alpha = torch.empty(A, dtype=torch.float32, device=dev) if A else None
+    with torch.cuda.device(dev):
+        _lib.family('eval')
+        _lib.call('dbw_eval_freespace_bwd', _ptr(ends), _ptr(frame), _ptr(origins), Nr, Nf, int(n_rays or 0), int(seed), int(step), _ptr(verts), V,
+                  _ptr(faces), F_, G, _ptr(vert_alpha), A, float(tau), float(margin), float(weight), _ptr(grad_out), int(segment), _ptr(records),
+                  _ptr(workspace), _ptr(g_verts), _ptr(g_alpha), _stream(ends))
+    return g_verts, g_alpha
+
+
+class _FreespaceTerm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, vert_alpha, ends, frame, origins, faces, face_group, group_keep, group_alpha, kw):
+        v = verts.detach().contiguous()
+        a = None if vert_alpha is None else vert_alpha.detach().contiguous()
+        records, value, ws = freespace_records(ends, frame, origins, v, faces, face_group, group_keep, group_alpha, a, n_rays=kw['n_rays'], tau=kw['tau'],
+                                               margin=kw['margin'], seed=kw['seed'], step=kw['step'], segment=kw['segment'])
+        ctx.kw = kw
+        ctx.save_for_backward(v, a, ends, frame, origins, faces, face_group, group_keep, group_alpha, records, ws)
+        return (value[0] * kw['weight']).to(torch.float32)        # (fp64 on the device, rounded once)
+
+    @staticmethod
+    def backward(ctx, g):
+        v, a, ends, frame, origins, faces, face_group, group_keep, group_alpha, records, ws = ctx.saved_tensors
+        kw = ctx.kw
+        g_verts, g_alpha = freespace_grads(ends, frame, origins, v, faces, face_group, group_keep, group_alpha, a, records, ws, n_rays=kw['n_rays'],
+                                           tau=kw['tau'], margin=kw['margin'], seed=kw['seed'], step=kw['step'], weight=kw['weight'],
+                                           grad_out=g.detach().reshape(1).to(torch.float32).contiguous(), segment=kw['segment'])
+        return (g_verts, (g_alpha if (a is not None and ctx.needs_input_grad[1]) else None)) + (None,) * 8
+
+
+def freespace_term(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, *, n_rays, tau, margin, seed, step, weight,
+                   segment=0):
+    """The free-space term of DESIGN.md 6v as ONE autograd node:
+        weight * (1/M) sum_i a_{k(i)} psi(g_i),   g_i = (1 - t*_i) l_i - margin,   psi(g) = 0 | g^2 | tau (2 g - tau)
+    -> the fp32 scalar of the fp64 value; gradients to verts (V,3) and to vert_alpha (A,).  Ray j runs from origins[frame[j]] to ends[j];
+    n_rays draws a step (0: all rays in order), taken inside the kernels from (seed, step); t* is the first hit of the ray with the faces
+    (F,3) int32 of the groups face_group (G+1) that group_keep (G, int32 or None) keeps; group_alpha (G) int32: a group's row of vert_alpha,
+    -1 for the ground (a = 1).  Parts: freespace_records, freespace_grads."""
+    kw = dict(n_rays=int(n_rays or 0), tau=float(tau), margin=float(margin), seed=int(seed), step=int(step), weight=float(weight), segment=int(segment))
+    return _FreespaceTerm.apply(verts, vert_alpha, ends, frame, origins, faces, face_group, group_keep, group_alpha, kw)
+
+
+def freespace_draw(seed, step, n_rays, n_total):
+    """The ray indices a step draws (csrc/freespace_math.h: freespace_draw_index), on the host: word 0 of Philox4x32-10 with counter
+    (i, 3, step) and key seed, mod the number of rays -> (n_rays,) int64."""
+    i = np.arange(int(n_rays), dtype=np.uint64)
+    c = [i, np.full_like(i, FREESPACE_STREAM), np.full_like(i, int(step) & 0xffffffff), np.full_like(i, (int(step) >> 32) & 0xffffffff)]
+    k = [np.uint64(int(seed) & 0xffffffff), np.uint64((int(seed) >> 32) & 0xffffffff)]
+    m32 = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k[0]) & m32, p1 & m32, ((p0 >> np.uint64(32)) ^ c[3] ^ k[1]) & m32, p0 & m32]
+        k = [(k[0] + np.uint64(0x9E3779B9)) & m32, (k[1] + np.uint64(0xBB67AE85)) & m32]
+    return torch.from_numpy((c[0] % np.uint64(int(n_total))).astype(np.int64))
+
+
+def freespace_first_hits(o, e, tri):
+    """o, e (n,3), tri (F,3,3) -> (t (n,F), u, v, candidate (n,F) bool): Moeller-Trumbore of DESIGN.md 6v for every ray and face, in the
+    tensors' dtype; t, u, v are only meaningful where candidate is set."""
+    a = tri[None, :, 0]
+    e1, e2 = tri[None, :, 1] - a, tri[None, :, 2] - a
+    n = torch.linalg.cross(e1, e2)
+    eb = e[:, None, :]
+    det = -(n * eb).sum(-1)
+    ok = det * det > FREESPACE_GRAZE * (n * n).sum(-1) * (eb * eb).sum(-1)
+    den = torch.where(ok, det, torch.ones_like(det))
+    h = torch.linalg.cross(eb.expand(-1, tri.shape[0], -1), e2.expand(e.shape[0], -1, -1))
+    s = o[:, None, :] - a
+    q = torch.linalg.cross(s, e1.expand_as(s))
+    u, v, t = (s * h).sum(-1) / den, (eb * q).sum(-1) / den, (e2 * q).sum(-1) / den
+    return t, u, v, ok & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0) & (t < 1)
+
+
+def freespace_term_torch(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, *, n_rays, tau, margin, seed, step,
+                         weight, chunk=1024):
+    """ops.freespace_term in torch, in the dtype of verts, on any device: the readable statement of DESIGN.md 6v, the timing baseline of
+    tools/freespace_bench.py and, in float64, the gradient reference of the tests.  The first hit is selected without a graph; t* of the
+    selected face is then formed again from the vertices, so autograd differentiates the intersection itself."""
+    dt, dev = verts.dtype, verts.device
+    P, O = ends.to(device=dev, dtype=dt), origins.to(device=dev, dtype=dt)
+    Nr, G = P.shape[0], face_group.numel() - 1
+    idx = freespace_draw(seed, step, n_rays, Nr).to(dev) if n_rays else torch.arange(Nr, device=dev)
+    counts = (face_group[1:] - face_group[:-1]).to(torch.int64)
+    fgroup = torch.repeat_interleave(torch.arange(G, device=dev), counts.to(dev), output_size=faces.shape[0])
+    fk = torch.ones(faces.shape[0], dtype=torch.bool, device=dev) if group_keep is None else group_keep.to(dev).to(torch.bool)[fgroup]
+    fid = fk.nonzero().flatten()
+    fc = faces.to(torch.int64)[fid]
+    row = group_alpha.to(dev).to(torch.int64)[fgroup[fid]]
+    ones = verts.new_ones(1)
+    alpha = ones if vert_alpha is None else torch.cat([vert_alpha.to(dt), ones])        # (row -1: the ground's 1)
+    fr = frame.to(dev).to(torch.int64)[idx]
+    valid = (fr >= 0) & (fr < O.shape[0])
+    idx, fr = idx[valid], fr[valid]
+    total = verts.new_zeros(())
+    for s0 in range(0, idx.shape[0], chunk):
+        p, o = P[idx[s0:s0 + chunk]], O[fr[s0:s0 + chunk]]
+        e = p - o
+        with torch.no_grad():
+            t, _, _, cand = freespace_first_hits(o, e, verts.detach()[fc])
+            t = torch.where(cand, t, torch.full_like(t, float('inf')))
+            j = t.argmin(1)
+            hit = cand.any(1)
+        if not bool(hit.any()):
+            continue
+        o, e, j = o[hit], e[hit], j[hit]
+        tri = verts[fc[j]]
+        e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+        n = torch.linalg.cross(e1, e2)
+        ts = (n * (tri[:, 0] - o)).sum(-1) / (n * e).sum(-1)
+        g = (1 - ts) * e.norm(dim=-1) - float(margin)
+        psi = torch.where(g <= 0, torch.zeros_like(g), torch.where(g <= tau, g * g, float(tau) * (2 * g - float(tau))))
+        total = total + (alpha[row[j]] * psi).sum()
+    M = int(n_rays) if n_rays else Nr
+    return float(weight) * total / M

@@ -103,4 +103,6 @@ def fast_path_refusal(model, renderer=None):
         return 'too many faces or maps for the packed face | map word'
     if 'surface' in m.loss_weights:
         return 'a surface term'
+    if 'freespace' in m.loss_weights:
+        return 'a free-space term'
     return None

@@ -1,6 +1,7 @@
 """python -m dbw_amd.train --config C --tag T --data-root D --runs-root R [--epochs N]
                           [--lpips-vgg F --lpips-lin F | --perceptual ssim | --no-perceptual] [--resume [TAG]] [--no-record]
                           [--pose-refine LR] [--blocks-init points] [--exposure LR] [--intrinsics-refine LR] [--surface WEIGHT]
+                          [--freespace WEIGHT]
 
 A run of one of the reference's configs, end to end, as its src/trainer.py:275-295 starts one: the config is loaded (the default.yml next
 to it, then the file), the scenes of cfg['dataset'] (dtu, bmvs or custom) are read from <data-root>, the model is built from cfg['model'], trained by Trainer,
@@ -42,7 +43,11 @@ printed and it is written to <run_dir>/depth_cloud.ply.
 
 model.loss.surface_weight -- or --surface WEIGHT -- with model.loss.surface: {points, tau, back, ground, start_epoch, max_cloud} on a custom
 scene with a point cloud: the surface term keeps the blocks on the cloud during training, loss_surface is a column of
-train_metrics.tsv.  The steps then take the general path (the one-call C step stands aside, as for masks)."""
+train_metrics.tsv.  The steps then take the general path (the one-call C step stands aside, as for masks).
+
+model.loss.freespace_weight -- or --freespace WEIGHT -- with model.loss.freespace: {rays, tau, margin, ground, start_epoch, max_rays} on a
+custom scene with depth maps (dataset.cloud: depth): the free-space term pushes the blocks out of the space the depth rays
+crossed on their way to the measured surface, loss_freespace is a column of train_metrics.tsv.  The general path, as above."""
 import argparse
 import os
 import sys
@@ -75,6 +80,9 @@ def parse_args(argv=None):
                     help="'points': start the blocks at the clusters of the custom scene's point cloud (training.blocks_init)")
     ap.add_argument('--surface', type=float, default=None, metavar='WEIGHT',
                     help="keep the blocks on the custom scene's point cloud: the weight of the surface term (model.loss.surface_weight)")
+    ap.add_argument('--freespace', type=float, default=None, metavar='WEIGHT',
+                    help="keep the blocks out of the space the custom scene's depth rays crossed: the weight of the free-space term "
+                         '(model.loss.freespace_weight)')
     ap.add_argument('--device', default='cuda:0')
     return ap.parse_args(argv)
 
@@ -112,6 +120,8 @@ def prepare_config(args):
         cfg['training']['exposure'] = dict(entry if isinstance(entry, dict) else {}, lr=args.exposure)
     if getattr(args, 'surface', None) is not None:
         cfg.setdefault('model', {}).setdefault('loss', {})['surface_weight'] = args.surface
+    if getattr(args, 'freespace', None) is not None:
+        cfg.setdefault('model', {}).setdefault('loss', {})['freespace_weight'] = args.freespace
     if getattr(args, 'blocks_init', None) is not None and not isinstance(cfg.setdefault('training', {}).get('blocks_init'), dict):
         cfg['training']['blocks_init'] = args.blocks_init      # (a mapping in the config already asks for the points, with its options)
     return cfg
@@ -246,6 +256,29 @@ def resolve_surface(scene, model, device):
     return n
 
 
+def resolve_freespace(scene, model, device):
+    """model.loss.freespace_weight > 0: the model gets the scene's depth rays (scene.rays: every depth sample of a capture with
+    dataset.cloud: depth, from its camera's centre) for the free-space term and the number it keeps is printed -> that number,
+    or None without the weight.  A custom scene without depth maps is refused with the scene's own words, and so are the DTU / BlendedMVS
+    scenes: they ship no depth maps, and their cloud is the ground truth the scores are computed against.  A resumed run comes here too: a
+    checkpoint does not carry the rays."""
+    if 'freespace' not in getattr(model, 'loss_weights', {}):
+        return None
+    if scene.name != 'custom':
+        raise SystemExit(f"model.loss.freespace_weight is for custom scenes with depth maps: a '{scene.name}' scene ships none, and its cloud is "
+                         'the ground truth its scores are computed against')
+    try:
+        ends, frame, origins = scene.rays(device)
+    except ValueError as e:
+        raise SystemExit(f'model.loss.freespace_weight: {e}') from e
+    n = model.set_freespace_rays(ends, frame, origins)
+    scene.release_rays(device)                      # (the model keeps its own, thinned copy: the scene's full set is read by nothing else)
+    c = model.freespace_cfg
+    print(f"freespace: weight {model.loss_weights['freespace']:g} on {n} of {len(ends)} rays of {len(origins)} frames, {c['rays'] or n} a step, "
+          f"tau {c['tau']:g}, margin {c['margin']:g}, from epoch {c['start_epoch']}")
+    return n
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = prepare_config(args)
@@ -272,6 +305,7 @@ def main(argv=None):
     model = create_model(cfg, train.img_size).to(args.device).train()
     resolve_blocks_init(cfg, train, model, args.device, run_dir, start.get('resume') or start.get('pretrained'))
     resolve_surface(train, model, args.device)
+    resolve_freespace(train, model, args.device)
     if 'perceptual' in model.loss_weights and model.perceptual_name != 'ssim':     # (ssim: the model installed its built-in term)
         from .lpips_vgg import LPIPSVGG
         net = LPIPSVGG()

@@ -167,6 +167,10 @@ class Trainer:
         if 'surface' in getattr(model, 'loss_weights', {}) and ws > 1:
             raise NotImplementedError('model.loss.surface_weight under data parallelism: every rank would add the whole term, and the ranks '
                                       'do not share out its points')
+        # ... and so is the free-space term (model.loss.freespace_weight) on the capture's depth rays
+        if 'freespace' in getattr(model, 'loss_weights', {}) and ws > 1:
+            raise NotImplementedError('model.loss.freespace_weight under data parallelism: every rank would add the whole term, and the ranks '
+                                      'do not share out its rays')
         # Validity masks ride along like every key of `views`; the sum of each view's mask is taken once, here (one host copy, fp64), so
         # that a batch carries its valid count as a host number ('mask_sum') and no step reads the device for it
         self.mask_sums = None

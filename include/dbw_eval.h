@@ -126,6 +126,44 @@ int dbw_eval_surface_bwd(const float *points, int64_t N, int64_t n_points, int64
                          float tau, float back, float weight, const float *grad_out, int segment, const void *records, void *workspace,
                          float *grad_verts, float *grad_alpha, dbw_stream_t stream);
 
+/* The free-space term (csrc/freespace_term.hip, arithmetic csrc/freespace_math.h), added under revision 1 of this header: a
+ * capture's depth rays against the posed meshes, in the frame of both.
+ *   value[0] = (1/M) sum_i a_{k(i)} psi(g_i), fp64.  Ray j runs from origins[frame[j]] to ends[j]: ends (Nr,3) fp32, frame (Nr) int32 (a
+ *     frame outside [0, Nf) is a ray without a hit), origins (Nf,3) fp32.  n_rays > 0: M = n_rays draws, draw i is ray
+ *     step_random(seed, step, stream 3, i).x mod Nr (csrc/rng_math.h), taken inside the kernels; n_rays == 0: M = Nr, all rays in order.
+ *   verts, faces, faces_host, face_group, group_keep: as for dbw_eval_surface_fwd.  group_alpha (G) int32: a group's row of vert_alpha (A)
+ *     fp32, or -1 (the ground: a = 1).  A == 0: vert_alpha may be NULL and every a is 1.
+ *   With o the origin, e = end - o, l = |e| and, per face (a, b, c), e1 = b - a, e2 = c - a, n = e1 x e2, h = e x e2, s = o - a, q = s x e1,
+ *     det = -(n . e), u = (s . h)/det, v = (e . q)/det, t = (e2 . q)/det: a face is a candidate when det^2 > 2^-16 (n . n)(e . e), u >= 0,
+ *     v >= 0, u + v <= 1 and 0 < t < 1 (two-sided).  The first hit is the smallest t, the lowest face on equal t.
+ *     g = (1 - t) l - margin;  psi(g) = 0 for g <= 0, g^2 for g <= tau, tau (2 g - tau) beyond.
+ *   records (M) of 16 bytes, 16-byte aligned: t fp32, face int32, u, v fp32.  A ray without a candidate: face -1, t NaN; it adds 0.
+ *   cull (0 | 1): skip a group whose slackened box no segment t in (0, best t) of a wave reaches.  Records and value do not depend on it for
+ *     meshes whose faces have sin(e1, e2) >= 2^-4 (DESIGN.md 6v has the derivation; thinner faces met at the grazing limit are outside it).
+ *   layout (0 | 1 | 2): the forward's schedule; records and value are the same bytes.  1: one workgroup per 256 rays walks every face.
+ *     2, and 0 (the default): a grid of (256 rays x 128 faces), the first hit taken with a 64-bit integer atomic minimum of the key
+ *     (bits(t) << 32) | face, its (t, u, v) formed again for the winner.
+ *   A face index outside [0, V) is read as vertex 0 by both calls (faces_host refuses it before any launch).
+ * dbw_eval_freespace_bwd, on the records and the workspace that dbw_eval_freespace_fwd left for the same arguments: with L = weight * value[0],
+ *   grad_verts (V,3) fp32 = grad_out[0] * dL/dverts (-(weight/M) a psi'(g) l wts_m n / (n . e) per record, wts = (1-u-v, u, v),
+ *   psi'(g) = 2 min(g, tau)), grad_alpha (A) fp32 or NULL when A == 0 = grad_out[0] * (weight/M) * the sum of psi over the records that hit
+ *   the block.  grad_out: one fp32 on the device, or NULL (= 1).  Both outputs are written whole.  No floating-point atomics: records are
+ *   walked in segments of `segment` (0: DBW_EVAL_FREESPACE_SEGMENT; else in [64, 2^20]) in index order, the segments added in order.
+ * 1 <= Nr < 2^31, 1 <= Nf <= 2^20, 1 <= M <= 2^24, 1 <= F <= 2^20, 1 <= V <= 2^21, 1 <= G <= 4096, 0 <= A <= V, tau > 0, margin >= 0.
+ * workspace: dbw_eval_freespace_workspace_bytes(M, F, V, G, segment) bytes (0: sizes refused), 16-byte aligned, kept untouched between the
+ * two calls; `segment` is the one dbw_eval_freespace_bwd will be given (its partials are the last part of the workspace). */
+#define DBW_EVAL_FREESPACE_SEGMENT 1024
+size_t dbw_eval_freespace_workspace_bytes(int64_t M, int F, int V, int G, int segment);
+int dbw_eval_freespace_fwd(const float *ends, const int32_t *frame, const float *origins, int64_t Nr, int Nf, int64_t n_rays, int64_t seed,
+                           int64_t step, const float *verts, int V, const int32_t *faces, const int32_t *faces_host, int F,
+                           const int32_t *face_group, const int32_t *group_keep, const int32_t *group_alpha, int G, const float *vert_alpha,
+                           int A, float tau, float margin, int cull, int layout, void *workspace, void *records, double *value,
+                           dbw_stream_t stream);
+int dbw_eval_freespace_bwd(const float *ends, const int32_t *frame, const float *origins, int64_t Nr, int Nf, int64_t n_rays, int64_t seed,
+                           int64_t step, const float *verts, int V, const int32_t *faces, int F, int G, const float *vert_alpha, int A,
+                           float tau, float margin, float weight, const float *grad_out, int segment, const void *records, void *workspace,
+                           float *grad_verts, float *grad_alpha, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

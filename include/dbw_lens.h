@@ -154,6 +154,19 @@ int dbw_lens_depth_cloud(const uint16_t *depth, int N, int H, int W, const float
                          const float *box, int G, int d_min, int d_max, int stride, int edge_permille, int min_count, void *workspace,
                          float *points, int32_t *counts, int64_t capacity, int64_t *info, dbw_stream_t stream);
 
+/* The depth rays of a capture, added under revision 1 of this header (csrc/depth_cloud.hip, arithmetic: csrc/depth_math.h depth_ray_end): the
+ * arguments of dbw_lens_depth_cloud without the grid and the cube.  rays on the DEVICE, 16-byte aligned: a dense array
+ * (N, ceil(H / stride), ceil(W / stride)) of 16-byte records [px, py, pz fp32, frame int32], one per target pixel (i, j) with i % stride == 0
+ * and j % stride == 0 of every frame, every record written.  (px, py, pz) is the world point p = A.c + t exactly as dbw_lens_depth_cloud
+ * forms it (the same operations in the same order, the same lens map, the nearest source pixel) and frame is n; where
+ * dbw_lens_depth_cloud drops the sample before the cube (lens, range, edge rule) or a coordinate of p is not finite, the record is
+ * [0, 0, 0, -1].  The cube is not applied.  Refused before any launch (DBW_ERR_INVALID): a null pointer; a misaligned one (rays 16 bytes,
+ * depth 2); N, H, W or stride below 1; d_min outside [1, d_max] or d_max above 65535; edge_permille outside [0, 1000];
+ * N * ceil(H / stride) * ceil(W / stride) of 2^31 or more; a value of cams, target or poses that is not finite, and the cameras
+ * dbw_lens_rectify_u8 refuses. */
+int dbw_lens_depth_rays(const uint16_t *depth, int N, int H, int W, const float *cams, const float *target, const float *poses, int d_min,
+                        int d_max, int stride, int edge_permille, void *rays, dbw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
