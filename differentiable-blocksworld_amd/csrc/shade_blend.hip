@@ -1188,8 +1188,15 @@ __global__ __launch_bounds__(256) void texbin_reduce_kernel(const int *__restric
         const int e_b = max(min(E, 254) - 126, BIN_FIX_EMIN);
         if (e_b > e_tile) {                                    // (uniform: every thread read the same four words)
             if (e_tile > -1000) {
-                const int sh = min(e_b - e_tile, (int)sizeof(bin_fix_t) * 8 - 1);
-                for (int i = threadIdx.x; i < 33 * 33 * 3; i += 256) { const bin_fix_t q = tile[i]; if (q) tile[i] = (q + ((bin_fix_t)1 << (sh - 1))) >> sh; }
+                // round(q / 2^sh), halves up, without leaving int32: the budget lets |q| reach 2^31 - 1, and `(q + (1 << (sh - 1))) >> sh` wrapped
+                // for q > 2^31 - 2^(sh-1) (-1 unit where 0.7 rounds to 1; tests/test_gpu_texbin_reduce.py).  A raise of more than 31 bits leaves
+                // less than half a unit of anything the tile can hold.
+                const int sh = e_b - e_tile;
+                const bool gone = sh > (int)sizeof(bin_fix_t) * 8 - 1;
+                for (int i = threadIdx.x; i < 33 * 33 * 3; i += 256) {
+                    const bin_fix_t q = tile[i];
+                    if (q) tile[i] = gone ? 0 : (q >> sh) + ((q >> (sh - 1)) & 1);
+                }
                 __syncthreads();
             }
             e_tile = e_b;

@@ -2,7 +2,7 @@
 // tests/_build/libdbw_device_checks.so by differentiable-blocksworld_amd/build.py: build_device_checks, loaded by tests/device_checks.py).
 // The kernels of libdbw_hip.so take their per-pair / per-vertex / per-lane arithmetic from host+device headers (csrc/raster_math.h,
 // csrc/model_math.h, csrc/dbw_common.h); the host tests hold the HOST build of those headers to the oracle and to the reference's golden
-// vectors -- these three entry points evaluate the SAME inline functions on the GPU (its v_rcp_f32, its powf / logf / expf, its DPP
+// vectors -- these entry points evaluate the SAME inline functions on the GPU (its v_rcp_f32, its powf / logf / expf, its DPP
 // lanes) on caller-supplied operands, compiled with the product's flags.  They used to be exported by the product library itself.
 #include "../differentiable-blocksworld_amd/csrc/dbw_common.h"
 #include "../differentiable-blocksworld_amd/csrc/model_math.h"
@@ -65,6 +65,32 @@ __global__ void model_math_kernel(int what, const float *__restrict__ a, const f
     }
 }
 
+// LdsAgg<3, LOG2> (dbw_common.h: the LDS hash table in front of the texel-gradient atomics; TexAgg = 256 slots, HardTexAgg = 64) on
+// caller-supplied (key, active, value[3]) triples: every workgroup of 256 threads clears a table, runs `rounds` rounds of one of the
+// three adds -- thread t of workgroup b takes triple (b * rounds + r) * 256 + t in round r -- and flushes into out (n_keys, 3).
+// OP 0: add (active lanes only), 1: add_wave, 2: add_wave_merged<2>.  Active keys must lie in [0, n_keys): the caller checks.
+template <int LOG2, int OP>
+__global__ __launch_bounds__(256) void lds_agg_kernel(const int *__restrict__ keys, const int *__restrict__ active, const float *__restrict__ values,
+                                                      int rounds, float *__restrict__ out) {
+    typedef LdsAgg<3, LOG2> Agg;
+    __shared__ double mem[(Agg::BYTES + 7) / 8];
+    Agg agg;
+    agg.bind(mem);
+    agg.clear(threadIdx.x, 256);
+    __syncthreads();
+    for (int r = 0; r < rounds; ++r) {
+        const long long i = ((long long)blockIdx.x * rounds + r) * 256 + threadIdx.x;
+        const int key = keys[i];
+        const bool on = active[i] != 0;
+        float v[3] = {values[i * 3], values[i * 3 + 1], values[i * 3 + 2]};
+        if (OP == 0) { if (on) agg.add(out, key, v); }
+        else if (OP == 1) agg.add_wave(out, key, v, on);
+        else agg.template add_wave_merged<2>(out, key, v, on);
+    }
+    __syncthreads();
+    agg.flush(out, threadIdx.x, 256);
+}
+
 int launched(const char *what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e)); return -3; }
@@ -90,6 +116,20 @@ extern "C" int dbwt_lane_merge(const int *keys, const int *active, const float *
     if (steps == 1) LM(1); else if (steps == 2) LM(2); else if (steps == 3) LM(3); else LM(4);
 #undef LM
     return launched("lane_merge_kernel");
+}
+
+// workgroups * rounds * 256 triples (keys, active 0 / 1, values (., 3)); log2_slots 6 | 8; op 0 add, 1 add_wave, 2 add_wave_merged<2>;
+// out (n_keys, 3) zeroed by the caller, every ACTIVE key in [0, n_keys) (inactive lanes may carry anything)
+extern "C" int dbwt_lds_agg(const int *keys, const int *active, const float *values, int workgroups, int rounds, int log2_slots, int op,
+                            float *out, void *stream) {
+    if (!keys || !active || !values || !out || workgroups < 0 || rounds < 1 || (log2_slots != 6 && log2_slots != 8) || op < 0 || op > 2) return -1;
+    if (workgroups == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+#define LA(L, O) hipLaunchKernelGGL((lds_agg_kernel<L, O>), dim3(workgroups), dim3(256), 0, s, keys, active, values, rounds, out)
+    if (log2_slots == 6) { if (op == 0) LA(6, 0); else if (op == 1) LA(6, 1); else LA(6, 2); }
+    else { if (op == 0) LA(8, 0); else if (op == 1) LA(8, 1); else LA(8, 2); }
+#undef LA
+    return launched("lds_agg_kernel");
 }
 
 // what = 0: superquadric surface point (superquadric.py:10-14); 1: implicit superquadric distance (superquadric.py:17-38, as_sdf = 2, clamped

@@ -178,13 +178,16 @@ def _block_alpha(m, scene):
     return (torch.rand(scene['faces'].shape[0] // m.BNF, generator=torch.Generator().manual_seed(1)) * 0.8 + 0.1).repeat_interleave(m.BNF)
 
 
-def _soft(fpp, hw=(48, 64), clip_inside=True):
-    m, R, T, Km = _model(fpp=fpp, hw=hw)
+def _soft(fpp, hw=(48, 64), clip_inside=True, ts=32, decimate=0, seed=3):
+    """decimate d: the maps are the nearest-upsampled copy of their d x d cell averages (dbw.py:331-334), as the decimated training phase
+    renders them.  The maps of the scene carry the circular padding `pads` = m.txt_padding in u."""
+    m, R, T, Km = _model(seed=seed, fpp=fpp, hw=hw, ts=ts)
+    m.decim_factor = decimate or m.decim_factor
     with torch.no_grad():
-        scene = m.build_blocks(True, True, False, None, kill_blocks=False)
+        scene = m.build_blocks(True, True, bool(decimate), None, kill_blocks=False)
     bg = (0., 0., 0.) if clip_inside else (0.1, 0.2, 0.3)
     return dict(scene=scene, R=R, T=T, Kmat=Km[0], H=hw[0], W=hw[1], sigma=1e-4, K=fpp, detach_bary=True, faces_alpha=_block_alpha(m, scene), bg=bg,
-                clip_inside=clip_inside, const_faces=0)
+                clip_inside=clip_inside, const_faces=0, pads=tuple(m.txt_padding), decimate=decimate)
 
 
 def _fine():
@@ -197,14 +200,15 @@ def _fine():
                 const_faces=0)
 
 
-def _env(rig, hw=(48, 64), const=False, seed=7):
+def _env(rig, hw=(48, 64), const=False, seed=7, decimate=0):
     m, _, _, _ = _model(seed=seed, ts=16, hw=hw)
+    m.decim_factor = decimate or m.decim_factor
     R, T, Km = O.synthetic_cameras(3, R_world=m.R_world[0], dist=2.8, elev_deg=rig[0], f_ndc=rig[1])
     with torch.no_grad():
-        scene = m.build_env(True, False)
+        scene = m.build_env(True, bool(decimate))
     nsky = int((scene['face_map'] == 0).sum())
     return dict(scene=scene, R=R, T=T, Kmat=Km[0], H=hw[0], W=hw[1], sigma=0.0, K=1, detach_bary=False, faces_alpha=None, bg=(0.1, 0.2, 0.3),
-                clip_inside=True, const_faces=nsky if const else 0)
+                clip_inside=True, const_faces=nsky if const else 0, pads=(0, 0), decimate=decimate)
 
 
 RENDER_CASES = {
@@ -218,6 +222,23 @@ RENDER_CASES = {
     # host), seed 8 measures 51; seed 9 holds 2.5 / 3.1 -- a case that sits at the cap on some host would make the host test a coin toss.
     'soft6_45x61': lambda: _soft(6, hw=(45, 61)), 'env_45x61': lambda: _env((5.0, 1.5), hw=(45, 61), seed=9),
 }
+# The texel-gradient accumulators of a training step (DESIGN.md "Texel-gradient accumulators against a float64 scatter").  A VARIANT hands
+# the library the same scene in the form a training phase stores it, and the oracle's map gradient is brought into that form:
+#   'bins'       full-resolution maps WITHOUT their circular padding (+ the wrap in the descriptor) and the texture-space bins of
+#                describe_bins, lds_aggregate off: records + dbw_texbin_reduce, wrapped footprints through the atomic fallback of the same pass;
+#   'decimated'  cell-resolution maps + descriptor shift 2 (LdsAgg when lds_aggregate is on, wave-aggregated atomics otherwise); the case's
+#                maps are the nearest-upsampled copy of the cells, the gradient of a cell is the sum over its 4x4 texels.
+# 64x64 maps: four bins per map, bilinear footprints cross from one into the halo of the next.  At 48x64 pixels such a map is minified and
+# its texel gradients are sums of few, unevenly weighted fragments: the fp32 oracle's own y(g_maps) measures 7.5, 10.9, 7.2, 26, 8.0, 9.3,
+# 9.5, 90 for model seeds 3 ... 10 -- at or near the cap -- and 5.2 for seed 12, which is taken.
+SHIFT = 2
+VARIANT_CASES = {
+    'soft6_ts64': lambda: _soft(6, ts=64, seed=12),
+    'soft6_dec4': lambda: _soft(6, decimate=1 << SHIFT), 'env_horizon_dec4': lambda: _env((5.0, 1.5), decimate=1 << SHIFT),
+}
+PLAIN_CASES = list(RENDER_CASES)                         # what the 'plain' variant runs (as before)
+RENDER_CASES.update(VARIANT_CASES)
+RENDER_VARIANTS = {'bins': ['soft6', 'soft16', 'soft6_45x61', 'soft6_ts64'], 'decimated': ['soft6_dec4', 'env_horizon_dec4']}
 RENDER_WEIGHTS = ['all', 'rgb', 'alpha']      # upstream on every channel / the colour channels only / the opacity channel only
 TENSORS = ['image', 'g_verts', 'g_maps', 'g_alpha']
 
@@ -278,23 +299,72 @@ def render_refs(name, weight='all', seed=0):
     return dict(o32=o32, o64=o64, w=w, M=M, masked=1.0 - float(M.mean()), p2f=f32['pix_to_face'])
 
 
-def hip_render(name, w, lds):
+def stored_maps(c, variant='plain'):
+    """The maps of a case as `variant` stores them -> (maps [(h, w, 3)], full-resolution shapes [(h, w)], pads (pl, pr), shift)."""
+    maps = [m.detach() for m in c['scene']['maps']]
+    if variant == 'plain':
+        return maps, [m.shape[:2] for m in maps], (0, 0), 0
+    pl, pr = c['pads']
+    unpadded = [m[:, pl:m.shape[1] - pr] for m in maps]
+    shapes = [m.shape[:2] for m in unpadded]
+    if variant == 'bins':
+        return unpadded, shapes, (pl, pr), 0
+    assert variant == 'decimated' and c['decimate'] == 1 << SHIFT
+    d = c['decimate']
+    cells = [m[::d, ::d].contiguous() for m in unpadded]
+    for m, cell in zip(unpadded, cells):                        # the case's maps ARE the nearest-upsampled copy of the cells
+        assert m.shape[0] % d == 0 and m.shape[1] % d == 0 and torch.equal(cell.repeat_interleave(d, 0).repeat_interleave(d, 1), m)
+    return cells, shapes, (pl, pr), SHIFT
+
+
+def stored_map_grads(c, g_flat, variant='plain'):
+    """The oracle's gradient of the case's (padded, full-resolution) maps, flat -> the gradient of the maps of stored_maps(c, variant), flat:
+    a padding column is a copy of the column it wraps to (F.pad circular: the last pl columns on the left, the first pr on the right) and
+    hands its gradient to it; a cell takes the sum over its texels."""
+    if variant == 'plain':
+        return g_flat
+    pl, pr = c['pads']
+    out, at = [], 0
+    for m in c['scene']['maps']:
+        h, wp = m.shape[:2]
+        g = g_flat[at:at + h * wp * 3].reshape(h, wp, 3)
+        at += h * wp * 3
+        w = wp - pl - pr
+        u = g[:, pl:pl + w].clone()
+        if pl:
+            u[:, w - pl:] += g[:, :pl]
+        if pr:
+            u[:, :pr] += g[:, pl + w:]
+        if variant == 'decimated':
+            d = c['decimate']
+            u = u.reshape(h // d, d, w // d, d, 3).sum((1, 3))
+        out.append(u.reshape(-1))
+    assert at == g_flat.numel()
+    return torch.cat(out)
+
+
+def hip_render(name, w, lds, variant='plain'):
     """The library on the same case with the same (masked) upstream weight -> dict like the oracle's.  ops.FUSED_FORWARD / FUSED_BACKWARD are
-    the caller's to set."""
+    the caller's to set.  variant: how the maps are stored (stored_maps); 'bins' also hands the pass its texture-space bins."""
     from dbw_amd import ops
     from dbw_amd.structures import PackedScene
     DEV = 'cuda:0'
     c = render_case(name)
     scene = c['scene']
-    maps = scene['maps']
-    desc, _ = PackedScene.describe_maps([m.shape[:2] for m in maps], [(0, 0)] * len(maps), DEV)
+    maps, shapes, pads, shift = stored_maps(c, variant)
+    desc, n_floats = PackedScene.describe_maps(shapes, [pads] * len(maps), DEV, shift=shift)
     flat = torch.cat([m.reshape(-1) for m in maps]).detach().to(DEV)
+    assert flat.numel() == n_floats
     ps = PackedScene(scene['verts'].detach().to(DEV), scene['faces'].to(torch.int32).to(DEV), scene['face_uvs'].float().to(DEV),
                      scene['face_map'].to(torch.int32).to(DEV), desc, flat)
     ps.verts.requires_grad_(True)
     ps.maps.requires_grad_(True)
     fa = None if c['faces_alpha'] is None else c['faces_alpha'].detach().to(DEV).requires_grad_(True)
-    cfg = ops.RenderCfg(c['H'], c['W'], c['K'], c['sigma'], 0.001, True, c['detach_bary'], scene['faces'].shape[0], lds_aggregate=lds,
+    texbins = None
+    if variant == 'bins':
+        assert not lds and ops.TEXTURE_BINS
+        texbins = PackedScene.describe_bins(shapes, DEV)
+    cfg = ops.RenderCfg(c['H'], c['W'], c['K'], c['sigma'], 0.001, True, c['detach_bary'], scene['faces'].shape[0], lds_aggregate=lds, texbins=texbins,
                         clip_inside=c['clip_inside'], const_faces=c['const_faces'])
     img = ops.render_scene(ps.verts, ps.maps, fa, ps.faces, c['R'].to(DEV), c['T'].to(DEV), c['Kmat'].to(DEV), ps.face_uvs, ps.face_map,
                            ps.map_desc, ops.make_bg(c['bg']), cfg)
@@ -305,11 +375,13 @@ def hip_render(name, w, lds):
     return res
 
 
-def render_three_ways(name, weight='all', lds=False, seed=0, hip=True):
-    """_render_both of tests/test_gpu_parity.py with a third leg: {tensor: (hip or None, oracle fp32, oracle fp64)} and the reference record."""
+def render_three_ways(name, weight='all', lds=False, seed=0, hip=True, variant='plain'):
+    """_render_both of tests/test_gpu_parity.py with a third leg: {tensor: (hip or None, oracle fp32, oracle fp64)} and the reference record.
+    variant: the library renders from the maps as stored_maps keeps them, and both oracle map gradients are brought into that form."""
     ref = render_refs(name, weight, seed)
-    got = hip_render(name, ref['w'], lds) if hip else {}
+    got = hip_render(name, ref['w'], lds, variant) if hip else {}
     out = {t: (got.get(t), ref['o32'][t], ref['o64'][t]) for t in TENSORS if t in ref['o64']}
+    out['g_maps'] = (out['g_maps'][0],) + tuple(stored_map_grads(render_case(name), g, variant) for g in out['g_maps'][1:])
     # the image on the pixels of M only (elsewhere the evaluations may have picked different faces)
     out['image'] = tuple(None if i is None else i.detach().cpu().double() * ref['M'].double() for i in out['image'])
     return out, ref

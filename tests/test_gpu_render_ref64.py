@@ -88,27 +88,34 @@ VARIANTS = [(True, False), (True, True), (False, False)]        # (ops.FUSED_FOR
 
 def _render_params():
     out = []
-    for name in R64.RENDER_CASES:
+    for name in R64.PLAIN_CASES:
         for fused, lds in VARIANTS:
             if name == 'const_faces' and not fused:             # const_faces is a switch of the fused hard backward kernels
                 continue
-            out.append((name, 'all', fused, lds))
+            out.append((name, 'all', fused, lds, 'plain'))
     for name in ('soft6', 'sigmoid6'):                            # the colour and the opacity branch of the blend backward, each alone
         for weight in ('rgb', 'alpha'):
-            out += [(name, weight, fused, lds) for fused, lds in VARIANTS]
-    return out
+            out += [(name, weight, fused, lds, 'plain') for fused, lds in VARIANTS]
+    # the texel-gradient accumulators as the training phases use them (R64.RENDER_VARIANTS; fused kernels only): full-resolution maps through
+    # the texture-space bins, decimated maps through the LDS table and through the wave-aggregated atomics
+    out += [(name, 'all', True, False, 'bins') for name in R64.RENDER_VARIANTS['bins']]
+    out += [(name, 'all', True, lds, 'decimated') for name in R64.RENDER_VARIANTS['decimated'] for lds in (True, False)]
+    return [pytest.param(*p, id='-'.join(str(v) for v in (p if p[4] != 'plain' else p[:4]))) for p in out]
 
 
-@pytest.mark.parametrize('name,weight,fused,lds', _render_params(), ids=lambda v: str(v))
-def test_render_pass_equals_float64(name, weight, fused, lds, monkeypatch, record_property):
+@pytest.mark.parametrize('name,weight,fused,lds,variant', _render_params())
+def test_render_pass_equals_float64(name, weight, fused, lds, variant, monkeypatch, record_property):
     """project -> clip -> raster -> shade -> blend and back at 48x64 (and 45x61, no multiple of a tile), three views: the soft block pass for
     every compiled faces_per_pixel bucket, the fine pass (sigma 5e-6, no opacities), the hard environment pass in both rigs (attached
     barycentrics, z clipping live), the sigmoid opacity of clip_inside=False with detached barycentrics, and const_faces; fused kernels on
     uv-fragments / hard uv-fragments, with LDS aggregation and with atomics, and the operator-level kernels.  The upstream weight is
-    zero on pixels where the fp32 and the fp64 oracle decide differently (none at these sizes; at most 2 %, host test)."""
+    zero on pixels where the fp32 and the fp64 oracle decide differently (none at these sizes; at most 2 %, host test).
+    Variants 'bins' and 'decimated': the same bar on the texel paths of a training step -- unpadded 32x32 and 64x64 maps through the
+    texture-space bins (records + dbw_texbin_reduce; wrapped footprints through the atomic fallback), cell-resolution maps with shift 2
+    through LdsAgg and through the wave-aggregated atomics; the float64 gradient of a cell is the oracle's summed over the cell."""
     monkeypatch.setattr(ops, 'FUSED_FORWARD', fused)
     monkeypatch.setattr(ops, 'FUSED_BACKWARD', fused)
-    res, ref = R64.render_three_ways(name, weight, lds=lds)
+    res, ref = R64.render_three_ways(name, weight, lds=lds, variant=variant)
     assert 'g_verts' in res and 'g_maps' in res
     failed = []
     for t, (hip, o32, o64) in res.items():

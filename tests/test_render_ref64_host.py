@@ -82,6 +82,41 @@ def test_render_cases_hold_their_preconditions(name, weight, record_property):
         assert sky_only.any() and float(res['g_verts'][2][sky_only].abs().max()) == 0 and float(R64.render_refs('env_horizon')['o64']['g_verts'][sky_only].abs().max()) > 0
 
 
+@pytest.mark.parametrize('variant,name', [(v, n) for v, names in R64.RENDER_VARIANTS.items() for n in names])
+def test_render_variants_hold_their_preconditions(variant, name, record_property):
+    """The 'bins' and 'decimated' variants of tests/test_gpu_render_ref64.py: the same preconditions with the map gradient in the form the
+    variant stores its maps in, and what makes the variant more than the plain case -- footprints that wrap around the unpadded map, maps of
+    several bins whose borders carry gradient, cells that are exactly the upsampled copy's."""
+    res, ref = R64.render_three_ways(name, 'all', hip=False, variant=variant)
+    ys = _y_all({t: (v[1], v[2]) for t, v in res.items()})
+    for t, y in ys.items():
+        record_property(f'y_{t}', round(y, 4))
+    print(variant, name, {t: round(y, 3) for t, y in ys.items()}, 'masked', ref['masked'])
+    assert max(ys.values()) <= R64.Y_CAP, ys
+    assert ref['masked'] <= R64.MAX_MASKED_PIXELS
+    c = R64.render_case(name)
+    maps, shapes, pads, shift = R64.stored_maps(c, variant)
+    g32, g64 = res['g_maps'][1], res['g_maps'][2]
+    assert g64.dtype == torch.float64 and g64.numel() == g32.numel() == sum(m.numel() for m in maps) and float(g64.abs().max()) > 0
+    assert abs(float(g64.sum()) - float(ref['o64']['g_maps'].sum())) <= 1e-9 * float(ref['o64']['g_maps'].abs().sum())    # nothing lost in the folding
+    if variant == 'bins':
+        assert shift == 0 and all(m.shape[:2] == s for m, s in zip(maps, shapes))
+        if c['pads'] != (0, 0):
+            # some footprints lie in the padding: the unpadded map sees them wrapped (the bins' atomic fallback)
+            pl, pr = c['pads']
+            at, in_pad = 0, 0.0
+            for m in c['scene']['maps']:
+                g = ref['o64']['g_maps'][at:at + m.numel()].reshape(m.shape)
+                at += m.numel()
+                in_pad += float(g[:, :pl].abs().sum() + g[:, m.shape[1] - pr:].abs().sum())
+            assert in_pad > 0
+        if name == 'soft6_ts64':
+            g = g64.reshape(len(maps), 64, 64, 3)
+            assert shapes[0] == (64, 64) and all(float(g[:, a:b, :].abs().sum()) > 0 and float(g[:, :, a:b].abs().sum()) > 0 for a, b in ((31, 32), (32, 33)))
+    else:
+        assert shift == R64.SHIFT and all(m.shape[0] << shift == s[0] and m.shape[1] << shift == s[1] for m, s in zip(maps, shapes))
+
+
 @pytest.mark.parametrize('stream', [0, 1, 2])
 def test_rasterize_bwd_raw_converts_fp32_upstream_for_fp64_faces(stream):
     """O.rasterize_bwd_raw used to pass data_ptr() of temporaries: with float64 face_verts and float32 upstream the three converted tensors
