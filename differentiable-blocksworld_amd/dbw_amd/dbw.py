@@ -979,7 +979,7 @@ class DifferentiableBlocksWorld(nn.Module):
     def _surface_tables(self, nb, ground, dev):
         """Constant tables of the term for `nb` packed blocks: faces (F,3) int32 into [ground vertices, block vertices], the groups' face
         offsets, each vertex's row of the opacities (-1 on the ground), a one for the ground's entry of group_keep.  The faces index the
-        vertices by construction (asserted once, here, on the host)."""
+        vertices by construction (asserted once, here, on the host).  Fifth: each group's row of the opacities (-1 for the ground)."""
         key = (nb, ground, str(dev))
         cache = self.__dict__.setdefault('_surface_table_cache', {})
         if key not in cache:
@@ -991,8 +991,36 @@ class DifferentiableBlocksWorld(nn.Module):
             fg = torch.tensor(([0, len(gf)] if ground else [0]) + [len(gf) + (k + 1) * self.BNF for k in range(nb)], dtype=torch.int32)
             vg = torch.cat([torch.full((ngv,), -1), torch.arange(nb).repeat_interleave(nv)]).to(torch.int32)
             assert faces.numel() and 0 <= int(faces.min()) and int(faces.max()) < len(vg)
-            cache[key] = (faces.to(dev), fg.to(dev), vg.to(dev), torch.ones(1, dtype=torch.int32, device=dev))
+            ga = torch.tensor(([-1] if ground else []) + list(range(nb)), dtype=torch.int32)
+            cache[key] = (faces.to(dev), fg.to(dev), vg.to(dev), torch.ones(1, dtype=torch.int32, device=dev), ga.to(dev))
         return cache[key]
+
+    def _posed_term_scene(self, c, what, dev):
+        """What a term on the posed meshes (`what`: its name in the message, c: its config) measures against: the vertex tensors the last
+        build_env_scene / build_blocks_scene produced and their constant tables -> (verts (V,3) fp32, faces, face_group, vert_group,
+        keep or None, nb), or None when no face is left."""
+        ground_v = getattr(self, '_surface_ground_v', None) if c['ground'] else None
+        block_v = getattr(self, '_surface_block_v', None)
+        if c['ground'] and ground_v is None:
+            raise RuntimeError(f'the {what} term reads the vertices of the scene the forward built: call the model, not compute_losses alone')
+        if ground_v is None and block_v is None:
+            return None
+        nb = 0 if block_v is None else block_v.reshape(-1, self._block_nv, 3).shape[0]
+        faces, face_group, vert_group, one, _ = self._surface_tables(nb, ground_v is not None, dev)
+        parts = [v.reshape(-1, 3) for v in (ground_v, block_v) if v is not None]
+        verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        keep = self._keep_mask if (self.sync_free and nb) else None
+        if keep is not None and ground_v is not None:
+            keep = torch.cat([one, keep.to(torch.int32)])
+        return verts.float().contiguous(), faces, face_group, vert_group, None if keep is None else keep.contiguous(), nb
+
+    def _term_step(self, counter):
+        """The step a term's draw is numbered by: the trainer's, or -- a model stepped by hand -- the term's own count of training losses."""
+        step = getattr(self, '_rng_step', None)
+        if step is None:
+            step = self.__dict__.setdefault(counter, 0)
+            setattr(self, counter, step + 1)
+        return int(step)
 
     def _surface_term(self, dev):
         """weight * the term on the vertex tensors the last build_env_scene / build_blocks_scene produced (no second sq_blocks launch)."""
@@ -1008,27 +1036,13 @@ class DifferentiableBlocksWorld(nn.Module):
             # (before start_epoch; and in eval mode: the term is a training signal, an evaluation neither pays for the nearest-neighbour search
             # over the cloud nor counts the term in its L_tot -- loss_surface is then 0)
             return torch.zeros((), device=dev)
-        ground_v = getattr(self, '_surface_ground_v', None) if c['ground'] else None
-        block_v = getattr(self, '_surface_block_v', None)
-        if c['ground'] and ground_v is None:
-            raise RuntimeError('the surface term reads the vertices of the scene the forward built: call the model, not compute_losses alone')
-        if ground_v is None and block_v is None:          # no face left: every point is at tau
+        scene = self._posed_term_scene(c, 'surface', dev)
+        if scene is None:                                 # no face left: every point is at tau
             return torch.full((), wgt * c['tau'] ** 2, device=dev)
-        nb = 0 if block_v is None else block_v.reshape(-1, self._block_nv, 3).shape[0]
-        faces, face_group, vert_group, one = self._surface_tables(nb, ground_v is not None, dev)
-        parts = [v.reshape(-1, 3) for v in (ground_v, block_v) if v is not None]
-        verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-        keep = self._keep_mask if (self.sync_free and nb) else None
-        if keep is not None and ground_v is not None:
-            keep = torch.cat([one, keep.to(torch.int32)])
-        back = c['back'] if nb else 0.0
-        step = getattr(self, '_rng_step', None)
-        if step is None:                                  # a model stepped by hand: its own count of training losses
-            step = self.__dict__.setdefault('_surface_calls', 0)
-            self._surface_calls = step + 1
-        return ops.surface_term(pts, verts.float().contiguous(), faces, face_group, None if keep is None else keep.contiguous(),
-                                self._alpha.float().contiguous() if nb else None, vert_group, n_points=min(c['points'], 1 << 24), tau=c['tau'],
-                                back=back, seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=int(step),
+        verts, faces, face_group, vert_group, keep, nb = scene
+        return ops.surface_term(pts, verts, faces, face_group, keep, self._alpha.float().contiguous() if nb else None, vert_group,
+                                n_points=min(c['points'], 1 << 24), tau=c['tau'], back=c['back'] if nb else 0.0,
+                                seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=self._term_step('_surface_calls'),
                                 weight=wgt, back_count=float(self.n_blocks * self._block_nv))
 
     # ------------------------------------------------------------------------------------------------ the free-space term
@@ -1071,31 +1085,15 @@ class DifferentiableBlocksWorld(nn.Module):
         if self.cur_epoch + 1 < c['start_epoch'] or not self.training:
             # (before start_epoch; and in eval mode: the term is a training signal, an evaluation does not count it in its L_tot)
             return torch.zeros((), device=dev)
-        ground_v = getattr(self, '_surface_ground_v', None) if c['ground'] else None
-        block_v = getattr(self, '_surface_block_v', None)
-        if c['ground'] and ground_v is None:
-            raise RuntimeError('the free-space term reads the vertices of the scene the forward built: call the model, not compute_losses alone')
-        if ground_v is None and block_v is None:          # no face left: no ray is stopped
+        scene = self._posed_term_scene(c, 'free-space', dev)
+        if scene is None:                                 # no face left: no ray is stopped
             return torch.zeros((), device=dev)
-        nb = 0 if block_v is None else block_v.reshape(-1, self._block_nv, 3).shape[0]
-        faces, face_group, _, one = self._surface_tables(nb, ground_v is not None, dev)
-        key = ('group_alpha', nb, ground_v is not None, str(dev))
-        cache = self.__dict__.setdefault('_surface_table_cache', {})
-        if key not in cache:
-            cache[key] = torch.tensor(([-1] if ground_v is not None else []) + list(range(nb)), dtype=torch.int32, device=dev)
-        parts = [v.reshape(-1, 3) for v in (ground_v, block_v) if v is not None]
-        verts = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-        keep = self._keep_mask if (self.sync_free and nb) else None
-        if keep is not None and ground_v is not None:
-            keep = torch.cat([one, keep.to(torch.int32)])
-        step = getattr(self, '_rng_step', None)
-        if step is None:                                  # a model stepped by hand: its own count of training losses
-            step = self.__dict__.setdefault('_freespace_calls', 0)
-            self._freespace_calls = step + 1
-        return ops.freespace_term(ends, self._freespace_frame, self._freespace_origins, verts.float().contiguous(), faces, face_group,
-                                  None if keep is None else keep.contiguous(), cache[key], self._alpha.float().contiguous() if nb else None,
-                                  n_rays=min(c['rays'], 1 << 24), tau=c['tau'], margin=c['margin'],
-                                  seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff, step=int(step), weight=wgt)
+        verts, faces, face_group, _, keep, nb = scene
+        group_alpha = self._surface_tables(nb, bool(c['ground']), dev)[4]
+        return ops.freespace_term(ends, self._freespace_frame, self._freespace_origins, verts, faces, face_group, keep, group_alpha,
+                                  self._alpha.float().contiguous() if nb else None, n_rays=min(c['rays'], 1 << 24), tau=c['tau'],
+                                  margin=c['margin'], seed=int(getattr(self, '_rng_seed', 227391)) & 0x7fffffffffffffff,
+                                  step=self._term_step('_freespace_calls'), weight=wgt)
 
     def compute_losses(self, imgs, rec, layers=None, rgb_value=None, masks=None, mask_count=None, exposure=None):
         """The loss dict of _image_and_regulariser_losses (same arguments), plus -- with surface_weight > 0 -- the surface term

@@ -2046,17 +2046,50 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), e
               float(betas[1]), float(eps), int(step), _stream(param))
 
 
-# ---------------------------------------------------------------------------------------------------------------- the surface term
-def _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count):
-    for t, dt, name in ((points, torch.float32, 'points'), (verts, torch.float32, 'verts'), (faces, torch.int32, 'faces'),
-                        (face_group, torch.int32, 'face_group'), (group_keep, torch.int32, 'group_keep'), (vert_alpha, torch.float32, 'vert_alpha'),
-                        (vert_group, torch.int32, 'vert_group')):
+# ------------------------------------------------- what the surface and free-space terms check and allocate alike (`what`: the term in the messages)
+def _term_tensors(what, tensors, rows3):
+    """tensors: (tensor or None, dtype, name), each a contiguous device tensor of that dtype; rows3: (tensor, 'name (n,3)'), each (n,3)."""
+    for t, dt, name in tensors:
         if t is not None:
             _chk(t, dt, name)
             if not t.is_contiguous():
-                raise RuntimeError(f'surface term: {name} must be contiguous')
-    if points.dim() != 2 or points.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f'surface term: points (N,3), verts (V,3), faces (F,3) expected, got {tuple(points.shape)}, {tuple(verts.shape)}, {tuple(faces.shape)}')
+                raise RuntimeError(f'{what}: {name} must be contiguous')
+    if any(t.dim() != 2 or t.shape[1] != 3 for t, _ in rows3):
+        raise ValueError(f'{what}: {", ".join(n for _, n in rows3)} expected, got {", ".join(str(tuple(t.shape)) for t, _ in rows3)}')
+
+
+def _term_workspace(size_fn_name, what, M, F_, V, G, segment, device):
+    nbytes = getattr(_lib.family('eval'), size_fn_name)(int(M), int(F_), int(V), int(G), int(segment))
+    if nbytes == 0:
+        raise ValueError(f'{what}: sizes M={M}, F={F_}, V={V}, G={G}, segment={segment} are refused (include/dbw_eval.h)')
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+
+
+def _term_faces_host(what, faces_host, faces):
+    if faces_host is not None and (faces_host.dtype != torch.int32 or faces_host.is_cuda or not faces_host.is_contiguous() or faces_host.shape != faces.shape):
+        raise ValueError(f'{what}: faces_host is a contiguous int32 CPU copy of faces')
+
+
+def _term_grads_outputs(size_fn_name, what, records_fn, M, F_, V, G, A, segment, records, workspace, grad_out, device):
+    """-> (grad_verts (V,3), grad_alpha (A,) or None), empty.  The backward's partials are the last part of the workspace and grow with the
+    number of segments: a workspace that the forward sized for another segment length may be too small, and the kernels do not know its size."""
+    need = getattr(_lib.family('eval'), size_fn_name)(int(M), int(F_), int(V), int(G), int(segment))
+    if need == 0 or workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
+        raise ValueError(f'{what}: the workspace has {workspace.numel() * workspace.element_size()} bytes, segment={segment} needs {need}: '
+                         f'give {records_fn} the same segment')
+    if tuple(records.shape) != (M, 4) or records.dtype != torch.int32 or not records.is_contiguous():
+        raise ValueError(f'{what}: records (M,4) int32 of {records_fn} expected, got {tuple(records.shape)} {records.dtype}')
+    if grad_out is not None:
+        _chk(grad_out, torch.float32, 'grad_out')
+    return torch.empty(V, 3, dtype=torch.float32, device=device), (torch.empty(A, dtype=torch.float32, device=device) if A else None)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the surface term (DESIGN.md 6u)
+def _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count):
+    _term_tensors('surface term', ((points, torch.float32, 'points'), (verts, torch.float32, 'verts'), (faces, torch.int32, 'faces'),
+                                   (face_group, torch.int32, 'face_group'), (group_keep, torch.int32, 'group_keep'),
+                                   (vert_alpha, torch.float32, 'vert_alpha'), (vert_group, torch.int32, 'vert_group')),
+                  ((points, 'points (N,3)'), (verts, 'verts (V,3)'), (faces, 'faces (F,3)')))
     N, V, F_, G = points.shape[0], verts.shape[0], faces.shape[0], face_group.numel() - 1
     if group_keep is not None and group_keep.numel() != G:
         raise ValueError(f'surface term: group_keep has {group_keep.numel()} entries for {G} groups')
@@ -2077,10 +2110,7 @@ def _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert
 
 
 def surface_workspace(M, F_, V, G, segment, device):
-    nbytes = _lib.family('eval').dbw_eval_surface_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
-    if nbytes == 0:
-        raise ValueError(f'surface term: sizes M={M}, F={F_}, V={V}, G={G}, segment={segment} are refused (include/dbw_eval.h)')
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+    return _term_workspace('dbw_eval_surface_workspace_bytes', 'surface term', M, F_, V, G, segment, device)
 
 
 def surface_records(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, *, n_points, tau, back, seed, step, back_count=None,
@@ -2094,10 +2124,8 @@ def surface_records(points, verts, faces, face_group, group_keep, vert_alpha, ve
     ws = surface_workspace(M, F_, V, G, segment, dev)
     records = torch.empty(M, 4, dtype=torch.int32, device=dev)
     value = torch.empty(2, dtype=torch.float64, device=dev)
-    if faces_host is not None and (faces_host.dtype != torch.int32 or faces_host.is_cuda or not faces_host.is_contiguous() or faces_host.shape != faces.shape):
-        raise ValueError('surface term: faces_host is a contiguous int32 CPU copy of faces')
+    _term_faces_host('surface term', faces_host, faces)
     with torch.cuda.device(dev):
-        _lib.family('eval')
         _lib.call('dbw_eval_surface_fwd', _ptr(points), N, int(n_points or 0), int(seed), int(step), _ptr(verts), V, _ptr(faces), _ptr(faces_host), F_,
                   _ptr(face_group), _ptr(group_keep), G, _ptr(vert_alpha), _ptr(vert_group), A, bc, float(tau), float(back), int(bool(cull)),
                   _ptr(ws), _ptr(records), _ptr(value), _stream(points))
@@ -2109,21 +2137,9 @@ def surface_grads(points, verts, faces, face_group, group_keep, vert_alpha, vert
     """dbw_eval_surface_bwd on what surface_records left (same arguments, same segment) -> (grad_verts (V,3), grad_alpha (A,) or None), fp32,
     written whole.  grad_out: a one-element fp32 device tensor that multiplies both, or None."""
     N, V, F_, G, A, M, bc = _surface_args(points, verts, faces, face_group, group_keep, vert_alpha, vert_group, n_points, tau, back, back_count)
-    dev = points.device
-    # the backward's partials are the last part of the workspace and grow with the number of segments: a workspace that surface_records
-    # sized for another segment length may be too small, and the kernels do not know its size
-    need = _lib.family('eval').dbw_eval_surface_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
-    if need == 0 or workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
-        raise ValueError(f'surface term: the workspace has {workspace.numel() * workspace.element_size()} bytes, segment={segment} needs {need}: '
-                         'give surface_records the same segment')
-    if tuple(records.shape) != (M, 4) or records.dtype != torch.int32 or not records.is_contiguous():
-        raise ValueError(f'surface term: records (M,4) int32 of surface_records expected, got {tuple(records.shape)} {records.dtype}')
-    if grad_out is not None:
-        _chk(grad_out, torch.float32, 'grad_out')
-    g_verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    g_alpha = torch.empty(A, dtype=torch.float32, device=dev) if A else None
-    with torch.cuda.device(dev):
-        _lib.family('eval')
+    g_verts, g_alpha = _term_grads_outputs('dbw_eval_surface_workspace_bytes', 'surface term', 'surface_records', M, F_, V, G, A, segment, records,
+                                           workspace, grad_out, points.device)
+    with torch.cuda.device(points.device):
         _lib.call('dbw_eval_surface_bwd', _ptr(points), N, int(n_points or 0), int(seed), int(step), _ptr(verts), V, _ptr(faces), F_, G, _ptr(vert_alpha),
                   _ptr(vert_group), A, bc, float(tau), float(back), float(weight), _ptr(grad_out), int(segment), _ptr(records), _ptr(workspace),
                   _ptr(g_verts), _ptr(g_alpha), _stream(points))
@@ -2172,17 +2188,11 @@ FREESPACE_GRAZE = 2.0 ** -16
 
 
 def _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, n_rays):
-    for t, dt, name in ((ends, torch.float32, 'ends'), (frame, torch.int32, 'frame'), (origins, torch.float32, 'origins'), (verts, torch.float32, 'verts'),
-                        (faces, torch.int32, 'faces'), (face_group, torch.int32, 'face_group'), (group_keep, torch.int32, 'group_keep'),
-                        (group_alpha, torch.int32, 'group_alpha'), (vert_alpha, torch.float32, 'vert_alpha')):
-        if t is not None:
-            _chk(t, dt, name)
-            if not t.is_contiguous():
-                raise RuntimeError(f'free-space term: {name} must be contiguous')
-    if (ends.dim() != 2 or ends.shape[1] != 3 or origins.dim() != 2 or origins.shape[1] != 3 or verts.dim() != 2 or verts.shape[1] != 3
-            or faces.dim() != 2 or faces.shape[1] != 3):
-        raise ValueError(f'free-space term: ends (Nr,3), origins (Nf,3), verts (V,3), faces (F,3) expected, got {tuple(ends.shape)}, '
-                         f'{tuple(origins.shape)}, {tuple(verts.shape)}, {tuple(faces.shape)}')
+    _term_tensors('free-space term', ((ends, torch.float32, 'ends'), (frame, torch.int32, 'frame'), (origins, torch.float32, 'origins'),
+                                      (verts, torch.float32, 'verts'), (faces, torch.int32, 'faces'), (face_group, torch.int32, 'face_group'),
+                                      (group_keep, torch.int32, 'group_keep'), (group_alpha, torch.int32, 'group_alpha'),
+                                      (vert_alpha, torch.float32, 'vert_alpha')),
+                  ((ends, 'ends (Nr,3)'), (origins, 'origins (Nf,3)'), (verts, 'verts (V,3)'), (faces, 'faces (F,3)')))
     Nr, Nf, V, F_, G = ends.shape[0], origins.shape[0], verts.shape[0], faces.shape[0], face_group.numel() - 1
     if frame.numel() != Nr:
         raise ValueError(f'free-space term: frame has {frame.numel()} entries for {Nr} rays')
@@ -2196,10 +2206,7 @@ def _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, 
 
 
 def freespace_workspace(M, F_, V, G, segment, device):
-    nbytes = _lib.family('eval').dbw_eval_freespace_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
-    if nbytes == 0:
-        raise ValueError(f'free-space term: sizes M={M}, F={F_}, V={V}, G={G}, segment={segment} are refused (include/dbw_eval.h)')
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+    return _term_workspace('dbw_eval_freespace_workspace_bytes', 'free-space term', M, F_, V, G, segment, device)
 
 
 def freespace_records(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, *, n_rays, tau, margin, seed, step,
@@ -2216,10 +2223,8 @@ def freespace_records(ends, frame, origins, verts, faces, face_group, group_keep
     ws = freespace_workspace(M, F_, V, G, segment, dev)
     records = torch.empty(M, 4, dtype=torch.int32, device=dev)
     value = torch.empty(1, dtype=torch.float64, device=dev)
-    if faces_host is not None and (faces_host.dtype != torch.int32 or faces_host.is_cuda or not faces_host.is_contiguous() or faces_host.shape != faces.shape):
-        raise ValueError('free-space term: faces_host is a contiguous int32 CPU copy of faces')
+    _term_faces_host('free-space term', faces_host, faces)
     with torch.cuda.device(dev):
-        _lib.family('eval')
         _lib.call('dbw_eval_freespace_fwd', _ptr(ends), _ptr(frame), _ptr(origins), Nr, Nf, int(n_rays or 0), int(seed), int(step), _ptr(verts), V,
                   _ptr(faces), _ptr(faces_host), F_, _ptr(face_group), _ptr(group_keep), _ptr(group_alpha), G, _ptr(vert_alpha), A, float(tau),
                   float(margin), int(bool(cull)), int(layout), _ptr(ws), _ptr(records), _ptr(value), _stream(ends))
@@ -2231,20 +2236,9 @@ def freespace_grads(ends, frame, origins, verts, faces, face_group, group_keep, 
     """dbw_eval_freespace_bwd on what freespace_records left (same arguments, same segment) -> (grad_verts (V,3), grad_alpha (A,) or None),
     fp32, written whole.  grad_out: a one-element fp32 device tensor that multiplies both, or None."""
     Nr, Nf, V, F_, G, A, M = _freespace_args(ends, frame, origins, verts, faces, face_group, group_keep, group_alpha, vert_alpha, n_rays)
-    dev = ends.device
-    # (as for the surface term: the backward's partials are the last part of the workspace and grow with the number of segments)
-    need = _lib.family('eval').dbw_eval_freespace_workspace_bytes(int(M), int(F_), int(V), int(G), int(segment))
-    if need == 0 or workspace.numel() * workspace.element_size() < need or not workspace.is_cuda:
-        raise ValueError(f'free-space term: the workspace has {workspace.numel() * workspace.element_size()} bytes, segment={segment} needs {need}: '
-                         'give freespace_records the same segment')
-    if tuple(records.shape) != (M, 4) or records.dtype != torch.int32 or not records.is_contiguous():
-        raise ValueError(f'free-space term: records (M,4) int32 of freespace_records expected, got {tuple(records.shape)} {records.dtype}')
-    if grad_out is not None:
-        _chk(grad_out, torch.float32, 'grad_out')
-    g_verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    g_alpha = torch.empty(A, dtype=torch.float32, device=dev) if A else None
-    with torch.cuda.device(dev):
-        _lib.family('eval')
+    g_verts, g_alpha = _term_grads_outputs('dbw_eval_freespace_workspace_bytes', 'free-space term', 'freespace_records', M, F_, V, G, A, segment,
+                                           records, workspace, grad_out, ends.device)
+    with torch.cuda.device(ends.device):
         _lib.call('dbw_eval_freespace_bwd', _ptr(ends), _ptr(frame), _ptr(origins), Nr, Nf, int(n_rays or 0), int(seed), int(step), _ptr(verts), V,
                   _ptr(faces), F_, G, _ptr(vert_alpha), A, float(tau), float(margin), float(weight), _ptr(grad_out), int(segment), _ptr(records),
                   _ptr(workspace), _ptr(g_verts), _ptr(g_alpha), _stream(ends))

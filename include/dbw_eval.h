@@ -106,6 +106,7 @@ int dbw_eval_cluster_fit(const float *points, int64_t N, int K, const float *ini
  *   back > 0: x_v are the vertices with 0 <= vert_group[v] < A, a = vert_alpha (A) fp32, nn the exact nearest cloud point (dbw_nn_points'
  *     search); back_count the constant n_blocks * vertices per block.  back == 0: value[1] = 0, vert_alpha / vert_group may be NULL.
  *   cull (0 | 1): skip a group whose box is farther than every running best of a wave; records and value do not depend on it.
+ *   A face index outside [0, V) is read as vertex 0 by both calls (faces_host refuses it before any launch).
  * dbw_eval_surface_bwd, on the records and the workspace that dbw_eval_surface_fwd left for the same arguments: with
  *   L = weight * (value[0] + back * value[1]),  grad_verts (V,3) fp32 = grad_out[0] * dL/dverts (-2 b_m (p - c) / M per record inside tau;
  *   2 a_k (x_v - nn) back / back_count per block vertex inside tau), grad_alpha (A) fp32 or NULL = grad_out[0] * dL/da (the sum of the block's

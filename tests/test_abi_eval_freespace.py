@@ -75,6 +75,15 @@ def test_names_exports_and_the_size_query():
     assert q(1000, 248, 135, 4, 0) < q(1000, 248, 1350, 4, 0) and q(1000, 248, 135, 4, 0) < q(1000, 2480, 135, 4, 0) < q(10000, 2480, 135, 4, 0)
 
 
+def test_the_workspace_sizes_are_those_of_the_layout_before_the_shared_header():
+    """(M, F, V, G, segment) -> bytes, read from the library of the commit before csrc/mesh_walk.h laid the common regions down."""
+    q = _lib.family('eval').dbw_eval_freespace_workspace_bytes
+    for args, nbytes in (((1, 1, 3, 1, 0), 208), ((257, 12, 8, 2, 64), 4720), ((1000, 928, 501, 11, 0), 68960),
+                         ((16384, 4128, 2181, 51, 0), 1234400), ((16384, 4128, 2181, 51, 64), 13796960)):
+        assert q(*args) == nbytes, args
+    assert q(0, 1, 3, 1, 0) == 0 and q(1, 1, 3, 1, -1) == 0
+
+
 def _caller(lib, fn, names, good):
     ints = {'Nr', 'Nf', 'n_rays', 'seed', 'step', 'V', 'F', 'G', 'A', 'cull', 'layout', 'segment'}
 

@@ -73,6 +73,15 @@ def test_names_exports_and_the_size_query():
     assert q(1000, 368, 135, 4, 0) < q(1000, 368, 1350, 4, 0) and q(1000, 368, 135, 4, 0) < q(1000, 3680, 135, 4, 0)
 
 
+def test_the_workspace_sizes_are_those_of_the_layout_before_the_shared_header():
+    """(M, F, V, G, segment) -> bytes, read from the library of the commit before csrc/mesh_walk.h laid the common regions down."""
+    q = _lib.family('eval').dbw_eval_surface_workspace_bytes
+    for args, nbytes in (((1, 1, 3, 1, 0), 240), ((257, 12, 8, 2, 64), 1728), ((1000, 928, 501, 11, 0), 63008),
+                         ((16384, 4128, 2181, 51, 0), 1064064), ((16384, 4128, 2181, 51, 64), 13626624)):
+        assert q(*args) == nbytes, args
+    assert q(0, 1, 3, 1, 0) == 0 and q(1, 1, 3, 1, -1) == 0
+
+
 def _caller(lib, fn, names, good):
     ints = {'N', 'n_points', 'seed', 'step', 'V', 'F', 'G', 'A', 'cull', 'segment'}
 

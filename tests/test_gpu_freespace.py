@@ -147,6 +147,28 @@ def test_the_backward_draws_what_the_forward_drew():
         ops.freespace_grads(**d, records=rec, workspace=ws, n_rays=257, weight=2.0, segment=64, **kw)
 
 
+def test_a_face_index_outside_the_vertices_is_vertex_0_to_both_calls():
+    """Without faces_host nothing refuses an index of V: the gather reads it as vertex 0, and the backward gives that corner's gradient to
+    vertex 0 -- records, value and both gradients are the bytes of the same call with the index 0."""
+    from dbw_amd import ops
+    sc, origins, ends, frame = _scene('blocks')
+    kw = dict(n_rays=257, tau=TAU, margin=MARGIN, seed=SEED, step=STEP, segment=64)
+    rec = ops.freespace_records(**_dev(sc, origins, ends, frame), **kw)[0].cpu().numpy()
+    f = int(np.bincount(rec[rec[:, 1] >= 0, 1], minlength=len(sc['faces'])).argmax())    # the face most rays meet first
+    outs = []
+    for index in (0, len(sc['verts'])):
+        faces = sc['faces'].copy()
+        faces[f, 0] = index
+        d = _dev(dict(sc, faces=faces), origins, ends, frame)
+        rec, value, ws = ops.freespace_records(**d, **kw)
+        gv, ga = ops.freespace_grads(**d, records=rec, workspace=ws, weight=2.0, **kw)
+        outs.append([x.cpu().numpy() for x in (rec, value, gv, ga)])
+    rec, b = outs[0][0], outs[0][0][:, 2:].view(np.float32)
+    assert ((rec[:, 1] == f) & (1 - b[:, 0] - b[:, 1] > 0)).any() and np.abs(outs[0][2][0]).max() > 0             # the moved corner carries gradient
+    for x, y in zip(*outs):
+        assert x.tobytes() == y.tobytes()
+
+
 # ---------------------------------------------------------------------------------------------------------------- the term in the model
 def _tiny_model(loss, n_blocks=2, size=(16, 24)):
     from dbw_amd import create_model

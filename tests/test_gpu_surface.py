@@ -145,6 +145,30 @@ def test_the_backward_draws_what_the_forward_drew():
         ops.surface_grads(**d, records=rec, workspace=ws, n_points=257, weight=2.0, segment=64, **kw)
 
 
+def test_a_face_index_outside_the_vertices_is_vertex_0_to_both_calls():
+    """Without faces_host nothing refuses an index of V: the gather reads it as vertex 0, and the backward gives that corner's gradient to
+    vertex 0 -- records, value and both gradients are the bytes of the same call with the index 0."""
+    from dbw_amd import ops
+    sc, cloud = _scene('blocks')
+    kw = dict(n_points=257, tau=TAU, back=BACK, seed=SEED, step=STEP, back_count=_back_count(sc), segment=64)
+    rec = ops.surface_records(**_dev(sc, cloud), **kw)[0].cpu().numpy()
+    inside = rec[:, 0].view(np.float32) < TAU * TAU
+    f = int(np.bincount(rec[inside, 1], minlength=len(sc['faces'])).argmax())           # the face most records inside tau name
+    outs = []
+    for index in (0, len(sc['verts'])):
+        faces = sc['faces'].copy()
+        faces[f, 2] = index
+        d = _dev(dict(sc, faces=faces), cloud)
+        rec, value, ws = ops.surface_records(**d, **kw)
+        gv, ga = ops.surface_grads(**d, records=rec, workspace=ws, weight=2.0, **kw)
+        outs.append([x.cpu().numpy() for x in (rec, value, gv, ga)])
+    rec = outs[0][0]
+    assert ((rec[:, 1] == f) & (rec[:, 0].view(np.float32) < TAU * TAU) & (rec[:, 3].view(np.float32) > 0)).any()      # the moved corner carries gradient
+    assert np.abs(outs[0][2][0]).max() > 0
+    for x, y in zip(*outs):
+        assert x.tobytes() == y.tobytes()
+
+
 # ---------------------------------------------------------------------------------------------------------------- the term in the model
 def _tiny_model(loss, surface=None, n_blocks=2, size=(16, 24)):
     from dbw_amd import create_model
