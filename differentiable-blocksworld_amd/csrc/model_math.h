@@ -89,11 +89,19 @@ struct Pose {
     float T[3];
 };
 
+// The exponent 1.8 sigmoid(x) + 0.1 of a superquadric (dbw.py:343-344): the sum, the division, the product and the sum behind the expf in
+// double, rounded ONCE.  All in float32 these four roundings leave it 2e-7 from its value, and |t|^eps turns an error of the exponent
+// into |log |t|| as much in the point: with a cosine of 1e-5 in the trig table (|log| = 11.5) the block-frame points were 1.6e-6 off --
+// all of it from here, the powf / logf behind it add nothing visible (tests/test_gpu_step_kernels.py:
+// test_prologue_kept_points_equal_float64).  The expf stays float32 (the one sigmoidf evaluates: its 1 ulp weighs 1.8 s (1 - s) <= 0.45)
+// and a double exp would sit on the latency of the step's prologue.  Twice per block.
+DBW_HD float sq_exponent(float x) { return (float)(1.8 / (1.0 + (double)expf(-x)) + 0.1); }
+
 DBW_HD void load_pose(const float *sq_eps, const float *S, const float *R6, const float *T, int k,
                                           float scale_min, Pose &p) {
     if (sq_eps) {
         p.se1 = sigmoidf(sq_eps[k * 2]); p.se2 = sigmoidf(sq_eps[k * 2 + 1]);
-        p.e1 = p.se1 * 1.8f + 0.1f; p.e2 = p.se2 * 1.8f + 0.1f;
+        p.e1 = sq_exponent(sq_eps[k * 2]); p.e2 = sq_exponent(sq_eps[k * 2 + 1]);
     } else { p.se1 = p.se2 = 0.f; p.e1 = p.e2 = 1.f; }
 #pragma unroll
     for (int i = 0; i < 3; ++i) { p.S[i] = S ? expf(S[k * 3 + i]) + scale_min : 1.f; p.T[i] = T[k * 3 + i]; }

@@ -11,6 +11,8 @@
 #include "step_kernels.h"
 #include "../../include/dbw_hip.h"
 
+#include <string.h>
+
 using namespace dbw;
 
 namespace {
@@ -401,6 +403,65 @@ int dbw::launch_regularisers(const RegulariserArgs &A, hipStream_t s) {
     const long long P = (long long)A.nb * A.npts;
     hipLaunchKernelGGL(regularisers_kernel, dim3(overlap ? (unsigned)((P + 255) / 256) : 1u), dim3(256), 0, s, A);
     return dbw_check_launch("regularisers_kernel");
+}
+
+// (tests: the three fused launches of the step, which have no entry point of their own, through their launchers -- flat arguments in the
+// order of the structs of step_kernels.h; tests/test_gpu_step_kernels.py)
+extern "C" int dbw_debug_step_prologue(const dbw_texture_set *sets, int nsets, const float *alpha_logit, const float *noise, float noise_scale, float thresh,
+                                       int nb, float *alpha, float *alpha_full, int32_t *keep, unsigned long long seed, unsigned long long rng_step,
+                                       const float *sq_eps, const float *S, const float *R6, const float *T, const float *trig, int nv, float ratio,
+                                       float scale_min, float S_world, const float *Rw, const float *Tw, float *blk_verts, float *sq_local,
+                                       const float *ground_base, int ngv, const float *R6g, const float *Tg, float *ground_verts, float *zero0, int nzero0,
+                                       dbw_stream_t stream) {
+    DBW_REQUIRE(nsets >= 0 && nsets <= STEP_MAX_SETS && (sets || nsets == 0), "0..4 texture sets");
+    // (Tw, noise and sq_local may be NULL: pose_fwd adds `Tw ? Tw[j] : 0`, as behind dbw_sq_blocks_fwd / dbw_posed_mesh_fwd)
+    DBW_REQUIRE(alpha_logit && alpha && alpha_full && keep && sq_eps && S && R6 && T && trig && Rw && blk_verts && ground_base && R6g && Tg && ground_verts &&
+                (zero0 || nzero0 == 0) && nzero0 >= 0, "null pointer");
+    PrologueArgs P;
+    memset(&P, 0, sizeof(P));
+    for (int k = 0; k < nsets; ++k) P.tex.s[k] = sets[k];
+    P.nsets = nsets;
+    P.alpha_logit = alpha_logit; P.noise = noise; P.noise_scale = noise_scale; P.thresh = thresh; P.nb = nb;
+    P.alpha = alpha; P.alpha_full = alpha_full; P.keep = keep; P.seed = seed; P.rng_step = rng_step;
+    P.sq_eps = sq_eps; P.S = S; P.R6 = R6; P.T = T; P.trig = trig; P.nv = nv;
+    P.ratio = ratio; P.scale_min = scale_min; P.S_world = S_world; P.Rw = Rw; P.Tw = Tw;
+    P.blk_verts = blk_verts; P.sq_local = sq_local;
+    P.ground_base = ground_base; P.ngv = ngv; P.R6g = R6g; P.Tg = Tg; P.ground_verts = ground_verts;
+    P.zero0 = zero0; P.nzero0 = nzero0;
+    return launch_step_prologue(P, (hipStream_t)stream);
+}
+
+extern "C" int dbw_debug_regularisers(const float *u, int npts, unsigned long long seed, unsigned long long rng_step, const float *sq_eps, const float *S,
+                                      const float *R6, const float *T, const float *alpha_full, int nb, float ratio, float scale_min, float inv_temp,
+                                      float thresh, float overlap_scale, float pars_eps, float pars_scale, float *loss_parsimony, float *loss_overlap,
+                                      float *g_sq_eps, float *g_S, float *g_R6, float *g_T, float *g_alpha_full, float *ws, unsigned *ticket,
+                                      dbw_stream_t stream) {
+    DBW_REQUIRE(overlap_scale == 0.f || (sq_eps && S && R6 && T), "null pointer");
+    RegulariserArgs A;
+    memset(&A, 0, sizeof(A));
+    A.u = u; A.npts = npts; A.seed = seed; A.rng_step = rng_step;
+    A.sq_eps = sq_eps; A.S = S; A.R6 = R6; A.T = T; A.alpha_full = alpha_full; A.nb = nb;
+    A.ratio = ratio; A.scale_min = scale_min; A.inv_temp = inv_temp; A.thresh = thresh; A.overlap_scale = overlap_scale;
+    A.pars_eps = pars_eps; A.pars_scale = pars_scale;
+    A.loss_parsimony = loss_parsimony; A.loss_overlap = loss_overlap;
+    A.g_sq_eps = g_sq_eps; A.g_S = g_S; A.g_R6 = g_R6; A.g_T = g_T; A.g_alpha_full = g_alpha_full;
+    A.ws = ws; A.ticket = ticket;
+    return launch_regularisers(A, (hipStream_t)stream);
+}
+
+extern "C" int dbw_debug_blocks_tail(const float *sq_eps, const float *S, const float *R6, const float *T, const float *sq_local, const int32_t *keep, int nb,
+                                     int nv, float scale_min, float S_world, const float *Rw, const float *g_verts, float *g_sq_eps, float *g_S, float *g_R6,
+                                     float *g_T, const float *alpha, const float *g_alpha_parts, const float *g_alpha_full, int alpha_parts, float *g_logit,
+                                     const float *void_raised, float *void_flag, dbw_stream_t stream) {
+    DBW_REQUIRE(!void_flag || void_raised, "void_flag without void_raised");
+    BlocksTailArgs A;
+    memset(&A, 0, sizeof(A));
+    A.sq_eps = sq_eps; A.S = S; A.R6 = R6; A.T = T; A.sq_local = sq_local; A.keep = keep; A.nb = nb; A.nv = nv;
+    A.scale_min = scale_min; A.S_world = S_world; A.Rw = Rw; A.g_verts = g_verts;
+    A.g_sq_eps = g_sq_eps; A.g_S = g_S; A.g_R6 = g_R6; A.g_T = g_T;
+    A.alpha = alpha; A.g_alpha_parts = g_alpha_parts; A.g_alpha_full = g_alpha_full; A.alpha_parts = alpha_parts; A.g_logit = g_logit;
+    A.void_raised = void_raised; A.void_flag = void_flag;
+    return launch_blocks_tail(A, (hipStream_t)stream);
 }
 
 extern "C" int dbw_block_alpha_fwd(const float *alpha_logit, const float *noise, float noise_scale, float mask_threshold, int Kb,

@@ -1,7 +1,14 @@
 // Fused small kernels of the training step (train_step.hip enqueues them).  Each replaces a chain of dependent 5-20 us launches of the
 // operator-level path, or runs two independent ones in one launch: at the reference's batch size (4 views, configs/dtu/default.yml:28) the
 // step is as long as its chain of dependent launches, whatever they compute.  The kernels live next to the kernels they fuse (same device
-// functions, same arithmetic, bit-identical results); this header is their host-side interface.  Internal: not part of the C ABI.
+// functions, same arithmetic); this header is their host-side interface.  Internal: not part of the C ABI.
+// What "same" means, kernel by kernel (tests/test_gpu_step_kernels.py holds each line): step_prologue and blocks_tail are bit-identical to
+// the operator-level kernels they replace.  regularisers: its parsimony term is; the overlap term's value is while the launch has one
+// workgroup (256 sample points: wave sums, a fixed sum of four, one atomic); the overlap term's gradients are wherever the operator-level
+// overlap kernel is bit-identical to ITSELF -- up to 64 sample points, with 64 blocks too.  With more than one wave at work the samples'
+// shares of a block's 18 raw gradients meet in LDS float atomics in the order the waves arrive, and two launches of either kernel differ
+// in the last bits (17 different results in 20 launches at 64 blocks x 4 points): there both are held to float64 on the same bar.  The
+// loss values' kernel has no operator twin: float64 for the sum, exact float32 for the rest.
 //
 //   step_prologue     (model_ops.hip)     block opacities (+ their noise), blocks' vertices, ground vertices, clearing of the small
 //                                         gradients [+ sigmoid / decimation of the three texture tensors when the bins do not take it]

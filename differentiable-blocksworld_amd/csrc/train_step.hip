@@ -83,6 +83,10 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float *__restric
         out5[4] = ((rgb + vals[1]) + tvv) + vals[3];
     }
 }
+int launch_loss_finish(const float *part, long long nparts, float scale, float tv_value_scale, float *vals, float *out5, hipStream_t s) {
+    hipLaunchKernelGGL(loss_finish_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, s, part, nparts, scale, tv_value_scale, vals, out5);
+    return dbw_check_launch("loss_finish_kernel");
+}
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -792,9 +796,7 @@ extern "C" int dbw_train_step_run(dbw_step_plan *p, const dbw_step_inputs *in, d
 
     // ---- Rg: the loss values (nothing is differentiated through them) ----
     auto loss_values = [&](hipStream_t st) -> int {
-        hipLaunchKernelGGL(loss_finish_kernel, dim3(LOSS_BLOCKS), dim3(256), 0, st, FP(L.part), (long long)B * L.tiles, mse_scale,
-                           d.tv_value_scale != 0.f ? d.tv_value_scale : 1.f, vals, FP(L.losses));
-        RC(dbw_check_launch("loss_finish_kernel"));
+        RC(launch_loss_finish(FP(L.part), (long long)B * L.tiles, mse_scale, d.tv_value_scale != 0.f ? d.tv_value_scale : 1.f, vals, FP(L.losses), st));
         // everything of Rg that the other streams wait for is done here: the copy to the host (of values outside the zero arena) is nobody's
         // business but the host's -- behind the signal, so that neither the env chain nor Adam ever waits for a transfer
         if (two) RC(signal(st, F_REG, p->ev_reg));
@@ -1006,6 +1008,12 @@ extern "C" int dbw_train_step_voided_runs(const dbw_step_plan *p) { return p ? p
 
 // (tests: 1 if the last run with Adam in the call ended in the one-launch tail, 0 if in the texture backward + Adam launches; not in the header)
 extern "C" int dbw_debug_train_step_last_tail(const dbw_step_plan *p) { return p ? (p->last_tail ? 1 : 0) : -1; }
+
+// (tests: the loss values' kernel through the launch line the step uses -- vals: 8 floats, out5: 5; not in the header; tests/test_gpu_step_kernels.py)
+extern "C" int dbw_debug_loss_finish(const float *part, int64_t nparts, float scale, float tv_value_scale, float *vals, float *out5, dbw_stream_t stream) {
+    DBW_REQUIRE((part || nparts == 0) && nparts >= 0 && vals && out5, "bad argument");
+    return launch_loss_finish(part, (long long)nparts, scale, tv_value_scale, vals, out5, (hipStream_t)stream);
+}
 
 extern "C" int64_t dbw_train_step_void_flag_offset(const dbw_step_plan *p) { return p ? (int64_t)p->L.losses + 7 * (int64_t)sizeof(float) : -1; }
 

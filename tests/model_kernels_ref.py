@@ -322,6 +322,35 @@ def sq_blocks(sq_eps, S, R6, T, trig, ratio, scale_min, S_world, Rw, Tw, gverts=
     return out
 
 
+def sq_local_points(e, trig, ratio):
+    """The block-frame point of every vertex and its derivatives in the two exponents (superquadric.py:10-14; what the step's prologue keeps
+    for its tail, 9 floats per vertex): e (Kb,2) the exponents, trig (4,Kb,nv) -> loc, de1, de2 (Kb,nv,3), each with M_ = its absolute value
+    (every element is one product)"""
+    e, trig, ratio = f64(e), f64(trig), f32v(ratio)
+    e1, e2 = e[:, 0, None], e[:, 1, None]
+    A, dA = _spow(trig[0], e1); C, dC = _spow(trig[1], e1)
+    Bc, dBc = _spow(trig[2], e2); Bs, dBs = _spow(trig[3], e2)
+    out = dict(loc=np.stack([A * Bs, C, A * Bc], -1) * ratio, de1=np.stack([dA * Bs, dC, dA * Bc], -1) * ratio,
+               de2=np.stack([A * dBs, np.zeros_like(A), A * dBc], -1) * ratio)
+    out.update({'M_' + k: np.abs(v) for k, v in list(out.items())})
+    return out
+
+
+def sq_local(sq_eps, trig, ratio):
+    """sq_local_points at the exponents of sq_eps (dbw.py:343-344)"""
+    return sq_local_points(exponents(sq_eps)[0], trig, ratio)
+
+
+# ---- the loss values of a step (dbw.py:361-408: what compute_losses returns) ---------------------------------------------------------------
+def loss_finish(part, scale, tv_value_scale, vals):
+    """part (n) the per-tile sums of squared differences, vals (8) float32 with parsimony, tv, overlap in slots 1..3 -> rgb = scale sum(part)
+    in float64 (M_rgb: the same over absolute values), and out5 = rgb, parsimony, tv * tv_value_scale, overlap, total in float64"""
+    p, v, scale, tvs = f64(part).reshape(-1), f64(vals), f32v(scale), f32v(tv_value_scale)
+    rgb = scale * p.sum()
+    out5 = np.array([rgb, v[1], v[2] * tvs, v[3], rgb + v[1] + v[2] * tvs + v[3]])
+    return dict(rgb=rgb, M_rgb=abs(scale) * np.abs(p).sum(), sum=p.sum(), M_sum=np.abs(p).sum(), out5=out5)
+
+
 # ---- overlap (dbw.py:389-405; superquadric.py:17-38 with safe=True, as_sdf=2) -----------------------------------------------------------
 def _safe_pow(t, e):
     """clamp(t, 1e-6)^e -> value, d / d t (0 below the clamp), d / d e"""
@@ -561,6 +590,21 @@ def torch_sq_blocks(sq_eps, S, R6, T, trig, ratio, scale_min, S_world, Rw, Tw, g
     return _np(out)
 
 
+def torch_sq_local(sq_eps, trig, ratio, dtype, device):
+    """the block-frame points and their exponent derivatives (sq_local_points) in torch's own operations"""
+    import torch
+    tr, ratio = _t(trig, dtype, device), f32v(ratio)
+    eps = torch.sigmoid(_t(sq_eps, dtype, device)) * 1.8 + 0.1
+    e1, e2 = eps[:, 0:1], eps[:, 1:2]
+
+    def sp(t, e):
+        r = _torch_signed_pow(t, e)
+        return r, torch.where(t == 0, torch.zeros_like(r), r * torch.log(torch.abs(t)))
+    (A, dA), (C, dC), (Bc, dBc), (Bs, dBs) = sp(tr[0], e1), sp(tr[1], e1), sp(tr[2], e2), sp(tr[3], e2)
+    return _np(dict(loc=torch.stack([A * Bs, C, A * Bc], -1) * ratio, de1=torch.stack([dA * Bs, dC, dA * Bc], -1) * ratio,
+                    de2=torch.stack([A * dBs, torch.zeros_like(A), A * dBc], -1) * ratio))
+
+
 def torch_implicit_sdf(pts, e1, e2, w, dtype, device):
     import torch
     p, e = _t(pts, dtype, device, True), torch.tensor([e1, e2], dtype=dtype, device=device, requires_grad=True)
@@ -611,13 +655,31 @@ OVERLAP_CASES = {
     'kb5-below-threshold': (5, 100, 6.0, 0),
 }
 OVERLAP_MARGINS = dict(sum=1e-3, pow=1e-4, inner=1e-4, clamp=1e-4)
+# The cases of the step's fused regularisers launch (tests/test_gpu_step_kernels.py), same conditions on the seed: P = Kb npts at the edges
+# of its 256-point workgroups -- 1; 64 (one full wave: the last size at which the LDS atomics have one order); 255, 256 (one workgroup);
+# 257 (one point in a second one); 64 blocks in one workgroup (the finish runs on `tid < nb` of 256 threads); 64 x 40 = 10 workgroups
+STEP_OVERLAP_CASES = {
+    'kb1-1': (1, 1, 0.3, 10),
+    'kb2-32': (2, 32, 0.6, 6),
+    'kb3-85': (3, 85, 0.3, 1),
+    'kb4-64': (4, 64, 0.6, 0),
+    'kb64-4': (64, 4, 1.95, 0),
+    'kb1-257': (1, 257, 0.5, 0),
+    'kb64-40': (64, 40, 1.95, 0),
+}
+# ... and one case for bit-equality with the operator kernels alone: 64 blocks x 1 sample = one wave, so the LDS atomics have one order and
+# the finish of all 64 blocks (dead ones, the opacities at the parsimony clamp) is compared bit for bit.  Its gradients are NOT held to
+# float64: with one sample per block nothing averages out, and torch's float32 on the CPU reads 2.8e-4 to 1 (a flipped branch) on every one
+# of 80 seeds tried, 9.4e-3 on this one -- above the gradient floor before any kernel runs (overlap_float32_cost).  The branch margins hold.
+STEP_BITWISE_CASES = {'kb64-1': (64, 1, 1.95, 0)}
 
 
 def overlap_case(name):
     """Blocks pulled together so that they overlap (T scaled to 0.15), exponents over the whole range, 6D vectors random and not
     orthonormal; the last block of a case with Kb >= 3 is small and away from the others (its |inv| > 5 clamp masks the other blocks'
     samples' gradients) -- 1.6 from the origin, not further: see overlap_point_rounding; alpha holds an exact 0 when Kb >= 3."""
-    Kb, npts, thresh, seed = OVERLAP_CASES[name]
+    step = {**STEP_OVERLAP_CASES, **STEP_BITWISE_CASES}
+    Kb, npts, thresh, seed = (OVERLAP_CASES.get(name) or step[name])
     rng = np.random.RandomState(1000 + seed)
     c = dict(Kb=Kb, npts=npts, thresh=thresh, scale=1.3, **OVERLAP_CONSTS)
     c['sq_eps'] = (rng.rand(Kb, 2) * 6 - 3).astype(np.float32)
@@ -630,6 +692,8 @@ def overlap_case(name):
         c['S'][-1] = -4.0
         c['T'][-1] = (0.9, -0.8, 1.0)
         c['alpha'][1] = 0.0
+    if name in step and Kb >= 5:        # the parsimony term of the same launch: an opacity exactly at its clamp and one just above it
+        c['alpha'][2], c['alpha'][3] = np.float32(PARSIMONY_EPS), np.nextafter(np.float32(PARSIMONY_EPS), np.float32(1))
     return c
 
 
@@ -655,6 +719,22 @@ def overlap_point_rounding(c, ref=None):
     finally:
         overlap_points = exact
     return max(err(per[k], ref[k], ref['M_' + k], 9 * c['Kb'] * c['npts']) for k in OVERLAP_GRADS)
+
+
+FLOAT32_COST_MARGIN = 0.5             # of the gradient floor
+
+
+def overlap_float32_cost(c, ref=None):
+    """What float32 alone costs the gradients of a case: torch's float32 formulation on the CPU (no kernel in it) against the reference,
+    in `err`.  The fewer samples a case has the less their roundings average out behind occupancy = sigmoid(-sdf / 0.005): of the
+    2 x 32 cases tried for the step's one-wave launch most read 1e-4 to 1e-2 here, some 1 (a sample's branch flips in float32).  A case of
+    STEP_OVERLAP_CASES, and a set of samples the step's generator draws, must keep this below FLOAT32_COST_MARGIN of the gradient floor,
+    so that at least half of the floor is about the kernel."""
+    import torch
+    ref = ref or overlap_ref(c)
+    t = torch_overlap(c['u'], c['sq_eps'], c['S'], c['R6'], c['T'], c['alpha'], c['ratio'], c['scale_min'], c['temperature'], c['thresh'], c['scale'],
+                      torch.float32, 'cpu')
+    return max(err(t[k], ref[k], ref['M_' + k], 9 * c['Kb'] * c['npts']) for k in OVERLAP_GRADS)
 
 
 def well_conditioned(cond):

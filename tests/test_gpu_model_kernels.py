@@ -34,15 +34,17 @@ Measured on the MI355X (the largest of the family's cases; the atomic sums diffe
 logit of 16.6 -- so its error is 1 at the planted +20 and +90 and the bar is the floor.  The kernels did the same until this test: see
 tex_sigmoid(x, one_minus_s) in csrc/texture_body.h.  Overlap, gradient: occupancy = sigmoid(-sdf / 0.005) turns every float32 rounding in
 front of it into 200 x as much in the exponent; torch and the kernel read 1e-5 to 4e-5 alike and the bar is the floor.  The blocks'
-gradient: the error of both sides is 1.8 se (1 - se) of a shape parameter near +8, from the rounded sigmoid.)
+gradient: the error of both sides is 1.8 se (1 - se) of a shape parameter near +8, from the rounded sigmoid.  The rows of the blocks and
+of overlap were measured again after load_pose began to round the exponent once, model_math.h: sq_exponent -- the same to three digits.)
 
 An accumulating output (the gradients of the blocks, the posed mesh, overlap and parsimony; the loss values) is launched twice: from zero,
 so that it is held on the magnitude of its own terms alone, and from half of each element's own magnitude, so that the sum is checked
 without the start value dwarfing what is added (starts()).  Constant start values are used only where the assertion is exact equality.
 
 The tail launch (adam_groups_tex_kernel) is held bit-equal to dbw_texture_prep_bwd_sets + dbw_adam_step_groups in
-tests/test_gpu_step_tail.py; both of those are held to float64 here.  blocks_tail_kernel has no entry point of its own (the C step runs
-it; tests/test_gpu_c_step.py)."""
+tests/test_gpu_step_tail.py; both of those are held to float64 here.  The step's fused model-side kernels (step_prologue_kernel,
+regularisers_kernel, blocks_tail_kernel, loss_finish_kernel) are held to the kernels of this file bit for bit and to the same float64
+references in tests/test_gpu_step_kernels.py."""
 import ctypes
 import math
 

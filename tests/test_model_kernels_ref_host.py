@@ -124,7 +124,41 @@ def test_superquadric_blocks_reference():
           ('verts', 'g_sq_eps', 'g_S', 'g_R6', 'g_T'))
 
 
-@pytest.mark.parametrize('name', list(R.OVERLAP_CASES))
+def test_block_frame_points_and_their_exponent_derivatives_reference():
+    """sq_local_points (what the step's prologue keeps for its tail): d / d eps1 and d / d eps2 against a central float64 difference in the
+    exponent, and the points against the vertices of sq_blocks under the identity pose.  A difference of step h of a function with
+    third derivative f''' is off by h^2 f''' / 6 + rounding 1e-16 / h.  Here f = |t|^e, f''' = f log^3 |t|, and |log|^3 < 1e3 for a cosine
+    down to 1e-4: at h = 1e-5 that is 2e-8 f + 1e-11 -- held to 1e-6 of M, which a derivative wrong in a factor or a sign misses by 1."""
+    sq, S, R6, T, trig, gv = _block_inputs(5, 20, 2)
+    e, _ = R.exponents(sq)
+    ref = R.sq_local_points(e, trig, 0.5)
+    assert not ref['de1'][:, :3].any() and not ref['de2'][:, :3].any() and not ref['de2'][..., 1].any()          # the poles; y does not depend on eps2
+    h = 1e-5
+    for j, key in enumerate(('de1', 'de2')):
+        d = np.zeros((1, 2)); d[0, j] = h
+        fd = (R.sq_local_points(e + d, trig, 0.5)['loc'] - R.sq_local_points(e - d, trig, 0.5)['loc']) / (2 * h)
+        M = ref['M_' + key] + ref['M_loc']          # (a point's own size: where the derivative vanishes the difference still rounds on it)
+        assert float((np.abs(fd - ref[key]) / (M + 1e-300)).max()) <= 1e-6, key          # (M = 0: a coordinate that is exactly 0, its difference too)
+        assert float(np.abs(ref[key]).max()) > 0.05          # not a comparison of zeros
+    # the points themselves: sq_blocks with S = 0 and scale_min = 0 (exp(S) + scale_min = 1), R = 1, T = 0, world = identity
+    ident6 = np.tile(np.array([1, 0, 0, 0, 1, 0], np.float64), (5, 1))
+    v = R.sq_blocks(sq, np.zeros((5, 3)), ident6, np.zeros((5, 3)), trig, 0.5, 0.0, 1.0, np.eye(3), np.zeros(3))
+    assert float(np.abs(v['verts'] - R.sq_local(sq, trig, 0.5)['loc']).max()) <= 1e-12
+    # and through them the shape gradient of sq_blocks: g_sq_eps = sum gloc . de * d eps / d sq_eps is what autograd holds above
+
+
+def test_loss_values_reference():
+    g = rnd(4)
+    part, = f32(g.rand(1000) * 3)
+    vals = np.array([0, 0.25, 1.5, 0.125, 0, 0, 0, 0], np.float32)
+    ref = R.loss_finish(part, 1e-3, 0.5, vals)
+    t = torch.from_numpy(part).double().sum() * R.f32v(1e-3)
+    assert abs(ref['rgb'] - float(t)) <= 1e-12 * ref['M_rgb'] and ref['M_rgb'] == ref['rgb']
+    assert np.array_equal(ref['out5'][1:4], [0.25, 0.75, 0.125]) and abs(ref['out5'][4] - (float(t) + 1.125)) <= 1e-12
+    assert R.loss_finish(np.zeros(0, np.float32), 1e-3, 0.5, vals)['rgb'] == 0
+
+
+@pytest.mark.parametrize('name', list(R.OVERLAP_CASES) + list(R.STEP_OVERLAP_CASES) + list(R.STEP_BITWISE_CASES))
 def test_overlap_reference_and_its_conditioning(name):
     c = R.overlap_case(name)
     ref = R.overlap_ref(c)
@@ -134,8 +168,16 @@ def test_overlap_reference_and_its_conditioning(name):
         assert cond[k] > margin, (name, k, cond[k])
     if name.endswith('below-threshold'):
         assert cond['active'] == 0 and ref['value'] == 0 and all(not ref[k].any() for k in ('g_sq_eps', 'g_S', 'g_R6', 'g_T', 'g_alpha'))
+    elif cond['points'] == 1:
+        assert cond['active'] == 1 and ref['value'] > 1e-3          # (the step's one-point case: that point is above the threshold)
     else:
         assert cond['active'] > 10 and ref['value'] > 1e-3
+    if name in R.STEP_OVERLAP_CASES:                           # ... and float32 as such less than half of it (small cases: few samples to average over)
+        assert R.overlap_float32_cost(c, ref) < R.FLOAT32_COST_MARGIN * R.FLOOR['overlap'][1], name
+    if name in R.STEP_BITWISE_CASES:                           # (held to the operator kernels bit for bit and not to float64: why -- float32 itself is above the floor)
+        assert R.overlap_float32_cost(c, ref) > R.FLOOR['overlap'][1] and c['Kb'] * c['npts'] <= 64, name
+    if name in {**R.STEP_OVERLAP_CASES, **R.STEP_BITWISE_CASES} and c['Kb'] >= 5:          # the parsimony term of the same launch: at its clamp and just above it
+        assert c['alpha'][2] == np.float32(R.PARSIMONY_EPS) and c['alpha'][3] > np.float32(R.PARSIMONY_EPS) and c['alpha'][3] < np.float32(1.000001e-6)
     # what float32 sample points alone cost the gradients, everything else exact: well below the floor, so that the floor is about the kernel
     assert R.overlap_point_rounding(c, ref) < R.POINT_ROUNDING_MARGIN * R.FLOOR['overlap'][1], name
     if c['Kb'] >= 3:
