@@ -330,6 +330,18 @@ class RenderCfg:
         self.detach_bary, self.eps, self.F = detach_bary, eps, F_
 
 
+def _all_geometry(cfg, camera_grads):
+    """The cfg a pass's backward runs under.  const_faces spares the backward the geometry gradient of faces whose vertices are constants (the
+    sky dome): right for the vertex gradient, which nobody reads there -- but a camera or K gradient sums over EVERY face a view shows, and
+    the sky moves in the image with the camera like anything else.  With such a gradient asked for, the same cfg without the skip."""
+    if not camera_grads or not cfg.const_faces:
+        return cfg
+    import copy
+    full = copy.copy(cfg)
+    full.const_faces = 0
+    return full
+
+
 HARD_UV_FRAGMENTS = True  # hard single-layer passes (K = 1, sigma = 0) store (u, v, face|map) per pixel: frag_layout 3
 
 
@@ -433,8 +445,8 @@ class _RenderScene(torch.autograd.Function):
         want_bary = need_geom and not cfg.detach_bary
         g_R = g_T = g_K = None
         if FUSED_BACKWARD and (ctx.tiled or (need_geom and (want_dists or want_bary))):
-            g_maps, g_alpha, g_fvc = _fused_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, cfg, bg, ctx.tiled, g_img.contiguous(),
-                                                R.shape[0], None)
+            g_maps, g_alpha, g_fvc = _fused_bwd(p2f, bary, dists, cl, face_uvs, face_map, map_desc, maps, fa, _all_geometry(cfg, need_cam or need_K), bg,
+                                                ctx.tiled, g_img.contiguous(), R.shape[0], None)
             g_verts = project_clip_bwd(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp) if need_verts else None
             if need_cam:
                 g_R, g_T = _cam_grads(ctx, 4, *project_clip_bwd_cam(verts, faces_i32, R, T, Kmat, cl, g_fvc, cfg.eps, cfg.z_clip, cfg.persp))
@@ -641,7 +653,8 @@ class _DecoupledRenderMSE(torch.autograd.Function):
         gs = go.detach().to(torch.float32).reshape(1).contiguous()
         gm_f, ga, g_fvc_f = _fused_bwd(p2f, bary, dists, cl_f, uv_f, fmap_f, desc_f, mf, fa, cfg_f, bg_f, 2, g_fg, B, gs)
         gv_f = project_clip_bwd(vf, faces_f, R, T, Kmat, cl_f, g_fvc_f, cfg_f.eps, cfg_f.z_clip, cfg_f.persp) if ctx.needs_input_grad[2] else None
-        gm_e, _, g_fvc_e = _fused_bwd(p2f_e, bary_e, dists_e, cl_e, uv_e, fmap_e, desc_e, me, None, cfg_e, bg_e, ctx.lay_e, g_env, B, gs)
+        need_cam = ctx.needs_input_grad[7] or ctx.needs_input_grad[8] or ctx.needs_input_grad[9]
+        gm_e, _, g_fvc_e = _fused_bwd(p2f_e, bary_e, dists_e, cl_e, uv_e, fmap_e, desc_e, me, None, _all_geometry(cfg_e, need_cam), bg_e, ctx.lay_e, g_env, B, gs)
         gv_e = project_clip_bwd(ve, faces_e, R, T, Kmat, cl_e, g_fvc_e, cfg_e.eps, cfg_e.z_clip, cfg_e.persp) if ctx.needs_input_grad[0] else None
         g_R = g_T = None
         if ctx.needs_input_grad[7] or ctx.needs_input_grad[8]:
